@@ -9,13 +9,17 @@ resident in HBM), run CompositeGenerator (SURVEY config 2: ngf 128, 3 down-sampl
 blocks, 512x512), shift the 2-frame FIFO and convert the frame to uint8 (tensor2im) in HBM.
 The HEADLINE (`value`) is the generator WITH its flow branch and flow-warp compositor -- the variant
 that contains every component north_star names (3.32 TFLOP/frame); the no-flow variant (2.57
-TFLOP/frame; what --openpose_only may select upstream) is timed in the same run over the
+TFLOP/frame; what --openpose_only may select upstream) is timed with --full over the
 same K steps and reported in config.variants (`--variant noflow` swaps the roles).  N>1: each rank
 runs its own 64-frame-style chunk (sequence-chunk sharding; weak scaling) and the chunk
 outputs are all-gathered over RCCL inside the timed region.  Weights are random-init (seeded), data
 is synthetic: there is no network for checkpoints.
 
-Prints ONE JSON line (rank 0) with the driver's contract fields plus
+A plain run sets up, warms up, times the K steps of the headline and prints ONE JSON line (rank 0) with the
+driver's contract fields (`value`, `ms_per_step` = milliseconds per timed step, ...) and `box` (the clock during the
+timed steps); --dump-outputs DIR also writes the last timed step's frame and generator output as .npy files.
+With --full the line also holds the other variant and the lock-step batch variants (config.variants), "hires",
+"train_step" and the blocks below (null in a plain run):
   "roofline":     dominant kernel (the batched-GEMM stage of the Winograd F(4x4,3x3) 1024->1024 ResnetBlock
                   conv: 19.3 GFLOP of executed fp32 MFMA work per launch at 512x512) timed with HIP events on
                   the launch stream vs the fp32 MFMA peak (157.3 TFLOP/s); "layer" = the whole conv
@@ -319,6 +323,20 @@ def build_models(dev, flow, scales):
         nets.append(HipGenerator(spec1, dev).load_state_dict(sd1))
         sds.append(sd1)
     return Vid2VidModelG(nets), sds
+
+
+def dump_outputs(out_dir, arrays, budget=64 << 20):
+    """--dump-outputs: each array as out_dir/<name>.npy in float32.  Past `budget` bytes in all, an array is cut to a fixed
+    sample of its elements (seeded; flattened order) so that two runs of the same command write comparable files."""
+    os.makedirs(out_dir, exist_ok=True)
+    share = budget // max(len(arrays), 1) // 4
+    for name, t in arrays.items():
+        a = t.detach().float().cpu().numpy()
+        if a.size > share:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, share, replace=False))
+            a = a.reshape(-1)[idx]
+            print("bench.py: %s.npy holds a fixed sample of %d of its %d elements" % (name, share, t.numel()), file=sys.stderr)
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def time_frames(model, dev, H, W, K, Wm, seed=0):
@@ -907,6 +925,13 @@ def main():
                     help="timed optimiser steps of the `train_step` block (configs[4] per-GPU work; 0 = skip; default geometry only)")
     ap.add_argument("--batch-variants", type=lambda v: [int(x) for x in v.split(",") if x], default=[2, 4],
                     help="lock-step batch sizes timed in addition to the headline (config.variants.batch<N>_fps)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beside the headline: the other variant and the batch variants, roofline, "
+                         "cpu_baseline, e2e, hires and train_step (their options above apply only with --full)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the headline's last timed step computed as DIR/<name>.npy "
+                         "(float32): frame.npy = the uint8 RGB0 frame(s) the step hands over ([world, H, W, 4]; every "
+                         "rank's with N > 1), generator_out.npy = rank 0's fp32 generator output behind it ([H, W, 4])")
     args = ap.parse_args()
 
     from text2video_amd import launch
@@ -971,6 +996,8 @@ def main():
             dist.all_gather_into_tensor(host, frames.cpu())
             gathered.copy_(host)
 
+    last_out = [None]      # sequence 0's fp32 generator output of the latest timed step (for --dump-outputs)
+
     def timed_run(model, sampler=None, nseq=1):
         """W untimed warm-up frames, then exactly K timed steps (+ the all-gather of the chunk's frames for N>1)
         between barrier + synchronize on both sides; returns the MAX over ranks of the elapsed seconds.
@@ -990,6 +1017,7 @@ def main():
             u8s = [ops.tensor2im_u8(o) for o in outs]
             if out_slot is not None:
                 frames[out_slot].copy_(u8s[0])
+                last_out[0] = outs[0]
 
         for t in range(Wm):
             step(t, None)
@@ -1023,9 +1051,13 @@ def main():
     spec = model.nets[0].spec
     sampler = ClockSampler(local_rank)
     elapsed = timed_run(model, sampler)            # the headline: `value`
+    if args.dump_outputs and rank == 0:
+        # before anything else runs on the model: its output buffer still holds the last timed step's frame
+        dump_outputs(args.dump_outputs, {"frame": gathered.view(world, K, H, W, 4)[:, K - 1] if dist else frames[K - 1:K],
+                                         "generator_out": last_out[0]})
     other = other_elapsed = None
     batch_elapsed = {}
-    if not args.single_variant:
+    if args.full and not args.single_variant:
         # the same model advancing 2 / 4 independent sequences in lock-step (t2v_generator_forward_batch): aggregate rate
         # over all sequences, reported in config.variants -- `value` stays the single-sequence figure
         for nb in args.batch_variants:
@@ -1044,10 +1076,10 @@ def main():
                 return gflop_per_frame(H, W, flow)
         gf = gflops(head_flow)
         g0h, g0w = (H // 2, W // 2) if args.scales == 2 else (H, W)   # G0 runs on the half-resolution pyramid level
-        roofline = gemm_stage_roofline(dev, sd, g0h, g0w, args.kernel_iters, sampler)
+        roofline = gemm_stage_roofline(dev, sd, g0h, g0w, args.kernel_iters, sampler) if args.full else None
         # ---- CPU baseline: the oracle on this box's host cores, bounded sample ----
         cpu = None
-        if args.cpu_frames > 0 and world == 1:   # reported at N=1 only (rank 0)
+        if args.full and args.cpu_frames > 0 and world == 1:   # reported at N=1 only (rank 0)
             from oracle.generator_ref import CompositeGenerator, Vid2VidInferenceRef
             cores = torch.get_num_threads()
             ref_net = CompositeGenerator(9, 3, 6, 128, 3, 9, spec.no_flow, "batch")
@@ -1103,7 +1135,7 @@ def main():
                    "value_8_threads": round(by_threads[8], 4) if 8 in by_threads else None, "parity": parity}
         # ---- end to end: the drop-in test.py frame loop on a dataset in the reference's layout ----
         e2e = None
-        if args.e2e_frames > 0 and world == 1 and args.scales == 1:
+        if args.full and args.e2e_frames > 0 and world == 1 and args.scales == 1:
             e2e = run_e2e(model, other, head_flow, args.e2e_frames)
             if default_geometry and not args.no_cold_start:
                 e2e["cold_start"] = cold_start_block(utterance=True)
@@ -1118,7 +1150,8 @@ def main():
         if batch_elapsed:
             variants["batch_note"] = "batch<N>_fps: N sequences in lock-step, aggregate"
         variants["headline"] = "flow" if head_flow else "noflow"
-        variants["note"] = "both variants timed in this run over K steps; `value` = headline"
+        if other_elapsed is not None:
+            variants["note"] = "both variants timed in this run over K steps; `value` = headline"
         result = {
             "metric": "frames/sec 512x512 pose->RGB (vid2vid generator)",
             "value": round(fps, 3), "unit": "frames/s", "n_gpus": world, "steps": K, "warmup": Wm,
@@ -1139,9 +1172,9 @@ def main():
                        "variants": variants},
             "roofline": roofline, "cpu_baseline": cpu, "e2e": e2e, "box": sampler.summary(),
         }
-        if args.hires_frames > 0 and world == 1 and default_geometry:
+        if args.full and args.hires_frames > 0 and world == 1 and default_geometry:
             result["hires"] = hires_block(dev, args.hires_frames, 4, args.kernel_iters, sampler)
-    if args.train_steps > 0 and default_geometry:
+    if args.full and args.train_steps > 0 and default_geometry:
         del model, other
         torch.cuda.empty_cache()
         # (RCCL prints its version banner through C stdio when a group is created: fd 1 points at stderr meanwhile, so that

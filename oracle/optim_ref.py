@@ -13,6 +13,8 @@ def adam_041_step(p, g, m, v, lr, b1, b2, eps, step):
     bias corrections are folded into the step size -- modern torch divides sqrt(v) by sqrt(bias_correction2) first."""
     m.mul_(b1).add_(g, alpha=1 - b1)                         # exp_avg.mul_(beta1).add_(1 - beta1, grad)
     v.mul_(b2).addcmul_(g, g, value=1 - b2)                  # exp_avg_sq.mul_(beta2).addcmul_(1 - beta2, grad, grad)
-    denom = v.sqrt().add_(eps)                               # denom = exp_avg_sq.sqrt().add_(group['eps'])
+    # denom = exp_avg_sq.sqrt().add_(group['eps']), the square root rounded correctly (taken in fp64): torch's own fp32 CPU
+    # sqrt is not on every host (1 ulp off for ~17 % of inputs on one), the golden steps' was
+    denom = v.double().sqrt().to(v.dtype).add_(eps)
     step_size = lr * (1 - b2 ** step) ** 0.5 / (1 - b1 ** step)
     p.addcdiv_(m, denom, value=-step_size)                   # p.data.addcdiv_(-step_size, exp_avg, denom)

@@ -10,8 +10,8 @@ has() { case " $what " in *" $1 "*) return 0;; esac; return 1; }
 if has bench; then
   # 1. the default bench line (what the driver runs); then the headline variant ALONE under the profiler
   #    (--single-variant --batch-variants "": the dominant kernel's AVERAGE in the CSV is the line's roofline.ms_per_launch)
-  python bench.py > $O/bench.json 2> $O/bench.err
-  rocprofv3 --kernel-trace --stats --output-format csv -d $O/bench_prof -o bench -- python bench.py --single-variant --batch-variants "" --cpu-frames 0 --e2e-frames 0 --hires-frames 0 --train-steps 0 > $O/bench_profiled_single.json 2> $O/bench_prof.err
+  python bench.py --full > $O/bench.json 2> $O/bench.err
+  rocprofv3 --kernel-trace --stats --output-format csv -d $O/bench_prof -o bench -- python bench.py --full --single-variant --batch-variants "" --cpu-frames 0 --e2e-frames 0 --hires-frames 0 --train-steps 0 > $O/bench_profiled_single.json 2> $O/bench_prof.err
   cp $(find $O/bench_prof -name "*kernel_stats.csv" | head -1) $O/bench_kernel_stats_single.csv
   rm -rf $O/bench_prof
 fi

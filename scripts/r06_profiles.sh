@@ -11,8 +11,8 @@ if has bench; then
   # the default bench line (what the driver runs), then the headline variant ALONE under the profiler with 2 + 1 frames only:
   # the dominant kernel's rows in the CSV are then the roofline loops' own launches (in two-stream frames a launch shares its
   # CUs with the other stream's kernels and takes 170-190 us), their average is the line's roofline.ms_per_launch
-  python bench.py > $O/bench.json 2> $O/bench.err
-  rocprofv3 --kernel-trace --stats --output-format csv -d $O/bench_prof -o bench -- python bench.py --single-variant --batch-variants "" --steps 2 --warmup 1 --cpu-frames 0 --e2e-frames 0 --hires-frames 0 --train-steps 0 > $O/bench_profiled_single.json 2> $O/bench_prof.err
+  python bench.py --full > $O/bench.json 2> $O/bench.err
+  rocprofv3 --kernel-trace --stats --output-format csv -d $O/bench_prof -o bench -- python bench.py --full --single-variant --batch-variants "" --steps 2 --warmup 1 --cpu-frames 0 --e2e-frames 0 --hires-frames 0 --train-steps 0 > $O/bench_profiled_single.json 2> $O/bench_prof.err
   cp $(find $O/bench_prof -name "*kernel_stats.csv" | head -1) $O/bench_kernel_stats_single.csv
   rm -rf $O/bench_prof
 fi

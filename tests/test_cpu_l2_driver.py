@@ -90,11 +90,9 @@ def test_utterance_key():
     assert L.utterance_key("今天天气好极了，不冷。", L.PINYIN) == "今天天气好极了不冷"
     assert L.utterance_key("你好啊", L.PINYIN) == "你好啊"
     assert L.utterance_key("a b", L.PINYIN) == "a b"                   # the pinyin driver keeps spaces
-    zhon = "/root/reference/venv_vid2vid/lib/python3.7/site-packages/zhon/hanzi.py"
-    if os.path.exists(zhon):                                          # build container only: the table itself
-        ns = {}
-        exec(compile(open(zhon, encoding="utf-8").read(), zhon, "exec"), ns)
-        assert set(ns["punctuation"]) == set(L.HANZI_PUNCTUATION)
+    # the table itself: zhon.hanzi.punctuation of the reference's environment, stored as UTF-8 text
+    with open(os.path.join(HERE, "golden", "zhon_hanzi_punctuation.txt"), encoding="utf-8", newline="") as f:
+        assert set(f.read()) == set(L.HANZI_PUNCTUATION)
 
 
 def test_long_gap_structure_and_smoothing_properties():

@@ -269,15 +269,18 @@ def test_train_dataset_sampling(tmp_path):
 
 def test_oracle_vgg19_taps_match_the_references_torchvision():
     """oracle.generator_ref.VGG19Features against taps produced by the reference's own vendored torchvision
-    vgg19 (tests/golden/make_vgg_golden.py imports it from /root/reference): same seeded weights and input."""
+    vgg19 (tests/golden/make_vgg_golden.py imports it from the reference's environment): same seeded weights and input.
+    The oracle runs in fp64, so that the golden taps' own fp32 rounding is all that differs, whichever fp32 convolution
+    kernels the host CPU would pick (those alone moved a tap by 1.2x the tolerance on one host)."""
     import numpy as np
     from oracle.generator_ref import VGG19Features
     from text2video_amd.train import vgg19_random_state_dict
     gold = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "vgg19_taps.npz"))
     net = VGG19Features().eval()
     net.load_state_dict(vgg19_random_state_dict(int(gold["seed"])))
+    net = net.double()
     with torch.no_grad():
-        taps = net(torch.from_numpy(gold["x"]))
+        taps = net(torch.from_numpy(gold["x"]).double())
     assert len(taps) == 5
     for i, t in enumerate(taps):
         ref = gold["tap%d" % i]

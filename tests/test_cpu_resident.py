@@ -10,6 +10,18 @@ import threading
 import pytest
 
 
+@pytest.fixture
+def sock_tmp():
+    """a directory with a short path for the sockets: AF_UNIX paths stop at 107 bytes, and pytest's tmp_path (with a long
+    user name or TMPDIR in it, plus t2v_resident/<key>.sock) can be longer"""
+    import pathlib
+    import shutil
+    import tempfile
+    d = tempfile.mkdtemp(prefix="t2v", dir="/tmp")
+    yield pathlib.Path(d)
+    shutil.rmtree(d, ignore_errors=True)
+
+
 def _fake_server(path, reply_frames, seen):
     srv = socket.socket(socket.AF_UNIX, socket.SOCK_STREAM)
     srv.bind(path)
@@ -33,9 +45,9 @@ def _fake_server(path, reply_frames, seen):
     return t
 
 
-def test_client_streams_the_servers_output_and_returns_its_status(tmp_path, monkeypatch, capsys):
+def test_client_streams_the_servers_output_and_returns_its_status(sock_tmp, monkeypatch, capsys):
     from text2video_amd import resident
-    path = str(tmp_path / "s.sock")
+    path = str(sock_tmp / "s.sock")
     monkeypatch.setattr(resident, "socket_path", lambda argv: path)
     monkeypatch.setenv("T2V_STREAMS", "1")
     seen = []
@@ -49,9 +61,9 @@ def test_client_streams_the_servers_output_and_returns_its_status(tmp_path, monk
     assert seen[0]["env"].get("T2V_STREAMS") == "1" and all(k.startswith("T2V_") for k in seen[0]["env"])
 
 
-def test_client_reports_a_lost_connection_and_does_not_start_a_server_just_to_stop_it(tmp_path, monkeypatch, capsys):
+def test_client_reports_a_lost_connection_and_does_not_start_a_server_just_to_stop_it(sock_tmp, monkeypatch, capsys):
     from text2video_amd import resident
-    path = str(tmp_path / "s.sock")
+    path = str(sock_tmp / "s.sock")
     monkeypatch.setattr(resident, "socket_path", lambda argv: path)
     assert resident.client(["--resident_stop"]) == 0                      # nothing running: nothing to do, nothing spawned
     assert not os.path.exists(path)
@@ -124,11 +136,11 @@ def test_run_dir_is_private_and_refuses_a_planted_one(tmp_path, monkeypatch):
     assert victim.read_text() == "keep"
 
 
-def test_client_takes_over_when_the_server_says_lean_unsupported(tmp_path, monkeypatch, capsys):
+def test_client_takes_over_when_the_server_says_lean_unsupported(sock_tmp, monkeypatch, capsys):
     """a checkpoint the torch-free server cannot read: the status frame tells the client to run the command itself (None), where
     vid2vid/test.py's LeanUnsupported handling starts it over with torch"""
     from text2video_amd import resident
-    path = str(tmp_path / "s.sock")
+    path = str(sock_tmp / "s.sock")
     monkeypatch.setattr(resident, "socket_path", lambda argv: path)
     seen = []
     t = _fake_server(path, [(b"e", b"resident: x.pth: refusing global -- the client runs this one itself\n"),
@@ -138,10 +150,10 @@ def test_client_takes_over_when_the_server_says_lean_unsupported(tmp_path, monke
     assert "the client runs this one itself" in capsys.readouterr().err
 
 
-def test_two_simultaneous_first_calls_start_one_server(tmp_path, monkeypatch):
+def test_two_simultaneous_first_calls_start_one_server(sock_tmp, monkeypatch):
     """the spawn is serialised by a lock file: the second caller finds the first one's server instead of starting its own"""
     from text2video_amd import resident
-    monkeypatch.setenv("XDG_RUNTIME_DIR", str(tmp_path))
+    monkeypatch.setenv("XDG_RUNTIME_DIR", str(sock_tmp))
     path = os.path.join(resident.run_dir(), "k.sock")
     monkeypatch.setattr(resident, "socket_path", lambda argv: path)
     spawned, seen = [], []

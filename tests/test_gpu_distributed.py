@@ -20,7 +20,7 @@ def test_bench_runs_its_rccl_path_on_one_rank():
     all_gather_into_tensor of the chunk's uint8 frames, MAX all-reduce of the elapsed time."""
     env = dict(os.environ, CUDA_VISIBLE_DEVICES="0", T2V_BENCH_FORCE_DIST="1", MASTER_ADDR="127.0.0.1", MASTER_PORT="29533",
                HSA_ENABLE_IPC_MODE_LEGACY="0")
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "4", "--warmup", "2",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "1", "--steps", "4", "--warmup", "2",
                         "--cpu-frames", "0", "--kernel-iters", "2", "--e2e-frames", "0", "--single-variant",
                         "--hires-frames", "0", "--train-steps", "2"],
                        cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
@@ -291,7 +291,7 @@ def test_bench_two_ranks_on_one_gpu_contract():
     weak scaling, no cpu_baseline / e2e legs (those are N = 1 only)."""
     env = dict(os.environ, CUDA_VISIBLE_DEVICES="0", T2V_DIST_BACKEND="gloo")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-           "--master-port", "29561", os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "6", "--warmup", "2",
+           "--master-port", "29561", os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--steps", "6", "--warmup", "2",
            "--kernel-iters", "2", "--single-variant", "--train-steps", "1", "--train-ngf", "32"]
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stdout[-1500:] + r.stderr[-3000:]

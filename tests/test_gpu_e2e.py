@@ -313,7 +313,7 @@ def test_bench_contract_line():
     """bench.py prints ONE JSON line with the driver's contract fields plus roofline and cpu_baseline."""
     import json
     env = dict(os.environ, CUDA_VISIBLE_DEVICES="0")
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "4", "--warmup", "2",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "1", "--steps", "4", "--warmup", "2",
                         "--cpu-frames", "1", "--kernel-iters", "4", "--e2e-frames", "12", "--hires-frames", "3", "--train-steps", "2"],
                        cwd=ROOT, env=env,
                        capture_output=True, text=True, timeout=900)
@@ -405,6 +405,32 @@ def test_bench_contract_line():
     assert len(t["kernels"]) == 3 and all(0.05 < k["frac"] < 1.0 for k in t["kernels"])
     assert all(np.isfinite(v) for v in t["losses"].values()) and "G_GAN" in t["losses"] and "D_f" in t["losses"]
     assert len(lines[0]) < 7200, len(lines[0])       # the driver keeps a bounded tail of stdout: the line stays compact
+
+
+def test_bench_plain_run_times_the_headline_only_and_dumps_its_last_step(tmp_path):
+    """bench.py without --full: the contract line of the headline alone (no other variant, no roofline / cpu_baseline / e2e /
+    hires / train_step); --dump-outputs writes the last timed step's frame and generator output, the same in two runs."""
+    import json
+    env = dict(os.environ, CUDA_VISIBLE_DEVICES="0")
+    dumps = []
+    for run in range(2):
+        out = tmp_path / ("out%d" % run)
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "5", "--warmup", "2",
+                            "--dump-outputs", str(out)], cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+        lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1 and r.stdout.rstrip().endswith(lines[0])
+        d = json.loads(lines[0])
+        assert d["steps"] == 5 and d["warmup"] == 2 and d["dtype"] == "f32" and d["unit"] == "frames/s"
+        assert d["higher_is_better"] is True and abs(d["value"] - 1e3 / d["ms_per_step"]) <= 0.01 * d["value"] and d["value"] > 30.0
+        assert d["roofline"] is None and d["cpu_baseline"] is None and d["e2e"] is None
+        assert "hires" not in d and "train_step" not in d and set(d["config"]["variants"]) == {"flow_fps", "headline"}
+        frame, g = np.load(out / "frame.npy"), np.load(out / "generator_out.npy")
+        assert frame.dtype == np.float32 and frame.shape == (1, 512, 512, 4) and g.dtype == np.float32 and g.shape == (512, 512, 4)
+        assert np.array_equal(frame, np.round(frame)) and frame.min() >= 0 and frame.max() <= 255 and frame[..., :3].std() > 0
+        assert np.abs(frame[0, ..., :3] - (g[..., :3] + 1) / 2 * 255).max() <= 1.0       # tensor2im of that output
+        dumps.append((frame, g))
+    assert all(np.array_equal(a, b) for a, b in zip(*dumps))       # same arguments, same inputs: the same outputs
 
 
 def test_lockstep_sequences_write_the_same_files_as_one_at_a_time(tmp_path):

@@ -66,7 +66,7 @@ def test_bench_gpus_8_plain_command_contract_line():
     device), barrier + MAX-over-ranks timing, ONE JSON line from rank 0; the configs[4] block runs a real 8-rank bucketed
     exchange (narrow nets: 1.5 GB through host-staged gloo takes minutes) and reports the replicas in sync."""
     port = _free_port()
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--steps", "6", "--warmup", "2",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "8", "--steps", "6", "--warmup", "2",
                         "--kernel-iters", "2", "--single-variant", "--train-steps", "1", "--train-ngf", "32"],
                        cwd=ROOT, env=_plain_env(port), capture_output=True, text=True, timeout=1500)
     assert r.returncode == 0, r.stdout[-1500:] + r.stderr[-3000:]
