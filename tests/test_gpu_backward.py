@@ -361,6 +361,7 @@ def test_transposed_winograd_data_gradient_matches_autograd(H, W, Cin, Cout, t2v
         err_full = (ref - want[b]).abs().max().item() / scale
         print("%dx%d C%d->%d image %d: transposed algorithm %.2e, full-correlation form %.2e (relative to max|dx|)"
               % (H, W, Cin, Cout, b, err, err_full))
+        assert err_full <= 2e-5, "the yardstick: the full-correlation form's own error %.2e" % err_full
         assert err <= 2e-5 and err <= 4 * err_full + 1e-6
     # the GEMM stage on the fixed grid (reading its rows out of the batch-wide matrix: row pitch != rows used) gives the
     # same bits as one block per tile -- forced here, the tile count of these shapes is below the grid

@@ -7,6 +7,8 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import kernel_variants as kv
+
 pytestmark = pytest.mark.gpu
 
 TOL = 1e-4
@@ -258,12 +260,15 @@ def test_fullsize_resblock_conv_1024():
 
 
 REPEAT_CASES = [
-    # name, H, W, Cin, Cout, k, stride, pad, pad_mode, transposed, stats, launches
-    ("head_7x7_cout3_fullsize", 512, 512, 128, 3, 7, 1, 3, 1, False, False, 60),   # small-Cout tile, 3-slot ring
-    ("resblock_1024_fullsize", 64, 64, 1024, 1024, 3, 1, 1, 1, False, True, 30),   # 128x128 tile, 3-slot ring
-    ("convT_256_fullsize", 256, 256, 256, 128, 3, 2, 1, 0, True, True, 20),        # 4 phases, 2-slot ring
-    ("stem_7x7_cin9_fullsize", 512, 512, 9, 128, 7, 1, 3, 1, False, True, 20),     # MODE 1 loader
-    ("resblock_64x40_quarter_tiles", 64, 40, 1024, 1024, 3, 1, 1, 1, False, True, 30),  # 64x64 tiles
+    # name, H, W, Cin, Cout, k, stride, pad, pad_mode, transposed, stats, launches, the kernel it runs (asserted below)
+    ("head_7x7_cout3_fullsize", 512, 512, 128, 3, 7, 1, 3, 1, False, False, 60, kv.head(128)),       # dedicated head kernel
+    ("resblock_1024_fullsize", 64, 64, 1024, 1024, 3, 1, 1, 1, False, True, 30,
+     kv.igemm("L", 0, True, True, 3)),                                                               # 256 blocks: 3-slot ring
+    ("convT_256_fullsize", 256, 256, 256, 128, 3, 2, 1, 0, True, True, 20,
+     kv.igemm("L", 0, True, False, 2)),                                                              # 4 x 512 blocks: 2-slot ring
+    ("stem_7x7_cin9_fullsize", 512, 512, 9, 128, 7, 1, 3, 1, False, True, 20, kv.stem(12, 4, 9)),    # halo-in-LDS stem kernel
+    ("resblock_64x40_quarter_tiles", 64, 40, 1024, 1024, 3, 1, 1, 1, False, True, 30,
+     kv.igemm("Q", 0, True, True, 2)),                                                               # 64x64 tiles
 ]
 
 
@@ -271,9 +276,10 @@ REPEAT_CASES = [
 def test_conv_bitwise_repeatable_race_screen(case):
     """Race screen for the LDS-DMA pipeline (counted vmcnt + raw barriers): the same launch must
     reproduce its first result bit for bit, output and norm partials, on NaN-poisoned buffers.
-    (Caught a real bug: loader waves issuing fewer DMA instructions than the vmcnt count assumed.)"""
+    (Caught a real bug: loader waves issuing fewer DMA instructions than the vmcnt count assumed.)  The first launch runs
+    under the profiler: the case screens the kernel instantiation it names, and no other direct conv kernel."""
     from text2video_amd import ops
-    name, H, W, Cin, Cout, k, stride, pad, pad_mode, transposed, stats, launches = case
+    name, H, W, Cin, Cout, k, stride, pad, pad_mode, transposed, stats, launches, kernel = case
     dev = _dev()
     desc = ops.conv_desc(H, W, Cin, Cout, k, stride, pad, pad_mode, transposed,
                          ops.ACT_TANH if Cout == 3 else ops.ACT_NONE)
@@ -285,7 +291,12 @@ def test_conv_bitwise_repeatable_race_screen(case):
     ho, wo = ops.conv_out_dims(desc)
     ycs = Cout if Cout % 4 == 0 else 4
     sb = ops.conv_stats_buffer(desc, dev) if stats else None
-    ref = ops.conv2d(x, pw, b, desc, y_cs=ycs, stats=sb).clone()
+    torch.cuda.synchronize()
+    with torch.profiler.profile(activities=[torch.profiler.ProfilerActivity.CUDA]) as prof:
+        ref = ops.conv2d(x, pw, b, desc, y_cs=ycs, stats=sb).clone()
+        torch.cuda.synchronize()
+    ran = {kv.normalise(e.name) for e in prof.events() if "t2v::" in e.name}
+    assert {n for n in ran if kv.family(n).startswith("conv_")} == {kernel}, sorted(ran)
     ref_s = sb.clone() if stats else None
     assert torch.isfinite(ref).all()
     for i in range(launches):
@@ -681,6 +692,12 @@ def test_polyphase_winograd_matches_torch_and_the_direct_kernel(case, t2v_env):
     ws = ops.winograd_workspace(dp, Cin, dev)
     scale = ref.abs().max().item()
     e0 = (y0.double() - ref).abs().max().item()
+    # the yardstick itself first: the direct kernel within the fp64 bound of a K-term fp32 sum (tests/kernel_variants.py)
+    K = (4 if tr else 9) * Cin + 1
+    A = (torch.nn.functional.conv_transpose2d(xr.abs(), w.double().abs(), b.double().abs(), stride=2, padding=1, output_padding=1)
+         if tr else torch.nn.functional.conv2d(xr.abs(), w.double().abs(), b.double().abs(), stride=2, padding=1))[0].permute(1, 2, 0)
+    excess = ((y0.double() - ref).abs() / kv.sum_bound(A, K)).max().item()
+    assert excess <= 1.0, "direct kernel: worst |y - r| / fp64 bound = %.3g" % excess
     for rep in range(3):
         ws.fill_(float("nan"))
         sp.fill_(float("nan"))
