@@ -163,6 +163,9 @@ int t2v_conv_best_algo(const t2v_conv_desc* d, int x_cs, int cap);
  * hand-over area of the fixed-grid GEMM stage (blocks that share a 128x128 tile pass accumulators through it; any
  * content on entry, one workspace per conv in flight) */
 size_t t2v_conv_winograd_workspace_floats(const t2v_conv_desc* d, int x_cs);
+/* ... of t2v_conv2d_forward_winograd_batch_stages for `nimg` packed images (F(4x4,3x3); nimg 1 for the other forms):
+ * V and M of pad(nimg * T) rows per position, then the hand-over area; 0 where the form does not take the shape */
+size_t t2v_conv_winograd_batch_workspace_floats(const t2v_conv_desc* d, int x_cs, int nimg);
 /* GEMM rows one image contributes per F(4x4,3x3) transform position: its ceil(H/4) x ceil(W/4) tiles padded to the
  * 64 / 128-row granule (the slot pitch of the batch-wide tile lists in the weight-gradient workspace) */
 int t2v_conv_winograd_tile_rows(const t2v_conv_desc* d);
@@ -184,6 +187,16 @@ int t2v_conv2d_forward_winograd(t2v_ctx* ctx, void* stream, const t2v_conv_desc*
 int t2v_conv2d_forward_winograd_stages(t2v_ctx* ctx, void* stream, const t2v_conv_desc* d, const float* x, int x_cs,
                                        const float* w_packed, const float* bias, float* y, int y_cs,
                                        float* stats_partial, float* workspace, int stages);
+/* ... of the generator's forms (tests): `nimg` F(4x4,3x3) images `img_stride` floats apart, packed into one tile list
+ * (image i owns GEMM rows [i*T, (i+1)*T), the last one also the padding rows; y and the statistics partials image after
+ * image), and with mean_rstd ([nimg][Cin][2]) the previous layer's instance norm applied inside the input transform:
+ * F(4x4): relu 1 gives d = relu((x - mean) * rstd [* gamma + beta]); relu 0 with res and xout (pad 1) gives
+ * d = norm(x) + res, written to xout as well.  A polyphase desc takes one image, relu 0 | 1 and no res / xout. */
+int t2v_conv2d_forward_winograd_batch_stages(t2v_ctx* ctx, void* stream, const t2v_conv_desc* d, int nimg, const float* x,
+                                             int x_cs, long img_stride, const float* w_packed, const float* bias, float* y,
+                                             int y_cs, float* stats_partial, float* workspace, int stages,
+                                             const float* mean_rstd, const float* gamma, const float* beta, int relu,
+                                             const float* res, float* xout);
 
 /* ------------------------------------------------------------------------------------------
  * Instance norm (+affine) + ReLU + residual.  Replaces BatchNormalization_updateOutput(train)

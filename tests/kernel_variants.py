@@ -1,19 +1,18 @@
 """Which test reaches which compiled kernel instantiation, and the float64 yardstick those tests use.
 
-A plain helper module (no fixtures, no pytest hooks), imported by tests/test_cpu_kernel_variants.py and
-tests/test_gpu_kernel_variants.py.
+A plain helper module (no fixtures, no pytest hooks), imported by tests/test_cpu_kernel_variants.py,
+tests/test_gpu_kernel_variants.py and tests/test_gpu_pipeline_variants.py.
 
 TABLE maps every `t2v::` kernel instantiation of libt2v_hip.so (the `__device_stub__` symbols, names normalised by
 normalise()) to one of
-  * Cases(...)       the ids of CONV_CASES below -- tests/test_gpu_kernel_variants.py runs each one, asserts with the
-                     profiler that exactly this instantiation of its family ran, and compares with float64 elementwise;
+  * Cases(...)       the ids of CONV_CASES or PIPE_CASES below -- tests/test_gpu_kernel_variants.py and
+                     tests/test_gpu_pipeline_variants.py run each one, assert with the profiler that exactly this
+                     instantiation of its family ran, and compare with float64 elementwise;
   * Existing(...)    node ids of tests that compare this instantiation's own output, at operator level, with a
                      reference (torch / autograd / float64 / an exact identity).  Those in tests/test_gpu_kernel_variants.py
                      also assert with the profiler that the kernel ran; the others were seen to launch it in a profiled
                      run of the suite.  Bit-for-bit twins and end-to-end frame or train-step tests do not count;
-  * Uncovered(...)   a reachable instantiation with no such test yet -- said plainly, not presented as covered.  Most are
-                     forms of the Winograd / polyphase pipelines, which still want pinned float64 cases with the
-                     transform-pipeline bound;
+  * Uncovered(...)   a reachable instantiation with no such test yet -- said plainly, not presented as covered;
   * Unreachable(...) a reason read off the dispatch code (launch_pad, launch_conv_igemm, build_conv_plan,
                      run_conv_batch) for why no call selects the instantiation.
 """
@@ -284,6 +283,515 @@ def stats_bounds(r, bnd, parts):
     return m, s, e_m, e_s
 
 
+# ---- the Winograd / polyphase pipelines: float64 stage references and their bounds ------------------------------------
+# Each reference takes the fp32 buffers the kernel actually read (its own V, U, M, dV, dU out of the workspace) and returns
+# the stage's output in float64; each bound is derived from the arithmetic the kernel does (winograd.hip, polyphase.hip,
+# conv_igemm.hip, conv_wgrad.hip) and written next to its formula.  gamma(n) = n u / (1 - n u): a value that went through n
+# roundings, each relative to what it rounded, is within gamma(n) of the exact result times the magnitudes it was formed
+# from; chains compose as gamma(a) + gamma(b) + gamma(a) gamma(b) <= gamma(a + b).
+import os
+
+_CSRC = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "text2video_amd", "csrc")
+TINY = 2.0 ** -149      # one flushed or subnormal result per rounding
+
+
+def gamma(n):
+    return n * U / (1 - n * U)
+
+
+def read_consts(path):
+    """{name: float64 tensor} of the `constexpr double kX[r][c] = {...};` tables of a generated header"""
+    src = open(path).read()
+    out = {}
+    for m in re.finditer(r"constexpr double (\w+)\[(\d+)\]\[(\d+)\] = \{(.*?)\};", src, re.S):
+        name, r, c, body = m.group(1), int(m.group(2)), int(m.group(3)), m.group(4)
+        vals = []
+        for tok in re.findall(r"-?[\d.]+(?:\s*/\s*[\d.]+)?", body):
+            num, _, den = tok.partition("/")
+            vals.append(float(num) / (float(den) if den else 1.0))
+        assert len(vals) == r * c, (name, len(vals))
+        out[name] = torch.tensor(vals, dtype=torch.float64).view(r, c)
+    return out
+
+
+F4 = read_consts(os.path.join(_CSRC, "winograd_f4_consts.h"))          # kAT 4x6, kG 6x3, kBT 6x6
+PP = read_consts(os.path.join(_CSRC, "polyphase_consts.h"))             # kBD 9x9, kGD 9x3, kAD 4x9, kBU 9x5, kGU 9x3, kAU 8x9
+# F(2x2,3x3): written out in winograd.hip's comments and code, not in a header
+F2 = {"kAT": torch.tensor([[1., 1., 1., 0.], [0., 1., -1., -1.]], dtype=torch.float64),
+      "kG": torch.tensor([[1., 0., 0.], [.5, .5, .5], [.5, -.5, .5], [0., 0., 1.]], dtype=torch.float64),
+      "kBT": torch.tensor([[1., 0., -1., 0.], [0., 1., 1., 0.], [0., -1., 1., 0.], [0., 1., 0., -1.]], dtype=torch.float64)}
+
+
+def nnz_rows(m):
+    """the longest cdot chain of a transform matrix applied row by row: its most nonzeros in one row (zero taps are skipped
+    at compile time, winograd.hip: cdot)"""
+    return int((m != 0).sum(1).max())
+
+
+def pad_tiles(T):
+    """wino_pad_tiles (t2v_internal.h): 64 or 128 multiple"""
+    a, b = -(-T // 64) * 64, -(-T // 128) * 128
+    return a if (b - a) * 8 >= b else b
+
+
+def patch_index(n, tiles, step, size, start, reflect):
+    """[tiles, size] source indices and validity of the patch rows (or columns) the input kernels read: row step*t - start + k;
+    reflected as |i| then min(i, 2n - 2 - i) clamped at 0 (past the reflected border: a ragged tile's masked outputs), or
+    zero outside [0, n)"""
+    i = torch.arange(tiles)[:, None] * step - start + torch.arange(size)[None, :]
+    if reflect:
+        j = i.abs()
+        return torch.clamp(torch.minimum(j, 2 * n - 2 - j), min=0), torch.ones_like(i, dtype=torch.bool)
+    ok = (i >= 0) & (i < n)
+    return i.clamp(0, n - 1), ok
+
+
+def gather_patches(x, rows, cols):
+    """x [H, W, C] -> [TH, P, TW, Q, C] patches (zeros where the index is not valid)"""
+    (ry, oky), (rx, okx) = rows, cols
+    d = x[ry.reshape(-1)][:, rx.reshape(-1)].view(ry.shape[0], ry.shape[1], rx.shape[0], rx.shape[1], x.shape[-1])
+    m = (oky[:, :, None, None] & okx[None, None, :, :]).to(d.dtype)
+    return d * m[..., None]
+
+
+def transform_in(d, BL, BR=None):
+    """V[p*Q'+q][tile][c] = (BL d BR^T)[p][q] of patches d [TH, P, TW, Q, C] -> [P' Q', TH TW, C]"""
+    BR = BL if BR is None else BR
+    v = torch.einsum("ia,jb,yaxbc->ijyxc", BL, BR, d)
+    return v.reshape(BL.shape[0] * BR.shape[0], d.shape[0] * d.shape[2], d.shape[-1])
+
+
+def wino_input64(x, H, W, pad, reflect, m=4, BT=None, d=None):
+    """F(m x m, 3x3) input transform of x [H, W, C] (fp32 values) in float64: [pos][T][C] over the real tiles.  The tile grid
+    covers the output (H + 2 pad - 2) x (W + 2 pad - 2); patch rows m*t - pad ... m*t - pad + m + 1.  d: the map the
+    patches are cut from, if not x itself (the normalised map of the lazy modes)."""
+    BT = (F4 if m == 4 else F2)["kBT"] if BT is None else BT
+    Ho, Wo = H + 2 * pad - 2, W + 2 * pad - 2
+    TH, TW = -(-Ho // m), -(-Wo // m)
+    src = x if d is None else d
+    p = gather_patches(src, patch_index(H, TH, m, m + 2, pad, reflect), patch_index(W, TW, m, m + 2, pad, reflect))
+    return transform_in(p, BT), TH, TW
+
+
+def input_bound(Aabs, n, e_d=None):
+    """Input transform: two cdot levels (rows, then columns), each a chain of <= n roundings (the product by a dyadic
+    constant and n - 1 additions): |V - V64| <= gamma(2n) |B^T| |d| |B| = gamma(2n) Aabs.  Lazy forms: d itself carries the
+    elementwise error e_d of forming it in fp32, carried through |B^T| . |B| (transform_in of e_d, passed in already
+    transformed) and rounded on the way: + (1 + gamma(2n)) e_d."""
+    b = gamma(2 * n) * Aabs + 2 * n * TINY
+    return b if e_d is None else b + (1 + gamma(2 * n)) * e_d
+
+
+def lazy_d64(x, mean_rstd, gamma_=None, beta=None, relu=False, res=None):
+    """d = [relu]((x - mean) * rstd [* gamma + beta]) [+ res] in float64 from the fp32 operands, and its elementwise error
+    bound in fp32: x - mean (1 rounding), * rstd (2), * gamma (3), + beta (4), + res (5); each rounding is relative to the
+    value it rounds, all of which are <= |x - mean| rstd |gamma| + |beta| (+ |res|); ReLU is 1-Lipschitz: e_d <= gamma(5) (that
+    sum).  x [.., C], mean_rstd [C, 2]."""
+    m, r = mean_rstd[:, 0].double(), mean_rstd[:, 1].double()
+    t = (x.double() - m) * r
+    mag = (x.double() - m).abs() * r
+    if gamma_ is not None:
+        t = t * gamma_.double() + beta.double()
+        mag = mag * gamma_.double().abs() + beta.double().abs()
+    if relu:
+        t = t.clamp(min=0)
+    if res is not None:
+        t = t + res.double()
+        mag = mag + res.double().abs()
+    return t, gamma(5) * mag + 5 * TINY
+
+
+def weight64(w, G, transposed_layout=False, flip=False):
+    """U[pos][n][c] = (G g G^T) of the torch-layout weight: w [Cout][Cin][3][3], or [Cin][Cout][3][3] (transposed_layout:
+    the adjoint / ConvTranspose2d layouts, U[.][n][c] from w[c][n]); flip rotates each 3x3 by 180 degrees"""
+    g = w.double()
+    if transposed_layout:
+        g = g.transpose(0, 1)
+    if flip:
+        g = g.flip(-1).flip(-2)
+    u = torch.einsum("ia,jb,ncab->ijnc", G, G, g)
+    return u.reshape(G.shape[0] ** 2, g.shape[0], g.shape[1])
+
+
+def weight_bound(U64, Aabs):
+    """F(4x4) and polyphase weight transforms run in fp64 and round once (winograd4_weight_store, polyphase_weight_kernel):
+    |U - U64| <= u |U64| + 2^-149, plus the fp64 chain itself (<= 6 roundings of 2^-53 relative to |G| |g| |G^T| = Aabs)"""
+    return U * U64.abs() + TINY + 8 * 2.0 ** -53 * Aabs
+
+
+def weight_bound_f2(Aabs):
+    """F(2x2) weight transform in fp32 (winograd_weight_kernel): per level 0.5 * (g0 + g1 + g2): 2 roundings (the halving is
+    exact), two levels: gamma(4) |G| |g| |G^T|"""
+    return gamma(4) * Aabs + 4 * TINY
+
+
+def gemm64(V, Ub):
+    """M[pos][t][n] = V[pos][t] . U[pos][n]^T in float64 (on V's device).  V [pos][T][K], Ub [pos][N][K]."""
+    return torch.bmm(V.double(), Ub.double().transpose(1, 2))
+
+
+def gemm_bound(V, Ub, K):
+    """the batched GEMMs are K-term MFMA sums: sum_bound(|V| |U|^T, K) with C_DIRECT (conv_igemm.hip; the stream-K forms add
+    one block's partial to another's, which is one more order of the same K terms)"""
+    return sum_bound(torch.bmm(V.double().abs(), Ub.double().abs().transpose(1, 2)), K)
+
+
+def output64(M, A, TH, TW, Ho, Wo, bias):
+    """y = A M A^T + bias per tile, M [pos][T][N] (real tiles) -> y [Ho, Wo, N] (ragged tiles cropped); also returns the same
+    on |M|, |bias| (the magnitude the bound scales)"""
+    e, k = A.shape
+    N = M.shape[-1]
+    m = M.double().view(k, k, TH, TW, N)
+    y = torch.einsum("ia,jb,abyxn->yixjn", A, A, m).reshape(TH * e, TW * e, N)[:Ho, :Wo] + bias.double()
+    a = torch.einsum("ia,jb,abyxn->yixjn", A.abs(), A.abs(), m.abs()).reshape(TH * e, TW * e, N)[:Ho, :Wo] + bias.double().abs()
+    return y, a
+
+
+def output_bound(Aabs, n, slope=None):
+    """output transform: two cdot levels of <= n roundings, then + bias: gamma(2n + 1) (|A| |M| |A^T| + |bias|).
+    With the LeakyReLU of winograd4_output_kernel (v < 0 ? v * slope : v, slope <= 1: 1-Lipschitz, so a v and v64 on two
+    sides of 0 differ after it by no more than before) the product by the slope is one more rounding: gamma(2n + 2)."""
+    k = 2 * n + 1 if slope is None else 2 * n + 2
+    return gamma(k) * Aabs + k * TINY
+
+
+def leaky64(y, slope):
+    return torch.where(y < 0, y * slope, y)
+
+
+def dy64(dy, Ho, Wo):
+    """winograd4_dy_kernel: Md[a*6+b][tile][n] = (A dy A^T)[a][b] = sum_ij AT[i][a] dy[i][j] AT[j][b] over the 4x4 dy tile
+    (zeros outside the map).  dy [Ho, Wo, N] float64 -> [36][T][N], and the same on |dy|."""
+    AT = F4["kAT"]
+    TH, TW = -(-Ho // 4), -(-Wo // 4)
+    d = torch.zeros(TH * 4, TW * 4, dy.shape[-1], dtype=torch.float64, device=dy.device)
+    d[:Ho, :Wo] = dy
+    d = d.view(TH, 4, TW, 4, -1)
+    A = AT.to(dy.device)
+    f = lambda t, M: torch.einsum("ia,jb,yixjn->abyxn", M, M, t).reshape(36, TH * TW, -1)
+    return f(d, A), f(d.abs(), A.abs())
+
+
+def dy_bound(Aabs, e_d=None):
+    """A dy A^T: rows then columns, each a chain of <= n = 4 roundings (a column of A^T has <= 4 nonzeros): gamma(8) |A| |dy|
+    |A^T|; the NORM form adds the error of the gradient it forms (dy_front64), carried through |A| . |A^T|"""
+    b = gamma(8) * Aabs + 8 * TINY
+    return b if e_d is None else b + (1 + gamma(8)) * e_d
+
+
+def dy_front64(dy, x, mean_rstd, gamma_, beta, relu, sums, npix):
+    """the gradient in front of the norm (winograd.hip, DyNormBackward): rstd gamma (g - S0/N - xhat S1/N), g = dy act'(gamma
+    xhat + beta), in float64 from the fp32 operands, and its error bound.  Roundings: invn = 1/N (1), k0 = S0 invn (2),
+    xh = (x - m) r (2), k1 (2), xh k1 (5), g - k0 (+1), - xh k1 (+1), rstd * gamma (1), the product (+1): every term <= 9:
+    e <= gamma(9) |r gamma| (|g| + |k0| + |xh| |k1|).
+    The activation's branch: the reference takes it from pre = gamma xhat + beta in float64.  The kernel decides on its own
+    fp32 pre, which is within gamma(4) (|gamma xhat| + |beta|) of that (two roundings for xhat, one each for the product and
+    the sum); where |pre| is no larger than that the two may disagree, and the bound there also admits the other branch:
+    + |r gamma dy| |act'(+) - act'(-)|."""
+    m, r = mean_rstd[:, 0].double(), mean_rstd[:, 1].double()
+    ga = gamma_.double() if gamma_ is not None else torch.ones_like(m)
+    be = beta.double() if beta is not None else torch.zeros_like(m)
+    xh = (x.double() - m) * r
+    pre = ga * xh + be
+    lo = 0.0 if relu == 1 else 0.2 if relu == 2 else 1.0
+    act = torch.where(pre > 0, 1.0, lo).double()
+    g = dy.double() * act
+    k0, k1 = sums[:, 0].double() / npix, sums[:, 1].double() / npix
+    front = r * ga * (g - k0 - xh * k1)
+    err = gamma(9) * (r * ga).abs() * (g.abs() + k0.abs() + xh.abs() * k1.abs()) + 9 * TINY
+    near = pre.abs() <= gamma(4) * ((ga * xh).abs() + be.abs()) + TINY
+    err = err + near.double() * (r * ga * dy.double()).abs() * (1.0 - lo)
+    return front, err
+
+
+def dgrad_output64(dV, TH, TW):
+    """winograd4_dgrad_output_kernel: the transposed algorithm's scatter -- per tile dd = B dV B^T (6x6, B = (B^T)^T), added
+    into the padded map dxp [(4 TH + 2), (4 TW + 2)] at rows 4 ty.., columns 4 tx.. (two rows / columns of overlap).
+    dV [36][T][C] (real tiles, float64) -> dxp, and the same on |dV|."""
+    BT = F4["kBT"].to(dV.device)
+    C = dV.shape[-1]
+
+    def scat(v, B):
+        dd = torch.einsum("ai,bj,abyxc->yixjc", B, B, v.view(6, 6, TH, TW, C))      # [TH, 6, TW, 6, C]
+        out = torch.zeros(4 * TH + 2, 4 * TW + 2, C, dtype=torch.float64, device=dV.device)
+        for r in range(6):
+            for q in range(6):
+                out[r:r + 4 * TH:4, q:q + 4 * TW:4] += dd[:, r, :, q]
+        return out
+    return scat(dV.double(), BT), scat(dV.double().abs(), BT.abs())
+
+
+def dgrad_output_bound(Aabs):
+    """dd = B dV B^T: two cdot levels of <= n roundings (n = the most nonzeros in a column of B^T), then up to 4 overlapping
+    contributions added to a zero start (3 more roundings): gamma(2n + 3) times the scatter of |B| |dV| |B^T|"""
+    n = nnz_rows(F4["kBT"].t())
+    return gamma(2 * n + 3) * Aabs + (2 * n + 3) * TINY
+
+
+def dw64(dU):
+    """winograd4_dw_kernel: dg[n][c] = G^T dU[.][n][c] G in fp64, rounded once.  dU [36][Cout][Cin] -> [Cout][Cin][3][3]"""
+    G = F4["kG"].to(dU.device)
+    d = dU.double().view(6, 6, dU.shape[1], dU.shape[2])
+    return torch.einsum("ai,bj,abnc->ncij", G, G, d), torch.einsum("ai,bj,abnc->ncij", G.abs(), G.abs(), d.abs())
+
+
+def reflect_fold(t):
+    """the adjoint of ReflectionPad2d(1) (what reflect_pad_backward computes): [(H + 2), (W + 2), C] -> [H, W, C]"""
+    H, W = t.shape[0] - 2, t.shape[1] - 2
+    z = torch.zeros(1, t.shape[2], H, W, dtype=t.dtype, device=t.device, requires_grad=True)
+    F.pad(z, (1, 1, 1, 1), mode="reflect").backward(t.permute(2, 0, 1)[None])
+    return z.grad[0].permute(1, 2, 0)
+
+
+def _abs_gemm_bound(AA, AB, eA, eB, K):
+    """|fl(A B^T) - A B^T| for inputs within eA, eB of |A| <= AA, |B| <= AB: the K-term sum's own rounding on the inputs'
+    magnitudes, plus the inputs' errors carried through the product"""
+    return sum_bound(gemm64(AA + eA, AB + eB), K) + gemm64(eA, AB) + gemm64(AA, eB) + gemm64(eA, eB)
+
+
+def dgrad64(dy, w):
+    """the data gradient of a 3x3 ReflectionPad(1) conv by the transposed algorithm, in float64: dy [H, W, Cout] (H, W multiples
+    of 4), w [Cout][Cin][3][3] -> dx [H, W, Cin] = fold(scatter(B (U^T (A dy A^T)) B^T)) -- the composition of dy64, the
+    GEMM with U^T (weight64 of the transposed layout), dgrad_output64 and reflect_fold"""
+    H, W = dy.shape[:2]
+    Md, _ = dy64(dy.double(), H, W)
+    Ut = weight64(w.to(dy.device), F4["kG"].to(dy.device), transposed_layout=True)
+    return reflect_fold(dgrad_output64(gemm64(Md, Ut), H // 4, W // 4)[0])
+
+
+def dgrad_bound(dy, w):
+    """End-to-end bound of the F(4x4) data gradient, the stage bounds composed on absolute values as in pipeline_bound:
+      A dy A^T:   e_Md = gamma(8) A_Md,  A_Md = |A| |dy| |A^T|
+      U^T:        e_U = u A_U  (fp64, one rounding),  A_U = |G| |w| |G^T|
+      dV = Md U:  e_dV = C_DIRECT u Cout (A_Md + e_Md)(A_U + e_U) + e_Md A_U + A_Md e_U + e_Md e_U,  A_dV = A_Md A_U
+      scatter:    e_p = S(e_dV) (1 + g) + g S(A_dV),  S = the scatter of |B| . |B^T|,  g = gamma(2 nB + 3)
+      fold:       <= 4 terms per pixel: e_dx = R(e_p) (1 + gamma(3)) + gamma(3) R(S(A_dV)),  R = reflect_fold
+    dy [H, W, Cout] fp32 values, w [Cout][Cin][3][3]; returns [H, W, Cin]."""
+    H, W, Cout = dy.shape
+    dev = dy.device
+    _, AMd = dy64(dy.double(), H, W)
+    AU = weight64(w.to(dev).abs(), F4["kG"].to(dev).abs(), transposed_layout=True)
+    eMd, eU = gamma(8) * AMd, U * AU
+    AdV = gemm64(AMd, AU)
+    edV = _abs_gemm_bound(AMd, AU, eMd, eU, Cout)
+    g = gamma(2 * nnz_rows(F4["kBT"].t()) + 3)
+    Sa = dgrad_output64(AdV, H // 4, W // 4)[1]
+    ep = dgrad_output64(edV, H // 4, W // 4)[1] * (1 + g) + g * Sa
+    return reflect_fold(ep) * (1 + gamma(3)) + gamma(3) * reflect_fold(Sa) + 16 * TINY
+
+
+def wgrad64(x, dy):
+    """the weight gradient of a 3x3 ReflectionPad(1) conv in the Winograd domain, in float64: x [B, H, W, Cin], dy [B, H, W, Cout]
+    -> dw [Cout][Cin][3][3] = G^T (sum over images and tiles of (A dy A^T)^T (B^T d B)) G -- wino_input64, dy64, the reduction
+    over tiles and dw64 composed"""
+    dU = 0
+    for b in range(x.shape[0]):
+        V, _, _ = wino_input64(x[b].double(), x.shape[1], x.shape[2], 1, True)
+        Md, _ = dy64(dy[b].double(), dy.shape[1], dy.shape[2])
+        dU = dU + gemm64(Md.transpose(1, 2), V.transpose(1, 2))
+    return dw64(dU)[0]
+
+
+def wgrad_bound(x, dy, Tp):
+    """End-to-end bound of the F(4x4) weight gradient, the stage bounds composed on absolute values:
+      V = B^T d B:   e_V = gamma(2 nB) A_V;   Md = A dy A^T:  e_Md = gamma(8) A_Md
+      dU = sum_t Md^T V over the batch's B Tp tile rows (K terms, padding rows zero):
+                     e_dU = C_DIRECT u K (A_Md + e_Md)^T (A_V + e_V) + e_Md^T A_V + A_Md^T e_V + e_Md^T e_V
+      dw = G^T dU G in fp64, rounded once:  e_dw = |G^T| e_dU |G| + (u + 2^-50) |G^T| (A_dU + e_dU) |G|
+    x [B, H, W, Cin], dy [B, H, W, Cout] fp32 values, Tp the padded tiles per image; returns [Cout][Cin][3][3]."""
+    nB = nnz_rows(F4["kBT"])
+    AV = torch.cat([wino_input64(x[b].double().abs(), x.shape[1], x.shape[2], 1, True, BT=F4["kBT"].abs())[0]
+                    for b in range(x.shape[0])], 1)
+    AMd = torch.cat([dy64(dy[b].double(), dy.shape[1], dy.shape[2])[1] for b in range(dy.shape[0])], 1)
+    AMdT, AVT = AMd.transpose(1, 2), AV.transpose(1, 2)
+    eMdT, eVT = gamma(8) * AMdT, gamma(2 * nB) * AVT
+    AdU = gemm64(AMdT, AVT)
+    edU = _abs_gemm_bound(AMdT, AVT, eMdT, eVT, x.shape[0] * Tp)
+    absG = lambda t: dw64(t)[1]
+    return absG(edU) + (U + 2.0 ** -50) * absG(AdU + edU) + TINY
+
+
+def pipeline_bound(x, w, b, algo, pad=1, reflect=True):
+    """End-to-end bound of a whole pipeline, composed from the stage bounds by running the same pipeline on absolute values:
+    |V| <= A_V = |B^T| |x| |B|, |U| <= A_U = |G| |w| |G^T|, |M| <= A_M = A_V . A_U (K terms), |y| <= |A^T| A_M |A| + |b|.
+    Each stage's error enters the next one's inputs and is carried through the absolute values:
+      e_V = gamma(2 nB) A_V,  e_U = u A_U (fp64 + one rounding; F(2x2): gamma(4) A_U),
+      e_M = C_DIRECT u K (A_V + e_V)(A_U + e_U) + e_V A_U + A_V e_U + e_V e_U,
+      e_y = |A^T| e_M |A| (1 + gamma(2 nA + 1)) + gamma(2 nA + 1) (|A^T| A_M |A| + |b|).
+    algo: "F4" | "F2" (x [H, W, C] fp32, w [Cout][Cin][3][3], the reflect / zero pad of the forward conv) | "down" | "up"
+    (polyphase: zero pad 1; "up" takes ConvTranspose2d's w [Cin][Cout][3][3]).  Returns the bound [Ho, Wo, Cout]."""
+    H, W, C = x.shape
+    if algo in ("down", "up"):
+        up = algo == "up"
+        AV, TH, TW = polyphase_input64(x.double().abs(), H, W, up, absolute=True)
+        AU = weight64(w.abs(), PP["kGU" if up else "kGD"].abs(), transposed_layout=up)
+        BT, AT = PP["kBU" if up else "kBD"], PP["kAU" if up else "kAD"]
+        Ho, Wo = (2 * H, 2 * W) if up else (H // 2, W // 2)
+        eU = U * AU
+    else:
+        mats = F4 if algo == "F4" else F2
+        AV, TH, TW = wino_input64(x.double().abs(), H, W, pad, reflect, m=4 if algo == "F4" else 2, BT=mats["kBT"].abs())
+        AU = weight64(w.abs(), mats["kG"].abs())
+        BT, AT = mats["kBT"], mats["kAT"]
+        Ho, Wo = H + 2 * pad - 2, W + 2 * pad - 2
+        eU = (U if algo == "F4" else gamma(4)) * AU
+    nB, nA = nnz_rows(BT), nnz_rows(AT)
+    eV = gamma(2 * nB) * AV
+    AM = gemm64(AV, AU)
+    eM = sum_bound(gemm64(AV + eV, AU + eU), C) + gemm64(eV, AU) + gemm64(AV, eU) + gemm64(eV, eU)
+    zb = torch.zeros(AU.shape[1], dtype=torch.float64)
+    _, aM = output64(eM, AT.abs(), TH, TW, Ho, Wo, zb)
+    _, aY = output64(AM, AT.abs(), TH, TW, Ho, Wo, b.double().abs())
+    return aM * (1 + gamma(2 * nA + 1)) + gamma(2 * nA + 1) * aY
+
+
+def polyphase_input64(x, H, W, up, d=None, absolute=False):
+    """polyphase_input_kernel: V[pr*9+pc][tile][c] = (B d B^T), down: B = kBD on the 9x9 patch at (8 ty - 1, 8 tx - 1) (zero
+    padding), tiles = 4x4 outputs of the H/2 x W/2 map; up: B = kBU on the 5x5 patch at (4 ty, 4 tx) (zeros past the map),
+    tiles = 4x4 inputs.  x [H, W, C] -> [81][T][C], TH, TW.  absolute: with |B| (the magnitude a bound scales)"""
+    src = x if d is None else d
+    f = (lambda m: m.abs()) if absolute else (lambda m: m)
+    if up:
+        TH, TW = -(-H // 4), -(-W // 4)
+        p = gather_patches(src, patch_index(H, TH, 4, 5, 0, False), patch_index(W, TW, 4, 5, 0, False))
+        return transform_in(p, f(PP["kBU"])), TH, TW
+    TH, TW = -(-(H // 2) // 4), -(-(W // 2) // 4)
+    p = gather_patches(src, patch_index(H, TH, 8, 9, 1, False), patch_index(W, TW, 8, 9, 1, False))
+    return transform_in(p, f(PP["kBD"])), TH, TW
+
+
+# ---- pinned Winograd / polyphase stage cases (tests/test_gpu_pipeline_variants.py) ------------------------------------
+# stage: which call runs (the test's STAGES); algo: "F4" | "F2" | "down" | "up"; H, W, Cin, Cout of the forward conv (the data
+# gradient: of the conv whose gradient it is); pad / reflect of that conv; nimg: packed forward images (the batch entry);
+# batch / slot: the weight gradient's workspace; opts: "affine" (gamma / beta), "relu", "res" (mode 2), "hint" (overlap hint
+# 1), "fw" (forward weights); env: T2V_* switches; expect: the pipeline instantiations that must run, and nothing else of
+# PIPE_FAMILIES.
+# the fixed-grid GEMM geometries (H, W, Cin, Cout) of the 3x3 reflect-pad F(4x4) convs the generator runs, shared with
+# tests/test_gpu_ops.py (the fixed-grid forms against one block per tile, bit for bit); the GEMM stage cases below take theirs
+FG_GEOMS = [(64, 64, 1024, 1024), (64, 88, 640, 640), (128, 128, 256, 256), (64, 128, 512, 1024), (128, 128, 512, 256),
+            (64, 40, 1024, 1024), (64, 40, 512, 384), (128, 128, 1024, 1024), (64, 85, 1024, 1024), (64, 56, 1024, 1024),
+            (64, 114, 1024, 1024), (60, 52, 256, 384)]
+PipeCase = collections.namedtuple("PipeCase", "id stage algo H W Cin Cout pad reflect nimg batch slot opts env expect note")
+PIPE_FAMILIES = ("winograd_weight_kernel", "winograd_input_kernel", "winograd_output_kernel", "winograd4_weight_kernel",
+                 "winograd4_weight_adjoint_kernel", "winograd4_input_kernel", "winograd4_output_kernel", "winograd4_dy_kernel",
+                 "winograd4_dgrad_output_kernel", "winograd4_dw_kernel", "polyphase_weight_kernel", "polyphase_input_kernel",
+                 "polyphase_output_down_kernel", "polyphase_output_up_kernel", "wino_gemm_sk_kernel", "wino_gemm_skr_kernel",
+                 "wino_gemm_skt_kernel", "wino_wgrad_sk_kernel", "conv_igemm_kernel", "conv_wgrad_kernel")
+_SK = (("T2V_WINO_GEMM_SK", "2"),)
+
+
+def _pc(id, stage, algo, H, W, Cin, Cout, expect, pad=1, reflect=True, nimg=1, batch=1, slot=0, opts=(), env=(), note=""):
+    if algo in ("down", "up"):
+        pad, reflect = 1, False
+    return PipeCase(id, stage, algo, H, W, Cin, Cout, pad, reflect, nimg, batch, slot, tuple(opts), tuple(env),
+                    tuple(expect) if isinstance(expect, (tuple, list)) else (expect,), note)
+
+
+def wi(mode, xcd):
+    return "t2v::winograd4_input_kernel<%d,%s>" % (mode, str(bool(xcd)).lower())
+
+
+def ppi(up, norm):
+    return "t2v::polyphase_input_kernel<%s,%s>" % (str(bool(up)).lower(), str(bool(norm)).lower())
+
+
+SK_L = "t2v::wino_gemm_sk_kernel<t2v::TileCfg<32,2,2,2,2>,2,false>"
+SK_L_BKN = "t2v::wino_gemm_sk_kernel<t2v::TileCfg<32,2,2,2,2>,2,true>"
+SK_W = "t2v::wino_gemm_sk_kernel<t2v::TileCfg<32,2,2,3,1>,2,false>"
+SK_T160 = "t2v::wino_gemm_sk_kernel<t2v::TileCfg<32,1,4,5,1>,3,false>"
+SK_T256 = "t2v::wino_gemm_sk_kernel<t2v::TileCfg<32,1,4,8,1>,3,false>"
+SKR = "t2v::wino_gemm_skr_kernel<2>"
+SKT = "t2v::wino_gemm_skt_kernel<3>"
+_NOXCD = (("T2V_XCD_SLICES", "1"),)
+
+PIPE_CASES = [
+    # --- weight transforms ---
+    _pc("w4_fwd", "weight", "F4", 8, 8, 96, 100, "t2v::winograd4_weight_kernel", note="Cout_p 128: 28 zero rows"),
+    _pc("w4_adjoint_flip", "weight_adjoint", "F4", 8, 8, 64, 36, "t2v::winograd4_weight_adjoint_kernel<true>",
+        note="data-gradient conv (zero pad 2) of a 36 -> 64 layer: the last 8 x 32 LDS tile partial in n"),
+    _pc("w4_transposed", "weight_transposed", "F4", 8, 8, 96, 64, "t2v::winograd4_weight_adjoint_kernel<false>",
+        note="U^T of a 96 -> 64 layer: rows 96 of Cout_p 128 (the data gradient asks Cout % 32 == 0)"),
+    _pc("w2_fwd", "weight", "F2", 8, 8, 32, 36, "t2v::winograd_weight_kernel"),
+    _pc("wp_down", "weight", "down", 8, 8, 32, 128, "t2v::polyphase_weight_kernel<false>"),
+    _pc("wp_up", "weight", "up", 4, 4, 64, 128, "t2v::polyphase_weight_kernel<true>"),
+    # --- forward input transforms (MODE 0) ---
+    _pc("in4_reflect_ragged", "input", "F4", 10, 14, 32, 32, wi(0, 0), note="3 x 4 tiles, ragged: reflected clamps"),
+    _pc("in4_reflect_h2", "input", "F4", 2, 7, 32, 32, wi(0, 0), note="H = 2, the smallest reflect size"),
+    _pc("in4_zero_p0", "input", "F4", 9, 13, 32, 32, wi(0, 0), pad=0, reflect=False),
+    _pc("in4_zero_p1", "input", "F4", 11, 6, 64, 32, wi(0, 0), pad=1, reflect=False),
+    _pc("in4_zero_p2", "input", "F4", 7, 9, 32, 32, wi(0, 0), pad=2, reflect=False, note="the data-gradient conv's padding"),
+    _pc("in4_pack2", "input", "F4", 17, 18, 32, 32, wi(0, 0), nimg=2, note="2 x 25 tiles packed into 64 rows"),
+    _pc("in4_pack3", "input", "F4", 10, 10, 32, 32, wi(0, 0), nimg=3, note="3 x 9 tiles packed into 64 rows"),
+    _pc("in4_xcd", "input", "F4", 13, 16, 1024, 32, wi(0, 1), env=_NOXCD, note="C2 = 512: channel slices per XCD"),
+    _pc("in4_xcd_pack2", "input", "F4", 8, 12, 1024, 32, wi(0, 1), nimg=2, env=_NOXCD),
+    _pc("in2_reflect_ragged", "input", "F2", 9, 11, 32, 32, "t2v::winograd_input_kernel"),
+    _pc("in2_zero_p2", "input", "F2", 6, 5, 32, 32, "t2v::winograd_input_kernel", pad=2, reflect=False),
+    # --- lazy-norm input transforms (the batch entry) ---
+    _pc("in4_lazy1", "input", "F4", 10, 13, 64, 32, wi(1, 0), opts=("relu",)),
+    _pc("in4_lazy1_affine_pack2", "input", "F4", 9, 10, 32, 32, wi(1, 0), nimg=2, opts=("relu", "affine")),
+    _pc("in4_lazy1_zero_p1", "input", "F4", 9, 7, 32, 32, wi(1, 0), pad=1, reflect=False, opts=("relu", "affine"),
+        note="beta != 0: a normalised padding would not be 0"),
+    _pc("in4_lazy1_xcd", "input", "F4", 8, 9, 1024, 32, wi(1, 1), opts=("relu", "affine"), env=_NOXCD),
+    _pc("in4_lazy2", "input", "F4", 10, 14, 32, 32, wi(2, 0), opts=("res",)),
+    _pc("in4_lazy2_affine_pack3", "input", "F4", 9, 6, 64, 32, wi(2, 0), nimg=3, opts=("res", "affine")),
+    _pc("in4_lazy2_xcd_pack2", "input", "F4", 7, 8, 1024, 32, wi(2, 1), nimg=2, opts=("res", "affine"), env=_NOXCD),
+    # --- polyphase input transforms ---
+    _pc("inp_down_ragged", "input", "down", 14, 10, 32, 128, ppi(0, 0), note="7 x 5 outputs: 2 x 2 ragged tiles"),
+    _pc("inp_up_odd", "input", "up", 7, 9, 32, 128, ppi(1, 0)),
+    _pc("inp_up_ragged", "input", "up", 10, 14, 64, 128, ppi(1, 0)),
+    _pc("inp_down_lazy", "input", "down", 10, 14, 32, 128, ppi(0, 1), opts=("relu", "affine"),
+        note="beta != 0: the zero padding must stay 0 after the norm"),
+    _pc("inp_up_lazy", "input", "up", 7, 9, 32, 128, ppi(1, 1), opts=("affine",)),
+    _pc("inp_up_lazy_relu_wide", "input", "up", 8, 85, 32, 128, ppi(1, 1), opts=("relu",)),
+    # --- batched GEMMs: the fixed-grid forms (T2V_WINO_GEMM_SK=2: wherever the shape allows) ---
+    # (the F(4x4) forms at FG_GEOMS entries: the same shapes test_gpu_ops.py checks bit for bit against one block per tile)
+    _pc("gemm_sk_128", "gemm", "F4", *FG_GEOMS[0], SK_L, env=_SK + (("T2V_WINO_GEMM_SK_RAGGED", "1"),),
+        note="256 rows, 576 tiles on 512 blocks: stream-K hand-over"),
+    _pc("gemm_sk_192x64", "gemm", "F4", *FG_GEOMS[6], SK_W, env=_SK + (("T2V_WINO_GEMM_SK_RAGGED", "0"),),
+        note="160 rows padded to 192, 108 tiles: too few for one block per CU"),
+    _pc("gemm_sk_160", "gemm", "F4", *FG_GEOMS[5], SK_T160, env=_SK + (("T2V_WINO_GEMM_SK_RAGGED", "0"),),
+        note="160 rows, 288 tiles: one block per CU"),
+    _pc("gemm_sk_256_pack2", "gemm", "F4", *FG_GEOMS[0], SK_T256, nimg=2, opts=("hint",),
+        env=_SK + (("T2V_WINO_GEMM_SK_RAGGED", "0"),), note="two packed images: 512 rows, the overlap hint"),
+    _pc("gemm_skr", "gemm", "F4", *FG_GEOMS[11], SKR, env=_SK + (("T2V_WINO_GEMM_SK_RAGGED", "1"),),
+        note="195 rows: 7 fragments"),
+    _pc("gemm_skt", "gemm", "F4", *FG_GEOMS[9], SKT, env=_SK + (("T2V_WINO_GEMM_SK_RAGGED", "2"),),
+        note="224 rows: 4 + 3 fragments"),
+    # (polyphase: no FG_GEOMS entry -- a stride-2 map whose 81-position GEMM has whole 128-row tiles)
+    _pc("gemm_sk_down", "gemm", "down", 64, 128, 128, 256, SK_L, env=_SK + (("T2V_WINO_GEMM_SK_RAGGED", "0"),)),
+    # --- output transforms ---
+    _pc("out4_ragged_stats", "output", "F4", 10, 14, 32, 96, "t2v::winograd4_output_kernel", opts=("stats",)),
+    _pc("out4_pack2_stats", "output", "F4", 9, 13, 32, 64, "t2v::winograd4_output_kernel", nimg=2, opts=("stats",)),
+    _pc("out4_lrelu", "output", "F4", 11, 10, 32, 68, "t2v::winograd4_output_kernel", opts=("lrelu",),
+        note="the VGG19 loss network's LeakyReLU in the output transform (no statistics with an activation)"),
+    _pc("out2_ragged_stats", "output", "F2", 9, 11, 32, 72, "t2v::winograd_output_kernel", opts=("stats",)),
+    _pc("outp_down_stats", "output", "down", 14, 10, 32, 128, "t2v::polyphase_output_down_kernel", opts=("stats",)),
+    _pc("outp_up_stats", "output", "up", 7, 9, 32, 128, "t2v::polyphase_output_up_kernel", opts=("stats",)),
+    # --- weight gradient: A dy A^T, the reduction over tiles, G^T dU G ---
+    _pc("dy_plain", "dy", "F4", 10, 14, 32, 36, "t2v::winograd4_dy_kernel<false>", batch=2, slot=1),
+    _pc("dy_norm_relu_affine", "dy_norm", "F4", 12, 9, 32, 40, "t2v::winograd4_dy_kernel<true>", batch=2, slot=1,
+        opts=("relu", "affine")),
+    _pc("dy_norm_plain", "dy_norm", "F4", 8, 8, 32, 32, "t2v::winograd4_dy_kernel<true>"),
+    _pc("wgrad_sk", "wgrad", "F4", 16, 20, 128, 256, ("t2v::wino_wgrad_sk_kernel<16,4>", "t2v::winograd4_dw_kernel"),
+        batch=2, env=(("T2V_WGRAD_SK", "2"),)),
+    _pc("wgrad_tile_per_block", "wgrad", "F4", 12, 10, 64, 36, ("t2v::conv_wgrad_kernel<false,16,4>",
+                                                                "t2v::winograd4_dw_kernel"),
+        batch=3, env=(("T2V_WGRAD_SK", "0"),)),
+    # --- data gradient by the transposed algorithm: dV = dM U^T (GEMM), the scatter B dV B^T ---
+    _pc("dgrad_bkn", "dgrad", "F4", 64, 64, 128, 128, (SK_L_BKN, "t2v::winograd4_dgrad_output_kernel<false>"), batch=2,
+        slot=1, opts=("fw",), env=_SK + (("T2V_XCD_SLICES", "0"),), note="forward weights as B [K][N]"),
+    _pc("dgrad_xcd", "dgrad", "F4", 8, 12, 1024, 64, ("t2v::conv_igemm_kernel<t2v::TileCfg<32,2,2,1,1>,0,false,false,2>",
+                                                      "t2v::winograd4_dgrad_output_kernel<true>"),
+        env=(("T2V_WINO_GEMM_SK", "0"),) + _NOXCD, note="C = 1024: channel slices per XCD; every border block touched"),
+]
+PIPE_BY_ID = {c.id: c for c in PIPE_CASES}
+# end to end, one per algorithm: the whole pipeline against F.conv2d / conv_transpose2d / autograd in float64 under
+# pipeline_bound() / dgrad_bound() / wgrad_bound() (catches a wrong matrix or a wrong adjoint, which the stage cases -- each
+# against the header's own matrices and the stage references' own algebra -- cannot): (algo, H, W, Cin, Cout)
+E2E_CASES = [("F4", 13, 18, 64, 96), ("F2", 9, 11, 32, 64), ("down", 14, 18, 64, 128), ("up", 7, 9, 64, 128),
+             ("F4_dgrad", 16, 20, 64, 128), ("F4_wgrad", 13, 18, 32, 64)]
+
+
 # ---- the table ----------------------------------------------------------------------------------------------------------
 Cases = collections.namedtuple("Cases", "ids")
 Existing = collections.namedtuple("Existing", "nodeids")
@@ -297,7 +805,6 @@ _Q_SINGLE_RING3 = ("64x64 tiles with one phase always take RING 2 in launch_pad 
 _Q_REFLECT_RING3 = ("64x64 tiles take RING 3 only with several phases (transposed), and transposed plans are zero-padded")
 
 # Written out entry by entry (a reviewer can diff it against `nm -C libt2v_hip.so | grep __device_stub__`).
-_PIPELINE = ('a form of the Winograd / polyphase pipeline: exercised by operator and end-to-end tests, but no pinned float64 case with the transform-pipeline bound yet')
 
 TABLE = {
     "t2v::accumulate_kernel":
@@ -499,21 +1006,21 @@ TABLE = {
     "t2v::pad_copy_kernel":
         Existing(("tests/test_gpu_backward.py::test_conv_weight_and_bias_gradient",)),
     "t2v::polyphase_input_kernel<false,false>":
-        Uncovered(_PIPELINE),
+        Cases(("inp_down_ragged",)),
     "t2v::polyphase_input_kernel<false,true>":
-        Uncovered(_PIPELINE),
+        Cases(("inp_down_lazy",)),
     "t2v::polyphase_input_kernel<true,false>":
-        Uncovered(_PIPELINE),
+        Cases(("inp_up_odd", "inp_up_ragged",)),
     "t2v::polyphase_input_kernel<true,true>":
-        Uncovered(_PIPELINE),
+        Cases(("inp_up_lazy", "inp_up_lazy_relu_wide",)),
     "t2v::polyphase_output_down_kernel":
-        Existing(("tests/test_gpu_ops.py::test_polyphase_winograd_matches_torch_and_the_direct_kernel",)),
+        Cases(("outp_down_stats",)),
     "t2v::polyphase_output_up_kernel":
-        Existing(("tests/test_gpu_ops.py::test_polyphase_winograd_matches_torch_and_the_direct_kernel",)),
+        Cases(("outp_up_stats",)),
     "t2v::polyphase_weight_kernel<false>":
-        Uncovered(_PIPELINE),
+        Cases(("wp_down",)),
     "t2v::polyphase_weight_kernel<true>":
-        Uncovered(_PIPELINE),
+        Cases(("wp_up",)),
     "t2v::reduce_final_kernel":
         Existing(("tests/test_gpu_kernel_variants.py::test_layout_and_reduction_forms_against_float64",)),
     "t2v::reduce_masked_l1_kernel":
@@ -545,55 +1052,55 @@ TABLE = {
     "t2v::wgrad_reduce_kernel":
         Existing(("tests/test_gpu_backward.py::test_conv_weight_and_bias_gradient",)),
     "t2v::wino_gemm_sk_kernel<t2v::TileCfg<32,1,4,5,1>,3,false>":
-        Uncovered(_PIPELINE),
+        Cases(("gemm_sk_160",)),
     "t2v::wino_gemm_sk_kernel<t2v::TileCfg<32,1,4,8,1>,3,false>":
-        Uncovered(_PIPELINE),
+        Cases(("gemm_sk_256_pack2",)),
     "t2v::wino_gemm_sk_kernel<t2v::TileCfg<32,2,2,2,2>,2,false>":
-        Uncovered(_PIPELINE),
+        Cases(("gemm_sk_128", "gemm_sk_down",)),
     "t2v::wino_gemm_sk_kernel<t2v::TileCfg<32,2,2,2,2>,2,true>":
-        Uncovered(_PIPELINE),
+        Cases(("dgrad_bkn",)),
     "t2v::wino_gemm_sk_kernel<t2v::TileCfg<32,2,2,3,1>,2,false>":
-        Uncovered(_PIPELINE),
+        Cases(("gemm_sk_192x64",)),
     "t2v::wino_gemm_skr_kernel<2>":
-        Uncovered(_PIPELINE),
+        Cases(("gemm_skr",)),
     "t2v::wino_gemm_skt_kernel<3>":
-        Uncovered(_PIPELINE),
+        Cases(("gemm_skt",)),
     "t2v::wino_wgrad_sk_kernel<16,4>":
-        Uncovered('compared with the one-block-per-tile form bit for bit and inside train steps only'),
+        Cases(("wgrad_sk",)),
     "t2v::winograd4_dgrad_output_kernel<false>":
-        Uncovered(_PIPELINE),
+        Cases(("dgrad_bkn",)),
     "t2v::winograd4_dgrad_output_kernel<true>":
-        Uncovered(_PIPELINE),
+        Cases(("dgrad_xcd",)),
     "t2v::winograd4_dw_kernel":
-        Existing(("tests/test_gpu_backward.py::test_weight_gradient_in_winograd_domain",)),
+        Cases(("wgrad_sk", "wgrad_tile_per_block",)),
     "t2v::winograd4_dy_kernel<false>":
-        Uncovered(_PIPELINE),
+        Cases(("dy_plain",)),
     "t2v::winograd4_dy_kernel<true>":
-        Uncovered(_PIPELINE),
+        Cases(("dy_norm_relu_affine", "dy_norm_plain",)),
     "t2v::winograd4_input_kernel<0,false>":
-        Uncovered(_PIPELINE),
+        Cases(("in4_reflect_ragged", "in4_reflect_h2", "in4_zero_p0", "in4_zero_p1", "in4_zero_p2", "in4_pack2", "in4_pack3",)),
     "t2v::winograd4_input_kernel<0,true>":
-        Uncovered(_PIPELINE),
+        Cases(("in4_xcd", "in4_xcd_pack2",)),
     "t2v::winograd4_input_kernel<1,false>":
-        Uncovered(_PIPELINE),
+        Cases(("in4_lazy1", "in4_lazy1_affine_pack2", "in4_lazy1_zero_p1",)),
     "t2v::winograd4_input_kernel<1,true>":
-        Uncovered(_PIPELINE),
+        Cases(("in4_lazy1_xcd",)),
     "t2v::winograd4_input_kernel<2,false>":
-        Uncovered(_PIPELINE),
+        Cases(("in4_lazy2", "in4_lazy2_affine_pack3",)),
     "t2v::winograd4_input_kernel<2,true>":
-        Uncovered(_PIPELINE),
+        Cases(("in4_lazy2_xcd_pack2",)),
     "t2v::winograd4_output_kernel":
-        Existing(("tests/test_gpu_ops.py::test_winograd_conv_matches_direct_and_reference",)),
+        Cases(("out4_ragged_stats", "out4_pack2_stats", "out4_lrelu",)),
     "t2v::winograd4_weight_adjoint_kernel<false>":
-        Uncovered(_PIPELINE),
+        Cases(("w4_transposed",)),
     "t2v::winograd4_weight_adjoint_kernel<true>":
-        Uncovered(_PIPELINE),
+        Cases(("w4_adjoint_flip",)),
     "t2v::winograd4_weight_kernel":
-        Existing(("tests/test_gpu_ops.py::test_winograd_conv_matches_direct_and_reference",)),
+        Cases(("w4_fwd",)),
     "t2v::winograd_input_kernel":
-        Existing(("tests/test_gpu_ops.py::test_winograd_conv_matches_direct_and_reference",)),
+        Cases(("in2_reflect_ragged", "in2_zero_p2",)),
     "t2v::winograd_output_kernel":
-        Existing(("tests/test_gpu_ops.py::test_winograd_conv_matches_direct_and_reference",)),
+        Cases(("out2_ragged_stats",)),
     "t2v::winograd_weight_kernel":
-        Existing(("tests/test_gpu_ops.py::test_winograd_conv_matches_direct_and_reference",)),
+        Cases(("w2_fwd",)),
 }

@@ -186,3 +186,36 @@ def test_makefile_rebuilds_objects_when_the_winograd_constants_change():
     rule = re.search(r"^%\.o: %\.hip (.*)$", mk, re.M).group(1).split()
     assert "winograd_f4_consts.h" in rule and "t2v_internal.h" in rule and "../../include/t2v.h" in rule
     assert "polyphase_consts.h" in rule
+
+
+def test_winograd_batch_stages_rejects_bad_arguments(lib_built):
+    """t2v_conv2d_forward_winograd_batch_stages (the generator's packed-batch and lazy-norm forms): every argument check
+    fails with a status and a message before anything is launched (the pointers below are never dereferenced)."""
+    from text2video_amd import _lib
+    f4 = _lib.ConvDesc(16, 16, 64, 64, 3, 3, 1, 1, _lib.PAD_REFLECT, 0, 0, 1.0, 0, _lib.ALGO_WINOGRAD_F4)
+    f2 = _lib.ConvDesc(16, 16, 64, 64, 3, 3, 1, 1, _lib.PAD_REFLECT, 0, 0, 1.0, 0, _lib.ALGO_WINOGRAD)
+    pp = _lib.ConvDesc(16, 16, 64, 128, 3, 3, 2, 1, _lib.PAD_ZERO, 0, 0, 1.0, 0, _lib.ALGO_POLYPHASE)
+    p = ctypes.c_void_p(64)
+    one = 16 * 16 * 64
+
+    def call(d, nimg=1, stride=one, stages=7, mr=None, gm=None, bt=None, relu=0, res=None, xout=None, ctx=p, y_cs=64, x_cs=64):
+        return lib_built.t2v_conv2d_forward_winograd_batch_stages(ctx, None, ctypes.byref(d), nimg, p, x_cs, stride, p, p, p,
+                                                                  y_cs, None, p, stages, mr, gm, bt, relu, res, xout)
+    cases = [(dict(d=f4, ctx=None), b"null pointer"),
+             (dict(d=f4, stages=8), b"stages mask"),
+             (dict(d=f4, nimg=0), b"nimg 0"),
+             (dict(d=f4, nimg=2, stride=one - 4), b"image stride"),
+             (dict(d=f4, gm=p, bt=p), b"need mean_rstd"),
+             (dict(d=f4, relu=1), b"need mean_rstd"),
+             (dict(d=f4, res=p), b"need mean_rstd"),
+             (dict(d=f4, x_cs=96), b"not supported"),
+             (dict(d=f4, y_cs=68), b"output channel storage"),
+             (dict(d=f2, nimg=2, stride=2 * one), b"F(4x4,3x3) only"),
+             (dict(d=f2, mr=p, relu=1), b"F(4x4,3x3) only"),
+             (dict(d=f4, mr=p, relu=2), b"relu 2"),
+             (dict(d=pp, y_cs=128, nimg=2, stride=2 * one), b"one image"),
+             (dict(d=pp, y_cs=128, mr=p, res=p, xout=p), b"one image"),
+             (dict(d=pp, y_cs=64), b"output channel storage")]
+    for kw, msg in cases:
+        assert call(**kw) == -1, kw
+        assert msg in lib_built.t2v_last_error(), (kw, lib_built.t2v_last_error())

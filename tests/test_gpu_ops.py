@@ -400,9 +400,7 @@ def test_winograd_f4_output_transform_applies_the_activation(slope):
         ops.conv2d_auto(_to_nhwc(x), U, b.to(_dev()), desc, stats=ops.conv_stats_buffer(desc, _dev()))
 
 
-_FG_GEOMS = [(64, 64, 1024, 1024), (64, 88, 640, 640), (128, 128, 256, 256), (64, 128, 512, 1024), (128, 128, 512, 256),
-             (64, 40, 1024, 1024), (64, 40, 512, 384), (128, 128, 1024, 1024), (64, 85, 1024, 1024), (64, 56, 1024, 1024),
-             (64, 114, 1024, 1024), (60, 52, 256, 384)]
+_FG_GEOMS = kv.FG_GEOMS          # (shared with the float64 GEMM stage cases, tests/kernel_variants.py)
 # too few tiles for one block per CU: T2V_WINO_GEMM_SK_RAGGED=2 stays on the two-per-CU ragged form there (= the "1" case)
 _FG_NO_TALL = {(64, 40, 1024, 1024), (64, 40, 512, 384), (60, 52, 256, 384)}
 _FG_NAMES = {"1": "ragged", "0": "whole_tiles", "2": "tall_ragged"}

@@ -71,6 +71,7 @@ SIGNATURES = {
     "t2v_conv_polyphase_supported": (c_int, [POINTER(ConvDesc), c_int]),
     "t2v_conv_best_algo": (c_int, [POINTER(ConvDesc), c_int, c_int]),
     "t2v_conv_winograd_workspace_floats": (c_size_t, [POINTER(ConvDesc), c_int]),
+    "t2v_conv_winograd_batch_workspace_floats": (c_size_t, [POINTER(ConvDesc), c_int, c_int]),
     "t2v_conv_winograd_tile_rows": (c_int, [POINTER(ConvDesc)]),
     "t2v_conv_winograd_gemm_form": (c_int, [POINTER(ConvDesc), c_int]),
     "t2v_conv2d_forward_winograd": (c_int, [c_void_p, c_void_p, POINTER(ConvDesc), c_void_p, c_int, c_void_p, c_void_p,
@@ -79,6 +80,9 @@ SIGNATURES = {
                                                    c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int]),
     "t2v_conv2d_backward_weight_winograd_dy_norm": (c_int, [c_void_p, c_void_p, POINTER(ConvDesc), c_int, c_int, c_int, c_void_p,
                                                             c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
+    "t2v_conv2d_forward_winograd_batch_stages": (c_int, [c_void_p, c_void_p, POINTER(ConvDesc), c_int, c_void_p, c_int, c_long,
+                                                         c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int,
+                                                         c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
     "t2v_conv2d_forward_winograd_keep_v": (c_int, [c_void_p, c_void_p, POINTER(ConvDesc), c_void_p, c_int, c_void_p,
                                                    c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int]),
     "t2v_instance_norm_finalize": (c_int, [c_void_p, c_void_p, POINTER(ConvDesc), c_void_p, c_float, c_void_p]),

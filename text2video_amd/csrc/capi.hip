@@ -641,6 +641,13 @@ size_t t2v_conv_winograd_workspace_floats(const t2v_conv_desc* d, int x_cs) {
     return winograd_workspace_floats(d);
 }
 
+size_t t2v_conv_winograd_batch_workspace_floats(const t2v_conv_desc* d, int x_cs, int nimg) {
+    if (!d || nimg < 1) return 0;
+    if (d->algo == T2V_ALGO_POLYPHASE) return nimg == 1 && polyphase_supported(d, x_cs) ? polyphase_workspace_floats(d) : 0;
+    if (!winograd_supported(d, x_cs, d->algo) || (nimg > 1 && d->algo != T2V_ALGO_WINOGRAD_F4)) return 0;
+    return winograd_workspace_floats(d, nimg);
+}
+
 int t2v_conv2d_forward_winograd_stages(t2v_ctx* ctx, void* stream, const t2v_conv_desc* d, const float* x, int x_cs,
                                        const float* w_packed, const float* bias, float* y, int y_cs,
                                        float* stats_partial, float* workspace, int stages) {
@@ -654,6 +661,45 @@ int t2v_conv2d_forward_winograd_stages(t2v_ctx* ctx, void* stream, const t2v_con
                 "winograd forward: shape/algo not supported (t2v_conv_winograd_supported)");
     T2V_REQUIRE(y_cs == d->Cout, "winograd forward: output channel storage must equal Cout");
     return winograd_forward(ctx, (hipStream_t)stream, d, x, w_packed, bias, y, stats_partial, workspace, stages);
+}
+
+// The generator's forms of a Winograd conv (generator.hip: wino4_conv_stats, conv_norm_one) with the same launchers and
+// nothing of its own: nimg packed images (F(4x4) only) and, with mean_rstd, the previous layer's norm applied inside the
+// input transform -- launch_winograd4_input_lazy for F(4x4), the PolyLazyNorm of polyphase_forward.
+int t2v_conv2d_forward_winograd_batch_stages(t2v_ctx* ctx, void* stream, const t2v_conv_desc* d, int nimg, const float* x,
+                                             int x_cs, long img_stride, const float* w_packed, const float* bias, float* y,
+                                             int y_cs, float* stats_partial, float* workspace, int stages,
+                                             const float* mean_rstd, const float* gamma, const float* beta, int relu,
+                                             const float* res, float* xout) {
+    T2V_REQUIRE(ctx && d && x && w_packed && y && workspace, "winograd batch forward: null pointer");
+    T2V_REQUIRE(stages >= 0 && stages <= 7, "winograd batch forward: stages mask %d", stages);
+    T2V_REQUIRE(nimg >= 1 && nimg <= 65535, "winograd batch forward: nimg %d", nimg);
+    T2V_REQUIRE(nimg == 1 || img_stride >= (long)d->H * d->W * x_cs, "winograd batch forward: image stride %ld below one map",
+                img_stride);
+    T2V_REQUIRE(mean_rstd || (!gamma && !beta && !res && !xout && relu == 0),
+                "winograd batch forward: gamma, beta, relu, res and xout need mean_rstd");
+    hipStream_t s = (hipStream_t)stream;
+    if (d->algo == T2V_ALGO_POLYPHASE) {
+        T2V_REQUIRE(polyphase_supported(d, x_cs), "polyphase forward: shape not supported (t2v_conv_polyphase_supported)");
+        T2V_REQUIRE(y_cs == d->Cout, "polyphase forward: output channel storage must equal Cout");
+        T2V_REQUIRE(nimg == 1 && !res && !xout, "polyphase batch forward: one image, no residual");
+        const PolyLazyNorm ln{mean_rstd, gamma, beta, relu};
+        return polyphase_forward(ctx, s, d, x, w_packed, bias, y, stats_partial, workspace, stages, mean_rstd ? &ln : nullptr);
+    }
+    T2V_REQUIRE(winograd_supported(d, x_cs, d->algo), "winograd forward: shape/algo not supported (t2v_conv_winograd_supported)");
+    T2V_REQUIRE(y_cs == d->Cout, "winograd forward: output channel storage must equal Cout");
+    T2V_REQUIRE(d->algo == T2V_ALGO_WINOGRAD_F4 || (nimg == 1 && !mean_rstd),
+                "winograd batch forward: batches and the lazy norm are F(4x4,3x3) only");
+    if (mean_rstd && (stages & 1)) {
+        T2V_REQUIRE(relu == 0 || relu == 1, "winograd batch forward: relu %d", relu);
+        T2V_TRY(launch_winograd4_input_lazy(s, x, workspace, d->H, d->W, d->Cin, d->pad, d->pad_mode == T2V_PAD_REFLECT, mean_rstd,
+                                            gamma, beta, relu, res, xout, nimg, img_stride));
+        stages &= ~1;
+    }
+    WinoBatch wb;
+    wb.nimg = nimg;
+    wb.img_stride_x = img_stride;
+    return winograd_forward(ctx, s, d, x, w_packed, bias, y, stats_partial, workspace, stages, &wb);
 }
 
 static bool wgrad_winograd_ok(const t2v_conv_desc* d, int x_cs, int dy_cs);

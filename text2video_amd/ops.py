@@ -170,6 +170,36 @@ def conv2d_winograd(x, packed_u, bias, desc, stats=None, out=None, workspace=Non
     return y
 
 
+def winograd_batch_workspace(desc, x_cs, nimg, device):
+    """workspace of conv2d_winograd_batch: V and M of `nimg` packed F(4x4,3x3) images ([36][pad(nimg*T)][C]), then the
+    fixed-grid GEMM's hand-over scratch"""
+    n = _lib.load().t2v_conv_winograd_batch_workspace_floats(ctypes.byref(desc), x_cs, nimg)
+    if n == 0:
+        raise RuntimeError("winograd_batch_workspace: shape not supported")
+    return torch.empty(n, dtype=torch.float32, device=device)
+
+
+def conv2d_winograd_batch(x, packed_u, bias, desc, workspace, stats=None, out=None, stages=7, mean_rstd=None, gamma=None,
+                          beta=None, relu=0, res=None, xout=None):
+    """The generator's forms of a Winograd / polyphase conv (t2v_conv2d_forward_winograd_batch_stages): x [nimg,H,W,Cin]
+    packed into one tile list (F(4x4) only for nimg > 1; workspace: winograd_batch_workspace), and with mean_rstd
+    ([nimg*Cin*2]) the previous layer's norm applied in the input transform -- relu 1: relu(norm(x)); F(4x4) relu 0 with
+    res and xout ([nimg,H,W,Cin]): norm(x) + res, also written to xout.  Returns y [nimg,Ho,Wo,Cout]."""
+    c = context()
+    if x.dim() == 3:
+        x = x.unsqueeze(0)
+    _chk(x, "x")
+    nimg, x_cs = x.shape[0], x.shape[-1]
+    ho, wo = conv_out_dims(desc)
+    y = out if out is not None else torch.empty(nimg, ho, wo, desc.Cout, dtype=torch.float32, device=x.device)
+    check(c.lib.t2v_conv2d_forward_winograd_batch_stages(c.handle, _stream(), ctypes.byref(desc), nimg, _p(x), x_cs,
+                                                         x[0].numel(), _p(packed_u), _p(bias), _p(y), desc.Cout, _p(stats),
+                                                         _p(workspace), stages, _p(mean_rstd), _p(gamma), _p(beta), int(relu),
+                                                         _p(res), _p(xout)),
+          "conv2d_forward_winograd_batch_stages")
+    return y
+
+
 def conv_out_dims(desc):
     h, w = ctypes.c_int(), ctypes.c_int()
     check(_lib.load().t2v_conv_out_dims(ctypes.byref(desc), ctypes.byref(h), ctypes.byref(w)), "conv_out_dims")
@@ -616,14 +646,20 @@ def backward_data_winograd_takes_forward_weights(desc, x_cs, dy_cs):
     return bool(_lib.load().t2v_conv_backward_data_winograd_takes_forward_weights(ctypes.byref(desc), x_cs, dy_cs))
 
 
-def conv2d_backward_data_winograd(desc, batch, slot, wgrad_ws, x_cs, ut, out=None, forward_weights=False):
+def backward_data_winograd_scratch(desc, x_cs, device):
+    n = _lib.load().t2v_conv_backward_data_winograd_scratch_floats(ctypes.byref(desc), x_cs)
+    return torch.empty(n, dtype=torch.float32, device=device)
+
+
+def conv2d_backward_data_winograd(desc, batch, slot, wgrad_ws, x_cs, ut, out=None, forward_weights=False, scratch=None):
     """dx [H,W,x_cs] of image `slot` of a batch whose A dy A^T already sits in the weight gradient's workspace `wgrad_ws`
     (conv2d_backward_weight_winograd_stages): the transposed Winograd algorithm (include/t2v.h).  `ut`: the transposed
-    packing (pack_conv_weight_transposed), or with forward_weights the forward layer's own F(4x4) packing."""
+    packing (pack_conv_weight_transposed), or with forward_weights the forward layer's own F(4x4) packing.  `scratch`
+    (backward_data_winograd_scratch): where dV = U^T dM lands, [36][Tp][Cin] first (its own buffer by default)."""
     c = context()
     dx = torch.empty(desc.H, desc.W, x_cs, dtype=torch.float32, device=wgrad_ws.device) if out is None else out
-    n = c.lib.t2v_conv_backward_data_winograd_scratch_floats(ctypes.byref(desc), x_cs)
-    scratch = torch.empty(n, dtype=torch.float32, device=wgrad_ws.device)
+    if scratch is None:
+        scratch = backward_data_winograd_scratch(desc, x_cs, wgrad_ws.device)
     fn = c.lib.t2v_conv2d_backward_data_winograd_fw if forward_weights else c.lib.t2v_conv2d_backward_data_winograd
     check(fn(c.handle, _stream(), ctypes.byref(desc), batch, slot, _p(wgrad_ws), x_cs, _p(ut), _p(scratch), _p(dx)),
           "conv2d_backward_data_winograd")
