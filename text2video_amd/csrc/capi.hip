@@ -306,28 +306,86 @@ int best_conv_algo(const t2v_conv_desc* d, int x_cs, int cap) {
     return T2V_ALGO_DIRECT;
 }
 
-// the batched GEMM of a Winograd conv as a plan of the implicit-GEMM kernel: a 1x1 conv over a 16|36 x T image
-int build_winograd_gemm_plan(const t2v_conv_desc* d, ConvPlan* pl, int nimg) {
-    const int T = wino_rows_batch(d, d->algo, nimg);   // GEMM rows per transform position: all images' tiles, packed
-    t2v_conv_desc g;
-    memset(&g, 0, sizeof(g));
-    g.H = wino_pos(d->algo); g.W = T; g.Cin = d->Cin; g.Cout = d->Cout; g.kH = g.kW = 1; g.stride = 1; g.pad = 0;
-    g.pad_mode = T2V_PAD_ZERO; g.act = T2V_ACT_NONE; g.act_scale = 1.f;
-    T2V_TRY(build_conv_plan(&g, d->Cin, /*need_stats: 128- or 64-row tiles only*/ true, pl));
+// ---- the batched per-position GEMM of the Winograd and polyphase paths: C[g] = A[g] B[g]^T for `groups` transform positions,
+// A[g] [T][K] (tile rows, the first `rows` of them real), B[g] [N][K], C[g] [T][N].  One place decides which kernel form
+// runs it (position_gemm_form: also what t2v_conv_winograd_gemm_form reports) and one place launches it (run_position_gemm).
+// The struct is data about the GEMM only; the callers differ in nothing else.
+struct PositionGemm {
+    int groups = 0;             // transform positions: 16 | 36 | 81
+    int rows = 0;               // real tile rows per position; 0: not known (only the whole-tile forms are considered)
+    int T = 0, K = 0, N = 0;    // padded tile rows per position, reduction length, output channels (= C's channel pitch)
+    int a_pitch = 0;            // tile rows between the positions of A where A is a window of a wider matrix (a kept V, the
+                                // weight gradient's batch-wide A dy A^T); 0: T
+    bool has_scratch = true;    // the workspace ends in the fixed-grid forms' hand-over scratch (wino_gemm_sk_scratch_floats());
+                                // false (F(2x2)): one block per tile
+    bool b_kn = false;          // B is [groups][K][N]: the caller has checked wino_gemm_sk_bkn_ok, the whole-tile fixed grid runs
+};
+
+// the one-block-per-tile form as a plan of the implicit-GEMM kernel: a 1x1 conv over a `groups` x T image
+static int build_position_gemm_plan(const PositionGemm& g, ConvPlan* pl) {
+    t2v_conv_desc d;
+    memset(&d, 0, sizeof(d));
+    d.H = g.groups; d.W = g.T; d.Cin = g.K; d.Cout = g.N; d.kH = d.kW = 1; d.stride = 1; d.pad = 0;
+    d.pad_mode = T2V_PAD_ZERO; d.act = T2V_ACT_NONE; d.act_scale = 1.f;
+    T2V_TRY(build_conv_plan(&d, g.K, /*need_stats: 128- or 64-row tiles only*/ true, pl));
     // A batch (nimg >= 2: T = 512, 1024, ... rows per position) keeps the 128x128 tiles build_conv_plan's fill rule
     // leaves it with: alone the 64x64 tiles are faster at T = 512 (315 vs 335 us per batch-2 launch), inside two-stream
     // frames they lose (11.80 vs 11.41 ms per frame) -- the big tiles leave wave slots to the other stream's kernels.
-    if (T % pl->BM != 0 && pl->tile == kTileL) {   // tile count padded to 64 only: the 64x64 tile config
+    if (g.T % pl->BM != 0 && pl->tile == kTileL) {   // tile count padded to 64 only: the 64x64 tile config
         pl->tile = kTileQ;
         conv_tile_dims(pl->tile, &pl->BM, &pl->BN);
-        pl->kp.ntiles = (g.Cout + pl->BN - 1) / pl->BN;
+        pl->kp.ntiles = (d.Cout + pl->BN - 1) / pl->BN;
         pl->kp.mtiles = (pl->kp.M + pl->BM - 1) / pl->BM;
         pl->nparts = pl->kp.nphases * pl->kp.mtiles;
     }
-    pl->kp.group_mtiles = T / pl->BM;               // T % 128 == 0 and BM in {128, 64, 256?}: checked below
-    T2V_REQUIRE(T % pl->BM == 0, "winograd gemm: tile rows %d do not divide %d", pl->BM, T);
-    pl->kp.group_w_stride = (long)pl->Cout_p * d->Cin;
+    T2V_REQUIRE(g.T % pl->BM == 0, "position gemm: tile rows %d do not divide %d", pl->BM, g.T);
+    pl->kp.group_mtiles = g.T / pl->BM;
+    pl->kp.group_w_stride = (long)pl->Cout_p * g.K;
+    if (g.a_pitch) {   // the [groups][T] "image" of the 1x1 plan is a window of a wider one: input row pitch a_pitch
+        T2V_REQUIRE((long)g.groups * g.a_pitch * g.K * 4 < 0x7fff0000L, "position gemm: A too large for 32-bit buffer offsets");
+        pl->kp.Win = g.a_pitch;
+    }
     return T2V_OK;
+}
+
+// Which form runs (T2V_GEMM_*; -1: none, the error is set): tall-ragged -> ragged -> whole-tile fixed grid -> one block per
+// tile.  plan (optional) receives the one-block-per-tile plan when that is the answer.
+static int position_gemm_form(const PositionGemm& g, ConvPlan* plan = nullptr) {
+    if (g.b_kn) return T2V_GEMM_FIXED_GRID_128x128;
+    if (g.has_scratch) {
+        if (wino_gemm_skt_ok(g.groups, g.rows, g.T, g.K, g.N, g.N)) return T2V_GEMM_FIXED_GRID_RAGGED_TALL;
+        if (wino_gemm_skr_ok(g.groups, g.rows, g.T, g.K, g.N, g.N)) return T2V_GEMM_FIXED_GRID_RAGGED;
+        if (wino_gemm_sk_ok(g.groups, g.T, g.K, g.N, g.N, g.rows))
+            switch (wino_gemm_sk_tall_rows(g.groups, g.rows, g.T, g.N)) {
+                case 160: return T2V_GEMM_FIXED_GRID_160x128;
+                case 256: return T2V_GEMM_FIXED_GRID_256x128;
+                default: return g.T % 128 == 0 ? T2V_GEMM_FIXED_GRID_128x128 : T2V_GEMM_FIXED_GRID_192x64;
+            }
+    }
+    ConvPlan local;
+    ConvPlan* pl = plan ? plan : &local;
+    if (build_position_gemm_plan(g, pl) != T2V_OK) return -1;
+    return pl->tile == kTileL ? T2V_GEMM_TILE_PER_BLOCK_128x128 : T2V_GEMM_TILE_PER_BLOCK_64x64;
+}
+
+static int run_position_gemm(t2v_ctx* ctx, hipStream_t s, const PositionGemm& g, const float* a, const float* b, float* c,
+                             float* scratch) {
+    T2V_REQUIRE(a && b && c && (scratch || !g.has_scratch), "position gemm: null pointer");
+    ConvPlan pl;
+    const int form = position_gemm_form(g, &pl);
+    if (form < 0) return T2V_ERR_INVALID;
+    if (form == T2V_GEMM_TILE_PER_BLOCK_128x128 || form == T2V_GEMM_TILE_PER_BLOCK_64x64)
+        return run_conv(ctx, s, pl, a, b, nullptr, c, g.N, nullptr);
+    SkGemm k;
+    k.a = a; k.b = b; k.c = c; k.scratch = scratch;
+    k.err = async_error_word();
+    k.rows = g.rows;
+    k.a_group_stride = (long)(g.a_pitch ? g.a_pitch : g.T) * g.K;
+    k.groups = g.groups; k.T = g.T; k.K = g.K; k.N = g.N; k.c_cs = g.N;
+    k.b_kn = g.b_kn;
+    if (form == T2V_GEMM_FIXED_GRID_RAGGED_TALL) return launch_wino_gemm_skt(s, k, g.rows);
+    if (form == T2V_GEMM_FIXED_GRID_RAGGED) return launch_wino_gemm_skr(s, k, g.rows);
+    return launch_wino_gemm_sk(s, k);
 }
 
 // `batch` images in one go (image b at x + b * x_stride, y + b * y_stride, statistics at stats + b * stats_stride, floats):
@@ -417,9 +475,7 @@ int winograd_forward(t2v_ctx* ctx, hipStream_t s, const t2v_conv_desc* d, const 
     const bool keep = wb.keep_v != nullptr;
     T2V_REQUIRE(!keep || (f4 && nimg == 1 && wb.keep_slot >= 0 && wb.keep_slot < wb.keep_total),
                 "winograd: V is kept for the weight gradient of single F(4x4,3x3) images only");
-    // (kept: slot keep_slot of [36][keep_total * Tp][Cin]; the positions are keep_total * Tp rows apart)
     float* V = keep ? wb.keep_v + (size_t)wb.keep_slot * T * d->Cin : workspace;
-    const long v_group_stride = (long)(keep ? wb.keep_total : 1) * (long)T * d->Cin;
     float* Mm = workspace + wino_pos(d->algo) * T * d->Cin;
     if (stages & 1) {
         const int reflect = d->pad_mode == T2V_PAD_REFLECT;
@@ -429,32 +485,14 @@ int winograd_forward(t2v_ctx* ctx, hipStream_t s, const t2v_conv_desc* d, const 
                    : launch_winograd_input(s, x, V, d->H, d->W, d->Cin, d->pad, reflect));
     }
     if (stages & 2) {
-        const int rows = nimg * wino_tiles_real(d, d->algo);      // real tile rows per position (the rest of T is padding)
-        const bool tall_ragged = f4 && wino_gemm_skt_ok(36, rows, (int)T, d->Cin, d->Cout, d->Cout);
-        if (tall_ragged || (f4 && wino_gemm_skr_ok(36, rows, (int)T, d->Cin, d->Cout, d->Cout))) {
-            SkGemm g;
-            g.a = V; g.b = w_packed; g.c = Mm; g.scratch = workspace + winograd_vm_floats(d, nimg);
-            g.err = async_error_word();
-            g.a_group_stride = v_group_stride;
-            g.groups = 36; g.T = (int)T; g.K = d->Cin; g.N = d->Cout; g.c_cs = d->Cout;
-            T2V_TRY(tall_ragged ? launch_wino_gemm_skt(s, g, rows) : launch_wino_gemm_skr(s, g, rows));
-        } else if (f4 && wino_gemm_sk_ok(36, (int)T, d->Cin, d->Cout, d->Cout, rows)) {
-            SkGemm g;
-            g.a = V; g.b = w_packed; g.c = Mm; g.scratch = workspace + winograd_vm_floats(d, nimg);
-            g.err = async_error_word();
-            g.rows = rows;
-            g.a_group_stride = v_group_stride;
-            g.groups = 36; g.T = (int)T; g.K = d->Cin; g.N = d->Cout; g.c_cs = d->Cout;
-            T2V_TRY(launch_wino_gemm_sk(s, g));
-        } else {
-            ConvPlan pl;
-            T2V_TRY(build_winograd_gemm_plan(d, &pl, nimg));
-            if (keep) {   // the [36][T] "image" of the 1x1 plan is a window of the batch-wide one: row pitch keep_total * T
-                T2V_REQUIRE(v_group_stride * 36 * 4 < 0x7fff0000L, "winograd: kept V too large for 32-bit buffer offsets");
-                pl.kp.Win = wb.keep_total * (int)T;
-            }
-            T2V_TRY(run_conv(ctx, s, pl, V, w_packed, nullptr, Mm, d->Cout, nullptr));
-        }
+        PositionGemm g;
+        g.has_scratch = f4;      // (F(2x2)'s workspace has none: winograd_workspace_floats)
+        g.groups = wino_pos(d->algo);
+        g.rows = nimg * wino_tiles_real(d, d->algo);      // real tile rows per position (the rest of T is padding)
+        g.T = (int)T; g.K = d->Cin; g.N = d->Cout;
+        // (kept: slot keep_slot of [36][keep_total * Tp][Cin]; the positions are keep_total * Tp rows apart)
+        if (keep) g.a_pitch = wb.keep_total * (int)T;
+        T2V_TRY(run_position_gemm(ctx, s, g, V, w_packed, Mm, f4 ? workspace + winograd_vm_floats(d, nimg) : nullptr));
     }
     if (stages & 4) {
         T2V_REQUIRE(d->act == T2V_ACT_NONE || !stats_partial, "winograd: an activation and norm statistics do not combine");
@@ -487,47 +525,17 @@ bool polyphase_pays(const t2v_conv_desc* d, int x_cs) {
 // stages bit 1 = input transform, 2 = the 81 batched GEMMs, 4 = output transform (bias, statistics partials)
 int polyphase_forward(t2v_ctx* ctx, hipStream_t s, const t2v_conv_desc* d, const float* x, const float* w_packed,
                       const float* bias, float* y, float* stats_partial, float* workspace, int stages,
-                      const PolyLazyNorm* lazy) {
+                      const LazyNorm* lazy) {
     T2V_TRY(check_async_errors());
     const int up = d->transposed ? 1 : 0;
     const int T = poly_tiles_padded(d), rows = poly_tiles_real(d);
     float* V = workspace;
     float* Mm = workspace + (size_t)81 * T * d->Cin;
-    if (stages & 1)
-        T2V_TRY(lazy ? launch_polyphase_input(s, x, V, d->H, d->W, d->Cin, up, T, lazy->mean_rstd, lazy->gamma, lazy->beta, lazy->relu)
-                     : launch_polyphase_input(s, x, V, d->H, d->W, d->Cin, up, T));
+    if (stages & 1) T2V_TRY(launch_polyphase_input(s, x, V, d->H, d->W, d->Cin, up, T, lazy));
     if (stages & 2) {
-        SkGemm g;
-        g.a = V; g.b = w_packed; g.c = Mm; g.scratch = workspace + (size_t)81 * T * ((size_t)d->Cin + d->Cout);
-        g.err = async_error_word();
-        g.a_group_stride = (long)T * d->Cin;
-        g.groups = 81; g.T = T; g.K = d->Cin; g.N = d->Cout; g.c_cs = d->Cout;
-        if (wino_gemm_skt_ok(81, rows, T, d->Cin, d->Cout, d->Cout)) {
-            T2V_TRY(launch_wino_gemm_skt(s, g, rows));
-        } else if (wino_gemm_skr_ok(81, rows, T, d->Cin, d->Cout, d->Cout)) {
-            T2V_TRY(launch_wino_gemm_skr(s, g, rows));
-        } else if (wino_gemm_sk_ok(81, T, d->Cin, d->Cout, d->Cout, rows)) {
-            g.rows = rows;
-            T2V_TRY(launch_wino_gemm_sk(s, g));
-        } else {      // one block per tile: the batched GEMM as a 1x1 conv over an 81 x T image
-            t2v_conv_desc gd;
-            memset(&gd, 0, sizeof(gd));
-            gd.H = 81; gd.W = T; gd.Cin = d->Cin; gd.Cout = d->Cout; gd.kH = gd.kW = 1; gd.stride = 1; gd.pad = 0;
-            gd.pad_mode = T2V_PAD_ZERO; gd.act = T2V_ACT_NONE; gd.act_scale = 1.f;
-            ConvPlan pl;
-            T2V_TRY(build_conv_plan(&gd, d->Cin, true, &pl));
-            if (T % pl.BM != 0 && pl.tile == kTileL) {
-                pl.tile = kTileQ;
-                conv_tile_dims(pl.tile, &pl.BM, &pl.BN);
-                pl.kp.ntiles = (gd.Cout + pl.BN - 1) / pl.BN;
-                pl.kp.mtiles = (pl.kp.M + pl.BM - 1) / pl.BM;
-                pl.nparts = pl.kp.nphases * pl.kp.mtiles;
-            }
-            T2V_REQUIRE(T % pl.BM == 0, "polyphase gemm: tile rows %d do not divide %d", pl.BM, T);
-            pl.kp.group_mtiles = T / pl.BM;
-            pl.kp.group_w_stride = (long)pl.Cout_p * d->Cin;
-            T2V_TRY(run_conv(ctx, s, pl, V, w_packed, nullptr, Mm, d->Cout, nullptr));
-        }
+        PositionGemm g;
+        g.groups = 81; g.rows = rows; g.T = T; g.K = d->Cin; g.N = d->Cout;
+        T2V_TRY(run_position_gemm(ctx, s, g, V, w_packed, Mm, workspace + (size_t)81 * T * ((size_t)d->Cin + d->Cout)));
     }
     if (stages & 4)
         T2V_TRY(launch_polyphase_output(s, Mm, bias, y, stats_partial, poly_out_h(d), poly_out_w(d), d->Cout, up, T));
@@ -665,7 +673,7 @@ int t2v_conv2d_forward_winograd_stages(t2v_ctx* ctx, void* stream, const t2v_con
 
 // The generator's forms of a Winograd conv (generator.hip: wino4_conv_stats, conv_norm_one) with the same launchers and
 // nothing of its own: nimg packed images (F(4x4) only) and, with mean_rstd, the previous layer's norm applied inside the
-// input transform -- launch_winograd4_input_lazy for F(4x4), the PolyLazyNorm of polyphase_forward.
+// input transform -- the LazyNorm of launch_winograd4_input for F(4x4) and of polyphase_forward.
 int t2v_conv2d_forward_winograd_batch_stages(t2v_ctx* ctx, void* stream, const t2v_conv_desc* d, int nimg, const float* x,
                                              int x_cs, long img_stride, const float* w_packed, const float* bias, float* y,
                                              int y_cs, float* stats_partial, float* workspace, int stages,
@@ -683,7 +691,7 @@ int t2v_conv2d_forward_winograd_batch_stages(t2v_ctx* ctx, void* stream, const t
         T2V_REQUIRE(polyphase_supported(d, x_cs), "polyphase forward: shape not supported (t2v_conv_polyphase_supported)");
         T2V_REQUIRE(y_cs == d->Cout, "polyphase forward: output channel storage must equal Cout");
         T2V_REQUIRE(nimg == 1 && !res && !xout, "polyphase batch forward: one image, no residual");
-        const PolyLazyNorm ln{mean_rstd, gamma, beta, relu};
+        const LazyNorm ln{mean_rstd, gamma, beta, relu};
         return polyphase_forward(ctx, s, d, x, w_packed, bias, y, stats_partial, workspace, stages, mean_rstd ? &ln : nullptr);
     }
     T2V_REQUIRE(winograd_supported(d, x_cs, d->algo), "winograd forward: shape/algo not supported (t2v_conv_winograd_supported)");
@@ -692,8 +700,9 @@ int t2v_conv2d_forward_winograd_batch_stages(t2v_ctx* ctx, void* stream, const t
                 "winograd batch forward: batches and the lazy norm are F(4x4,3x3) only");
     if (mean_rstd && (stages & 1)) {
         T2V_REQUIRE(relu == 0 || relu == 1, "winograd batch forward: relu %d", relu);
-        T2V_TRY(launch_winograd4_input_lazy(s, x, workspace, d->H, d->W, d->Cin, d->pad, d->pad_mode == T2V_PAD_REFLECT, mean_rstd,
-                                            gamma, beta, relu, res, xout, nimg, img_stride));
+        const LazyNorm ln{mean_rstd, gamma, beta, relu, res, xout};
+        T2V_TRY(launch_winograd4_input(s, x, workspace, d->H, d->W, d->Cin, d->pad, d->pad_mode == T2V_PAD_REFLECT, nimg, 0, nimg,
+                                       img_stride, &ln));
         stages &= ~1;
     }
     WinoBatch wb;
@@ -1048,18 +1057,10 @@ int t2v_conv_winograd_tile_rows(const t2v_conv_desc* d) {
 }
 int t2v_conv_winograd_gemm_form(const t2v_conv_desc* d, int nimg) {
     if (!d || d->algo != T2V_ALGO_WINOGRAD_F4 || nimg < 1) return -1;
-    const int T = wino_rows_batch(d, d->algo, nimg), rows = nimg * wino_tiles_real(d, d->algo);
-    if (wino_gemm_skt_ok(36, rows, T, d->Cin, d->Cout, d->Cout)) return T2V_GEMM_FIXED_GRID_RAGGED_TALL;
-    if (wino_gemm_skr_ok(36, rows, T, d->Cin, d->Cout, d->Cout)) return T2V_GEMM_FIXED_GRID_RAGGED;
-    if (wino_gemm_sk_ok(36, T, d->Cin, d->Cout, d->Cout, rows))
-        switch (wino_gemm_sk_tall_rows(36, rows, T, d->Cout)) {
-            case 160: return T2V_GEMM_FIXED_GRID_160x128;
-            case 256: return T2V_GEMM_FIXED_GRID_256x128;
-            default: return T % 128 == 0 ? T2V_GEMM_FIXED_GRID_128x128 : T2V_GEMM_FIXED_GRID_192x64;
-        }
-    ConvPlan pl;
-    if (build_winograd_gemm_plan(d, &pl, nimg) != T2V_OK) return -1;
-    return pl.tile == kTileL ? T2V_GEMM_TILE_PER_BLOCK_128x128 : T2V_GEMM_TILE_PER_BLOCK_64x64;
+    PositionGemm g;      // as winograd_forward fills it
+    g.groups = 36; g.rows = nimg * wino_tiles_real(d, d->algo); g.T = wino_rows_batch(d, d->algo, nimg);
+    g.K = d->Cin; g.N = d->Cout;
+    return position_gemm_form(g);
 }
 int t2v_conv2d_backward_weight_winograd_stages(t2v_ctx* ctx, void* stream, const t2v_conv_desc* d, int batch, int b0,
                                                int nb, const float* x, int x_cs, const float* dy, int dy_cs,
@@ -1210,26 +1211,12 @@ static int backward_data_winograd(t2v_ctx* ctx, void* stream, const t2v_conv_des
     float* dxp = scratch + (size_t)36 * Tp * x_cs;
     // dV[xi][t][c] = sum_n M_dy[xi][slot*Tp + t][n] * U[xi][n][c]: the batched GEMM of a conv with the channel roles swapped,
     // reading its rows out of the batch-wide matrix (input row pitch Tt, Tp rows per position)
-    if (forward_weights || (wino_gemm_sk_ok(36, Tp, d->Cout, x_cs, x_cs) && round_up(x_cs, 128) == x_cs)) {
-        SkGemm g;
-        g.b_kn = forward_weights;
-        g.a = Md + (size_t)slot * Tp * d->Cout; g.b = ut_packed; g.c = dV;
-        g.scratch = dxp + (size_t)(d->H + 2) * (d->W + 2) * x_cs;
-        g.err = async_error_word();
-        g.a_group_stride = (long)Tt * d->Cout;
-        g.groups = 36; g.T = Tp; g.K = d->Cout; g.N = x_cs; g.c_cs = x_cs;
-        T2V_TRY(launch_wino_gemm_sk(s, g));
-    } else {
-        t2v_conv_desc da = *d;
-        da.Cin = d->Cout;
-        da.Cout = d->Cin;
-        da.algo = T2V_ALGO_WINOGRAD_F4;
-        ConvPlan pl;
-        T2V_TRY(build_winograd_gemm_plan(&da, &pl));
-        T2V_REQUIRE((long)36 * Tt * d->Cout * 4 < 0x7fff0000L, "backward_data_winograd: M_dy too large for 32-bit buffer offsets");
-        pl.kp.Win = Tt;
-        T2V_TRY(run_conv(ctx, s, pl, Md + (size_t)slot * Tp * d->Cout, ut_packed, nullptr, dV, x_cs, nullptr));
-    }
+    // (rows not given: only the whole-tile fixed grid or one block per tile)
+    PositionGemm g;
+    g.groups = 36; g.T = Tp; g.K = d->Cout; g.N = x_cs;
+    g.a_pitch = Tt;
+    g.b_kn = forward_weights;
+    T2V_TRY(run_position_gemm(ctx, s, g, Md + (size_t)slot * Tp * d->Cout, ut_packed, dV, dxp + (size_t)(d->H + 2) * (d->W + 2) * x_cs));
     T2V_TRY(launch_winograd4_dgrad_output(s, dV, dxp, d->H, d->W, x_cs));
     return launch_reflect_pad_backward(s, dxp, dx, d->H, d->W, x_cs, 1);
 }

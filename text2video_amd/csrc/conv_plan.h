@@ -19,19 +19,13 @@ int build_conv_plan(const t2v_conv_desc* d, int x_cs, bool need_stats, ConvPlan*
 inline bool is_winograd(int algo) { return algo == T2V_ALGO_WINOGRAD || algo == T2V_ALGO_WINOGRAD_F4; }
 inline int wino_m(int algo) { return algo == T2V_ALGO_WINOGRAD_F4 ? 4 : 2; }          // output tile edge
 inline int wino_pos(int algo) { return (wino_m(algo) + 2) * (wino_m(algo) + 2); }    // transform positions: 16 | 36
-// tiles of the ceil(H/m) x ceil(W/m) grid, padded to whole 128-row GEMM tiles per transform position
 inline int wino_out_h(const t2v_conv_desc* d) { return d->H + 2 * d->pad - 2; }   // 3x3, stride 1
 inline int wino_out_w(const t2v_conv_desc* d) { return d->W + 2 * d->pad - 2; }
-inline int wino_tiles_padded(const t2v_conv_desc* d, int algo) {
-    const int m = wino_m(algo);
-    const int T = ((wino_out_h(d) + m - 1) / m) * ((wino_out_w(d) + m - 1) / m);
-    return wino_pad_tiles(T);
-}
+// tiles of the ceil(H/m) x ceil(W/m) grid, real and padded to whole GEMM tiles per transform position
+inline TileGrid wino_tile_grid(const t2v_conv_desc* d, int algo) { return tile_grid(wino_out_h(d), wino_out_w(d), wino_m(algo)); }
+inline int wino_tiles_padded(const t2v_conv_desc* d, int algo) { return wino_tile_grid(d, algo).Tp; }
+inline int wino_tiles_real(const t2v_conv_desc* d, int algo) { return wino_tile_grid(d, algo).T; }
 // GEMM rows per transform position for a batch of nimg images: F(4x4) packs the images' tiles and pads the total
-inline int wino_tiles_real(const t2v_conv_desc* d, int algo) {
-    const int m = wino_m(algo);
-    return ((wino_out_h(d) + m - 1) / m) * ((wino_out_w(d) + m - 1) / m);
-}
 inline int wino_rows_batch(const t2v_conv_desc* d, int algo, int nimg) {
     return (nimg > 1 && algo == T2V_ALGO_WINOGRAD_F4) ? wino_pad_tiles(nimg * wino_tiles_real(d, algo)) : wino_tiles_padded(d, algo);
 }
@@ -49,10 +43,11 @@ bool winograd_supported(const t2v_conv_desc* d, int x_cs, int algo);
 // (down) | 4x4 inputs = 8x8 outputs (up)
 bool polyphase_supported(const t2v_conv_desc* d, int x_cs);
 bool polyphase_pays(const t2v_conv_desc* d, int x_cs);      // ... and is the faster form (the generator's selection rule)
-inline int poly_tiles_real(const t2v_conv_desc* d) {
-    return d->transposed ? ((d->H + 3) / 4) * ((d->W + 3) / 4) : ((d->H / 2 + 3) / 4) * ((d->W / 2 + 3) / 4);
+inline TileGrid poly_tile_grid(const t2v_conv_desc* d) {
+    return d->transposed ? tile_grid(d->H, d->W, 4) : tile_grid(d->H / 2, d->W / 2, 4);
 }
-inline int poly_tiles_padded(const t2v_conv_desc* d) { return wino_pad_tiles(poly_tiles_real(d)); }
+inline int poly_tiles_real(const t2v_conv_desc* d) { return poly_tile_grid(d).T; }
+inline int poly_tiles_padded(const t2v_conv_desc* d) { return poly_tile_grid(d).Tp; }
 inline int poly_out_h(const t2v_conv_desc* d) { return d->transposed ? 2 * d->H : d->H / 2; }
 inline int poly_out_w(const t2v_conv_desc* d) { return d->transposed ? 2 * d->W : d->W / 2; }
 inline int poly_m(const t2v_conv_desc* d) { return d->transposed ? 8 : 4; }       // output tile edge (statistics partial geometry)
@@ -60,17 +55,10 @@ inline size_t polyphase_workspace_floats(const t2v_conv_desc* d) {              
     return (size_t)81 * poly_tiles_padded(d) * ((size_t)d->Cin + d->Cout) + wino_gemm_sk_scratch_floats();
 }
 // lazy != null: x is the previous layer's raw conv output; its norm (+ ReLU) is applied inside the input transform
-struct PolyLazyNorm {
-    const float* mean_rstd;
-    const float* gamma;
-    const float* beta;
-    int relu;
-};
 int polyphase_forward(t2v_ctx* ctx, hipStream_t s, const t2v_conv_desc* d, const float* x, const float* w_packed,
                       const float* bias, float* y, float* stats_partial, float* workspace, int stages,
-                      const PolyLazyNorm* lazy = nullptr);
+                      const LazyNorm* lazy = nullptr);
 int best_conv_algo(const t2v_conv_desc* d, int x_cs, int cap);
-int build_winograd_gemm_plan(const t2v_conv_desc* d, ConvPlan* pl, int nimg = 1);
 // A batch of images through one Winograd conv (F(4x4,3x3) only when nimg > 1): the images' maps x / y are
 // `img_stride_x` / H*W*Cout floats apart, V and M hold nimg*Tp tile rows per transform position (one GEMM with
 // M = nimg*Tp rows per position), the statistics partials follow each other image by image.

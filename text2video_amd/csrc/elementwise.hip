@@ -10,6 +10,7 @@
 
 #include "t2v_internal.h"
 #include "norm_pool.h"
+#include "transform_common.h"
 
 namespace t2v {
 
@@ -215,27 +216,27 @@ __global__ __launch_bounds__(256) void inorm_apply_kernel(const float4* __restri
         const int c4 = (int)(i % C4);
         const float4 a = mean_rstd[2 * c4], b = mean_rstd[2 * c4 + 1];  // (m0,r0,m1,r1) (m2,r2,m3,r3)
         float4 v = x[i];
-        v.x = (v.x - a.x) * a.y;
-        v.y = (v.y - a.z) * a.w;
-        v.z = (v.z - b.x) * b.y;
-        v.w = (v.w - b.z) * b.w;
+        v.x = norm_scale(v.x, a.x, a.y);
+        v.y = norm_scale(v.y, a.z, a.w);
+        v.z = norm_scale(v.z, b.x, b.y);
+        v.w = norm_scale(v.w, b.z, b.w);
         if (gamma) {
             const float4 gm = gamma[c4], bt = beta[c4];
-            v.x = v.x * gm.x + bt.x;
-            v.y = v.y * gm.y + bt.y;
-            v.z = v.z * gm.z + bt.z;
-            v.w = v.w * gm.w + bt.w;
+            v.x = norm_affine(v.x, gm.x, bt.x);
+            v.y = norm_affine(v.y, gm.y, bt.y);
+            v.z = norm_affine(v.z, gm.z, bt.z);
+            v.w = norm_affine(v.w, gm.w, bt.w);
         }
-        if (relu == 1) {
-            v.x = fmaxf(v.x, 0.f);
-            v.y = fmaxf(v.y, 0.f);
-            v.z = fmaxf(v.z, 0.f);
-            v.w = fmaxf(v.w, 0.f);
-        } else if (relu == 2) {  // LeakyReLU(0.2)
-            v.x = v.x > 0.f ? v.x : 0.2f * v.x;
-            v.y = v.y > 0.f ? v.y : 0.2f * v.y;
-            v.z = v.z > 0.f ? v.z : 0.2f * v.z;
-            v.w = v.w > 0.f ? v.w : 0.2f * v.w;
+        if (relu == 1) {          // (one uniform branch per float4, the activation a constant inside it)
+            v.x = norm_act(v.x, 1);
+            v.y = norm_act(v.y, 1);
+            v.z = norm_act(v.z, 1);
+            v.w = norm_act(v.w, 1);
+        } else if (relu == 2) {
+            v.x = norm_act(v.x, 2);
+            v.y = norm_act(v.y, 2);
+            v.z = norm_act(v.z, 2);
+            v.w = norm_act(v.w, 2);
         }
         if (res1) {
             const float4 r = res1[i];
@@ -714,9 +715,6 @@ int launch_reflect_pad_backward(hipStream_t s, const float* dxp, float* dx, int 
 
 // norm backward, stage 1: per channel  S0 = sum g,  S1 = sum g*xhat   with g = dy * act'(gamma*xhat+beta)
 // block = 64 channels x 4 pixel lanes; grid = (C/64, slices); partial[slice][c] (float2), then a final pass.
-__device__ __forceinline__ float act_grad(float pre, int relu) {
-    return relu == 1 ? (pre > 0.f ? 1.f : 0.f) : (relu == 2 ? (pre > 0.f ? 1.f : 0.2f) : 1.f);
-}
 __global__ __launch_bounds__(256) void inorm_bwd_reduce_kernel(const float4* __restrict__ x, const float4* __restrict__ dy,
                                                                const float2* __restrict__ mean_rstd,
                                                                const float* __restrict__ gamma,
@@ -742,10 +740,9 @@ __global__ __launch_bounds__(256) void inorm_bwd_reduce_kernel(const float4* __r
             const float xs[4] = {xv.x, xv.y, xv.z, xv.w}, gs[4] = {gv.x, gv.y, gv.z, gv.w};
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
-                const float xh = (xs[k] - mean[k]) * rstd[k];
-                const float g = gs[k] * act_grad(ga[k] * xh + be[k], relu);
-                s0[k] += g;
-                s1[k] += g * xh;
+                const NormBwdTerms t = norm_bwd_terms(xs[k], gs[k], mean[k], rstd[k], ga[k], be[k], relu);
+                s0[k] += t.g;
+                s1[k] += t.g * t.xh;
             }
         };
         // four pixels' loads in flight per thread, added in pixel order (the sums do not depend on the unrolling)
@@ -841,9 +838,7 @@ __global__ __launch_bounds__(256) void inorm_bwd_apply_kernel(const float4* __re
         float o[4];
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
-            const float xh = (xs[k] - mean[k]) * rstd[k];
-            const float g = gs[k] * act_grad(ga[k] * xh + be[k], relu);
-            o[k] = rstd[k] * ga[k] * (g - k0[k] - xh * k1[k]);
+            o[k] = norm_bwd_dx(norm_bwd_terms(xs[k], gs[k], mean[k], rstd[k], ga[k], be[k], relu), rstd[k], ga[k], k0[k], k1[k]);
         }
         return make_float4(o[0], o[1], o[2], o[3]);
     };

@@ -243,7 +243,7 @@ struct Runner {
         T2V_REQUIRE(!lazy_out || (relu == 1 && !res1 && !res2), "internal: a lazy output carries a plain norm + ReLU");
         if (L.cd.algo == T2V_ALGO_POLYPHASE) {
             const int Ho = poly_out_h(&L.cd), Wo = poly_out_w(&L.cd);
-            const PolyLazyNorm ln{mr, g.norm_affine ? layers[l - 1].gamma : nullptr, g.norm_affine ? layers[l - 1].beta : nullptr, 1};
+            const LazyNorm ln{mr, g.norm_affine ? layers[l - 1].gamma : nullptr, g.norm_affine ? layers[l - 1].beta : nullptr, 1};
             T2V_TRY(polyphase_forward(ctx, s, &L.cd, x, w.w, w.bias, y, stats, b.wino[sc], 7, lazy_in ? &ln : nullptr));
             T2V_TRY(launch_inorm_finalize_winograd(s, stats, poly_m(&L.cd), Ho, Wo, Cout, g.eps, mr, 1, fin_of(im)));
             if (lazy_out) return T2V_OK;
@@ -306,11 +306,12 @@ struct Runner {
         const t2v_conv_desc& cd = L.cd;
         if (g.norm_affine) T2V_REQUIRE(w.gamma && w.beta, "layer %d: norm_affine=1 but gamma/beta missing", li - 1);
         T2V_REQUIRE(b.mr_stride == (size_t)2 * cd.Cout, "internal: chain scratch layout");
-        if (lz)
-            T2V_TRY(launch_winograd4_input_lazy(s, x, b.wino[sc], cd.H, cd.W, cd.Cin, cd.pad, cd.pad_mode == T2V_PAD_REFLECT,
-                                                b.mean_rstd[sc], g.norm_affine ? lz->norm->gamma : nullptr,
-                                                g.norm_affine ? lz->norm->beta : nullptr, lz->relu, lz->res, lz->xout, nimg,
-                                                (long)b.bott));
+        if (lz) {
+            const LazyNorm ln{b.mean_rstd[sc], g.norm_affine ? lz->norm->gamma : nullptr, g.norm_affine ? lz->norm->beta : nullptr,
+                              lz->relu, lz->res, lz->xout};
+            T2V_TRY(launch_winograd4_input(s, x, b.wino[sc], cd.H, cd.W, cd.Cin, cd.pad, cd.pad_mode == T2V_PAD_REFLECT, nimg, 0,
+                                           nimg, (long)b.bott, &ln));
+        }
         WinoBatch wb;
         wb.nimg = nimg;
         wb.img_stride_x = (long)b.bott;

@@ -18,86 +18,14 @@
 #include "t2v_internal.h"
 #include "norm_pool.h"
 #include "polyphase_consts.h"
+#include "transform_common.h"
 
 namespace t2v {
 
-namespace {
+// at most 65535 x 16 blocks: the cap decides how many tiles a thread of the grid-stride transforms walks
+static inline int pp_grid(long n, int block) { return capped_grid(n, block, 65535L * 16); }
 
-inline int pp_grid(long n, int block) {
-    long g = (n + block - 1) / block;
-    if (g > 65535L * 16) g = 65535L * 16;
-    return (int)(g < 1 ? 1 : g);
-}
-
-template <int K>
-__device__ __forceinline__ float pdot(const double (&row)[K], const float (&v)[K]) {
-    float acc = 0.f;
-    bool first = true;
-#pragma unroll
-    for (int k = 0; k < K; ++k) {
-        if (row[k] != 0.0) {   // compile-time after unrolling: x * 0 is not foldable under IEEE rules
-            const float t = (float)row[k] * v[k];
-            acc = first ? t : acc + t;
-            first = false;
-        }
-    }
-    return acc;
-}
-
-// B^T of F(4,2) (5 x 5) = rows 0..4 of kBU;  A^T (4 x 5) = columns 0..4 of kAD
-struct PpBT {
-    double m[5][5];
-    constexpr PpBT() : m{} {
-        for (int r = 0; r < 5; ++r)
-            for (int c = 0; c < 5; ++c) m[r][c] = pp::kBU[r][c];
-    }
-};
-struct PpAT {
-    double m[4][5];
-    constexpr PpAT() : m{} {
-        for (int r = 0; r < 4; ++r)
-            for (int c = 0; c < 5; ++c) m[r][c] = pp::kAD[r][c];
-    }
-};
-constexpr PpBT kBT5{};
-constexpr PpAT kAT4{};
-
-// the 128-pixel statistics partial of an output-transform block (64 channels x 4 lanes x 32 values): same arithmetic and the
-// same partial layout as winograd.hip's block_stats_128, so inorm_finalize pools it with the geometry of wm x wm tiles
-__device__ __forceinline__ void pp_block_stats_128(const float (&val)[32], unsigned mask, float (*sh)[64], int tl, int cl, bool ok,
-                                                   float2* __restrict__ stats, int N, int n) {
-    if (stats == nullptr) return;
-    sh[tl][cl] = (float)__popc(mask);
-    __syncthreads();
-    const float cnt = (sh[0][cl] + sh[1][cl]) + (sh[2][cl] + sh[3][cl]);
-    __syncthreads();
-    const float inv_cnt = cnt > 0.f ? 1.f / cnt : 0.f;
-    float mean_b = 0.f;
-#pragma unroll
-    for (int pass = 0; pass < 2; ++pass) {
-        float v[32];
-#pragma unroll
-        for (int i = 0; i < 32; ++i) {
-            const float dlt = val[i] - mean_b;
-            v[i] = ((mask >> i) & 1u) ? (pass ? dlt * dlt : val[i]) : 0.f;
-        }
-#pragma unroll
-        for (int w = 16; w >= 1; w >>= 1)
-#pragma unroll
-            for (int i = 0; i < w; ++i) v[i] += v[i + w];
-        sh[tl][cl] = v[0];
-        __syncthreads();
-        const float tot = (sh[0][cl] + sh[1][cl]) + (sh[2][cl] + sh[3][cl]);
-        __syncthreads();
-        if (pass == 0) {
-            mean_b = tot * inv_cnt;
-        } else if (tl == 0 && ok) {
-            stats[(size_t)blockIdx.x * N + n] = make_float2(mean_b, tot);
-        }
-    }
-}
-
-}  // namespace
+// B^T of F(4,2) (5 x 5) = rows 0..4 of pp::kBU;  A^T (4 x 5) = the first five columns of pp::kAD: cdot takes both in place
 
 // ---- weights: U[pr*9+pc][n][c] = sum_{a,b} G[pr][a] G[pc][b] g[a][b], in fp64, rounded once ---------------------------------------
 // UP = false: w is Conv2d's [Cout][Cin][3][3]; UP = true: ConvTranspose2d's [Cin][Cout][3][3]
@@ -151,8 +79,8 @@ int launch_polyphase_weight(hipStream_t s, const float* w, float* U, int Cout, i
 // F(4,2), the first four are also the 1-tap samples.  The four (transformed | plain) x (transformed | plain) sub-blocks are
 // done one after the other, so that at most 25 values per channel are live.
 // NORM: x is the previous layer's conv output that has not gone through its norm layer yet; the transform applies
-// relu((x - mean) * rstd [* gamma + beta]) on the fly -- inorm_apply_kernel's arithmetic in the same order, so the result is
-// bit-identical to apply-then-transform -- and that layer's apply pass (a read and a write of the map) is dropped.  The zero
+// relu((x - mean) * rstd [* gamma + beta]) on the fly -- by norm_apply (transform_common.h), the function inorm_apply_kernel
+// calls, so the result is bit-identical to apply-then-transform -- and that layer's apply pass (a read and a write of the map) is dropped.  The zero
 // padding pads the NORMALISED map: samples outside stay exact zeros.
 template <bool UP, bool NORM>
 __global__ __launch_bounds__(256) void polyphase_input_kernel(const float2* __restrict__ x, float2* __restrict__ V, int H, int W,
@@ -187,16 +115,8 @@ __global__ __launch_bounds__(256) void polyphase_input_kernel(const float2* __re
             if (!((unsigned)yy < (unsigned)H && (unsigned)xx < (unsigned)W)) return make_float2(0.f, 0.f);
             float2 v = x[((long)yy * W + xx) * C2 + c2];
             if (NORM) {
-                v.x = (v.x - mr0.x) * mr0.y;
-                v.y = (v.y - mr1.x) * mr1.y;
-                if (gamma) {
-                    v.x = v.x * gm.x + bt.x;
-                    v.y = v.y * gm.y + bt.y;
-                }
-                if (relu == 1) {
-                    v.x = fmaxf(v.x, 0.f);
-                    v.y = fmaxf(v.y, 0.f);
-                }
+                v.x = norm_apply(v.x, mr0.x, mr0.y, gamma != nullptr, gm.x, bt.x, relu == 1);
+                v.y = norm_apply(v.y, mr1.x, mr1.y, gamma != nullptr, gm.y, bt.y, relu == 1);
             }
             return v;
         };
@@ -215,8 +135,8 @@ __global__ __launch_bounds__(256) void polyphase_input_kernel(const float2* __re
                 }
 #pragma unroll
                 for (int q = 0; q < 5; ++q) {
-                    rx[a][q] = pdot<5>(kBT5.m[q], dx);
-                    ry[a][q] = pdot<5>(kBT5.m[q], dy);
+                    rx[a][q] = cdot<5>(pp::kBU[q], dx);
+                    ry[a][q] = cdot<5>(pp::kBU[q], dy);
                 }
             }
 #pragma unroll
@@ -228,7 +148,7 @@ __global__ __launch_bounds__(256) void polyphase_input_kernel(const float2* __re
                     cy[a] = ry[a][q];
                 }
 #pragma unroll
-                for (int p = 0; p < 5; ++p) store(p, q, pdot<5>(kBT5.m[p], cx), pdot<5>(kBT5.m[p], cy));
+                for (int p = 0; p < 5; ++p) store(p, q, cdot<5>(pp::kBU[p], cx), cdot<5>(pp::kBU[p], cy));
             }
         }
         // (2) transformed rows x plain columns: per plain column a 5-vector down the rows
@@ -242,7 +162,7 @@ __global__ __launch_bounds__(256) void polyphase_input_kernel(const float2* __re
                 cy[a] = v.y;
             }
 #pragma unroll
-            for (int p = 0; p < 5; ++p) store(p, 5 + b, pdot<5>(kBT5.m[p], cx), pdot<5>(kBT5.m[p], cy));
+            for (int p = 0; p < 5; ++p) store(p, 5 + b, cdot<5>(pp::kBU[p], cx), cdot<5>(pp::kBU[p], cy));
         }
         // (3) plain rows x transformed columns
 #pragma unroll
@@ -255,7 +175,7 @@ __global__ __launch_bounds__(256) void polyphase_input_kernel(const float2* __re
                 dy[b] = v.y;
             }
 #pragma unroll
-            for (int q = 0; q < 5; ++q) store(5 + a, q, pdot<5>(kBT5.m[q], dx), pdot<5>(kBT5.m[q], dy));
+            for (int q = 0; q < 5; ++q) store(5 + a, q, cdot<5>(pp::kBU[q], dx), cdot<5>(pp::kBU[q], dy));
         }
         // (4) plain x plain: copies
 #pragma unroll
@@ -268,18 +188,19 @@ __global__ __launch_bounds__(256) void polyphase_input_kernel(const float2* __re
     }
 }
 // H, W: the INPUT map; tiles: 4x4 outputs of the H/2 x W/2 map (down) | 4x4 inputs (up); Tt = padded tile rows of V.
-// mean_rstd != null: x still has to go through its norm layer (relu: 0 | 1 after it)
-int launch_polyphase_input(hipStream_t s, const float* x, float* V, int H, int W, int C, int up, int Tt, const float* mean_rstd,
-                           const float* gamma, const float* beta, int relu) {
-    T2V_REQUIRE((gamma == nullptr) == (beta == nullptr) && (relu == 0 || relu == 1), "polyphase_input: bad norm arguments");
-    const int TH = up ? (H + 3) / 4 : (H / 2 + 3) / 4, TW = up ? (W + 3) / 4 : (W / 2 + 3) / 4;
-    const int T = TH * TW;
+// lazy != null: x still has to go through its norm layer (relu: 0 | 1 after it)
+int launch_polyphase_input(hipStream_t s, const float* x, float* V, int H, int W, int C, int up, int Tt, const LazyNorm* lazy) {
+    const LazyNorm none{};
+    const LazyNorm& ln = lazy ? *lazy : none;
+    T2V_REQUIRE((ln.gamma == nullptr) == (ln.beta == nullptr) && (ln.relu == 0 || ln.relu == 1) && !ln.res && !ln.xout,
+                "polyphase_input: bad norm arguments");
+    const TileGrid tg = up ? tile_grid(H, W, 4) : tile_grid(H / 2, W / 2, 4);
     const int grid = pp_grid((long)Tt * (C / 2), 256);
-    auto kern = up ? (mean_rstd ? polyphase_input_kernel<true, true> : polyphase_input_kernel<true, false>)
-                   : (mean_rstd ? polyphase_input_kernel<false, true> : polyphase_input_kernel<false, false>);
+    auto kern = up ? (ln.mean_rstd ? polyphase_input_kernel<true, true> : polyphase_input_kernel<true, false>)
+                   : (ln.mean_rstd ? polyphase_input_kernel<false, true> : polyphase_input_kernel<false, false>);
     hipLaunchKernelGGL(kern, dim3(grid), dim3(256), 0, s, reinterpret_cast<const float2*>(x), reinterpret_cast<float2*>(V), H, W,
-                       C / 2, TW, T, Tt, reinterpret_cast<const float2*>(mean_rstd), reinterpret_cast<const float2*>(gamma),
-                       reinterpret_cast<const float2*>(beta), relu);
+                       C / 2, tg.TW, tg.T, Tt, reinterpret_cast<const float2*>(ln.mean_rstd),
+                       reinterpret_cast<const float2*>(ln.gamma), reinterpret_cast<const float2*>(ln.beta), ln.relu);
     T2V_HIP_CHECK(hipGetLastError());
     return T2V_OK;
 }
@@ -289,40 +210,7 @@ __global__ __launch_bounds__(256) void polyphase_output_down_kernel(const float*
                                                                     float* __restrict__ y, float2* __restrict__ stats, int Ho,
                                                                     int Wo, int N, int TW, int T, int Tt) {
     __shared__ float sh[4][64];
-    const int cl = threadIdx.x & 63, tl = threadIdx.x >> 6;
-    const int n = blockIdx.y * 64 + cl;
-    const bool ok = n < N;
-    const float bv = (ok && bias) ? bias[n] : 0.f;
-    float out[32];
-    unsigned mask = 0;
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-        const long tile = (long)blockIdx.x * 8 + tl + 4 * i;
-        const bool tv = tile < T;
-        float r[4][9];   // r[i2][pc] = sum_pr A[i2][pr] m[pr][pc]
-#pragma unroll
-        for (int pc = 0; pc < 9; ++pc) {
-            float m[9];
-#pragma unroll
-            for (int pr = 0; pr < 9; ++pr) m[pr] = (ok && tv) ? Mm[((long)(pr * 9 + pc) * Tt + tile) * N + n] : 0.f;
-#pragma unroll
-            for (int i2 = 0; i2 < 4; ++i2) r[i2][pc] = pdot<9>(pp::kAD[i2], m);
-        }
-        const int ty = (int)(tile / TW), tx = (int)(tile - (long)ty * TW);
-#pragma unroll
-        for (int i2 = 0; i2 < 4; ++i2)
-#pragma unroll
-            for (int j2 = 0; j2 < 4; ++j2) {
-                const float v = pdot<9>(pp::kAD[j2], r[i2]) + bv;
-                out[i * 16 + i2 * 4 + j2] = v;
-                const int oy = 4 * ty + i2, ox = 4 * tx + j2;
-                if (tv && oy < Ho && ox < Wo) {
-                    mask |= 1u << (i * 16 + i2 * 4 + j2);
-                    if (ok) y[((long)oy * Wo + ox) * N + n] = v;
-                }
-            }
-    }
-    pp_block_stats_128(out, mask, sh, tl, cl, ok, stats, N, n);
+    output_transform_4x4<9>(pp::kAD, Mm, bias, y, stats, Ho, Wo, N, TW, T, Tt, sh, [](float v) { return v; });
 }
 
 // ---- output transform, up: y (8 x 8 per tile) = A M A^T + bias; a thread makes HALF a tile (4 output rows x 8 columns = 32
@@ -349,7 +237,7 @@ __global__ __launch_bounds__(256) void polyphase_output_up_kernel(const float* _
         for (int k = 0; k < 2; ++k) {
             const int q = 2 * half + k;                                  // plain sample / F(4,2) output index 0..3
             r[2 * k][pc] = (ok && tv) ? Mm[((long)((5 + q) * 9 + pc) * Tt + tile) * N + n] : 0.f;
-            r[2 * k + 1][pc] = half ? (k ? pdot<5>(kAT4.m[3], m) : pdot<5>(kAT4.m[2], m)) : (k ? pdot<5>(kAT4.m[1], m) : pdot<5>(kAT4.m[0], m));
+            r[2 * k + 1][pc] = half ? (k ? cdot<5>(pp::kAD[3], m) : cdot<5>(pp::kAD[2], m)) : (k ? cdot<5>(pp::kAD[1], m) : cdot<5>(pp::kAD[0], m));
         }
     }
     const int ty = (int)(tile / TW), tx = (int)(tile - (long)ty * TW);
@@ -359,7 +247,7 @@ __global__ __launch_bounds__(256) void polyphase_output_up_kernel(const float* _
     for (int i2 = 0; i2 < 4; ++i2)
 #pragma unroll
         for (int j2 = 0; j2 < 8; ++j2) {
-            const float v = pdot<9>(pp::kAU[j2], r[i2]) + bv;
+            const float v = cdot<9>(pp::kAU[j2], r[i2]) + bv;
             out[i2 * 8 + j2] = v;
             const int oy = 8 * ty + 4 * half + i2, ox = 8 * tx + j2;
             if (tv && oy < Ho && ox < Wo) {
@@ -367,13 +255,13 @@ __global__ __launch_bounds__(256) void polyphase_output_up_kernel(const float* _
                 if (ok) y[((long)oy * Wo + ox) * N + n] = v;
             }
         }
-    pp_block_stats_128(out, mask, sh, tl, cl, ok, stats, N, n);
+    block_stats_128(out, mask, sh, tl, cl, ok, stats, N, n);
 }
 // Ho, Wo: the OUTPUT map
 int launch_polyphase_output(hipStream_t s, const float* Mm, const float* bias, float* y, float* stats, int Ho, int Wo, int N,
                             int up, int Tt) {
-    const int e = up ? 8 : 4;
-    const int TW = (Wo + e - 1) / e, T = ((Ho + e - 1) / e) * TW, Tp = wino_pad_tiles(T);
+    const TileGrid tg = tile_grid(Ho, Wo, up ? 8 : 4);
+    const int TW = tg.TW, T = tg.T, Tp = tg.Tp;
     if (up)
         hipLaunchKernelGGL(polyphase_output_up_kernel, dim3(Tp / 2, (N + 63) / 64), dim3(256), 0, s, Mm, bias, y,
                            reinterpret_cast<float2*>(stats), Ho, Wo, N, TW, T, Tt);

@@ -189,22 +189,43 @@ inline int wino_pad_tiles(int T) {
     const int a = (T + 63) / 64 * 64, b = (T + 127) / 128 * 128;
     return (b - a) * 8 >= b ? a : b;
 }
+// the tile grid of an Ho x Wo output map cut into edge x edge tiles (ragged at the bottom / right): TW tiles per row, T in
+// all, Tp = T padded for the GEMM.  Every transform launcher and the planning inlines of conv_plan.h take it from here.
+struct TileGrid {
+    int TW, T, Tp;
+};
+inline TileGrid tile_grid(int Ho, int Wo, int edge) {
+    const int TW = (Wo + edge - 1) / edge, T = ((Ho + edge - 1) / edge) * TW;
+    return {TW, T, wino_pad_tiles(T)};
+}
+// blocks of a grid-stride launch over n items, at most `cap`
+inline int capped_grid(long n, int block, long cap) {
+    const long g = (n + block - 1) / block;
+    return (int)(g > cap ? cap : g < 1 ? 1 : g);
+}
+// x is a conv output that has not gone through its norm layer yet: the input transform applies [relu](norm(x)) on the fly
+struct LazyNorm {
+    const float* mean_rstd = nullptr;
+    const float* gamma = nullptr;    // both or neither
+    const float* beta = nullptr;
+    int relu = 0;                    // 0 | 1
+    // F(4x4,3x3) only, relu == 0: norm(x) + res goes into the transform and is also written to xout (both or neither)
+    const float* res = nullptr;
+    float* xout = nullptr;
+};
 int launch_winograd_weight(hipStream_t s, const float* w, float* U, int Cout, int Cin, int Cout_p, int Cin_s, int adjoint = 0);
 int launch_winograd_input(hipStream_t s, const float* x, float* V, int H, int W, int C, int pad, int reflect);
 int launch_winograd_output(hipStream_t s, const float* Mm, const float* bias, float* y, float* stats, int H, int W, int N);
 int launch_winograd4_weight(hipStream_t s, const float* w, float* U, int Cout, int Cin, int Cout_p, int Cin_s, int adjoint = 0);
-// nimg == 0: slot layout (image -> slot `image` of `batch` slots of Tp rows); nimg > 0: packed batch of nimg images
+// nimg == 0: slot layout (image -> slot `image` of `batch` slots of Tp rows); nimg > 0: packed batch of nimg images.
+// lazy (packed only): x still has to go through its norm layer (winograd4_input_kernel<1|2>)
 int launch_winograd4_input(hipStream_t s, const float* x, float* V, int H, int W, int C, int pad, int reflect, int batch = 1,
-                           int image = 0, int nimg = 0, long img_stride = 0);
-// input transform of a conv output that still has to go through its norm layer (winograd4_input_kernel<1|2>)
-int launch_winograd4_input_lazy(hipStream_t s, const float* x, float* V, int H, int W, int C, int pad, int reflect,
-                                const float* mean_rstd, const float* gamma, const float* beta, int relu_only,
-                                const float* res, float* xout, int nimg = 1, long img_stride = 0);
+                           int image = 0, int nimg = 0, long img_stride = 0, const LazyNorm* lazy = nullptr);
 int launch_winograd4_dgrad_output(hipStream_t s, const float* dV, float* dxp, int H, int W, int C);
 // polyphase.hip
 int launch_polyphase_weight(hipStream_t s, const float* w, float* U, int Cout, int Cin, int Cout_p, int Cin_s, int up);
 int launch_polyphase_input(hipStream_t s, const float* x, float* V, int H, int W, int C, int up, int Tt,
-                           const float* mean_rstd = nullptr, const float* gamma = nullptr, const float* beta = nullptr, int relu = 0);
+                           const LazyNorm* lazy = nullptr);
 int launch_polyphase_output(hipStream_t s, const float* Mm, const float* bias, float* y, float* stats, int Ho, int Wo, int N,
                             int up, int Tt);
 int launch_winograd4_dy(hipStream_t s, const float* dy, float* Md, int Ho, int Wo, int N, int dy_cs, int batch, int image);

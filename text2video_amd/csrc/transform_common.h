@@ -1,0 +1,156 @@
+// transform_common.h -- device functions shared by the transform passes around the batched per-position GEMM (winograd.hip,
+// polyphase.hip) and by the norm kernels whose arithmetic those passes fold in (elementwise.hip).  Every piece exists once:
+// a kernel that applies a norm "on the fly" calls the function the stand-alone norm kernel calls, so the two agree bit for
+// bit by construction (the build uses -ffp-contract=off: inlining into different kernels cannot change a result).
+#pragma once
+#include <hip/hip_runtime.h>
+
+namespace t2v {
+
+// sum_k row[k] * v[k] over the first K entries of a row of a constant matrix.  Zero coefficients are skipped and the first
+// term is not an add (compile-time after unrolling: x * 0 is not foldable under IEEE rules).
+template <int K, int R>
+__device__ __forceinline__ float cdot(const double (&row)[R], const float (&v)[K]) {
+    static_assert(K <= R, "cdot: more values than coefficients");
+    float acc = 0.f;
+    bool first = true;
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+        if (row[k] != 0.0) {
+            const float t = (float)row[k] * v[k];
+            acc = first ? t : acc + t;
+            first = false;
+        }
+    }
+    return acc;
+}
+// ... down column `col` of the matrix: sum_k m[k][col] * v[k], the product with the transposed matrix.  V: float, or float2
+// for a channel pair (component-wise)
+template <int K, int R, int C, class V>
+__device__ __forceinline__ V cdot_col(const double (&m)[R][C], int col, const V (&v)[K]) {
+    static_assert(K <= R, "cdot_col: more values than coefficients");
+    V acc{};
+    bool first = true;
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+        if (m[k][col] != 0.0) {
+            const V t = (float)m[k][col] * v[k];
+            acc = first ? t : acc + t;
+            first = false;
+        }
+    }
+    return acc;
+}
+
+// The consumer side of a norm layer, per value, in two steps: (x - mean) * rstd [* gamma + beta], then the activation
+// (relu: 0 none, 1 ReLU, 2 LeakyReLU(0.2)).  inorm_apply_kernel and the input transforms that take a conv output before
+// its norm all call these.
+__device__ __forceinline__ float norm_scale(float x, float mean, float rstd) { return (x - mean) * rstd; }
+__device__ __forceinline__ float norm_affine(float v, float gamma, float beta) { return v * gamma + beta; }
+__device__ __forceinline__ float norm_act(float v, int relu) {
+    return relu == 1 ? fmaxf(v, 0.f) : (relu == 2 ? (v > 0.f ? v : 0.2f * v) : v);
+}
+__device__ __forceinline__ float norm_apply(float x, float mean, float rstd, bool affine, float gamma, float beta, int relu) {
+    const float v = norm_scale(x, mean, rstd);
+    return norm_act(affine ? norm_affine(v, gamma, beta) : v, relu);
+}
+
+// The norm backward, per value: xhat and g = dy * act'(gamma * xhat + beta) (what the per-channel sums S0 = sum g,
+// S1 = sum g * xhat are made of), then dx = rstd * gamma * (g - S0/N - xhat * S1/N) with k0 = S0/N, k1 = S1/N.
+__device__ __forceinline__ float act_grad(float pre, int relu) {
+    return relu == 1 ? (pre > 0.f ? 1.f : 0.f) : (relu == 2 ? (pre > 0.f ? 1.f : 0.2f) : 1.f);
+}
+struct NormBwdTerms {
+    float xh, g;
+};
+__device__ __forceinline__ NormBwdTerms norm_bwd_terms(float x, float dy, float mean, float rstd, float gamma, float beta,
+                                                       int relu) {
+    const float xh = (x - mean) * rstd;
+    return {xh, dy * act_grad(gamma * xh + beta, relu)};
+}
+__device__ __forceinline__ float norm_bwd_dx(const NormBwdTerms& t, float rstd, float gamma, float k0, float k1) {
+    return rstd * gamma * (t.g - k0 - t.xh * k1);
+}
+
+// (mean, M2) of a block's <= 128 valid output pixels per channel: each of the 4 tile lanes holds 32 pixel
+// slots, `mask` marks the ones inside the image (all of them except in ragged / padding tiles).  Two passes,
+// tree-summed (exact for constant maps over power-of-two counts), written as the partial inorm_finalize
+// merges; the partial's pixel count is recomputed there from the geometry.
+__device__ __forceinline__ void block_stats_128(const float (&val)[32], unsigned mask, float (*sh)[64], int tl, int cl,
+                                                bool ok, float2* __restrict__ stats, int N, int n) {
+    if (stats == nullptr) return;
+    sh[tl][cl] = (float)__popc(mask);
+    __syncthreads();
+    const float cnt = (sh[0][cl] + sh[1][cl]) + (sh[2][cl] + sh[3][cl]);
+    __syncthreads();
+    const float inv_cnt = cnt > 0.f ? 1.f / cnt : 0.f;
+    float mean_b = 0.f;
+#pragma unroll
+    for (int pass = 0; pass < 2; ++pass) {
+        float v[32];
+#pragma unroll
+        for (int i = 0; i < 32; ++i) {
+            const float dlt = val[i] - mean_b;
+            v[i] = ((mask >> i) & 1u) ? (pass ? dlt * dlt : val[i]) : 0.f;
+        }
+#pragma unroll
+        for (int w = 16; w >= 1; w >>= 1)
+#pragma unroll
+            for (int i = 0; i < w; ++i) v[i] += v[i + w];
+        sh[tl][cl] = v[0];
+        __syncthreads();
+        const float tot = (sh[0][cl] + sh[1][cl]) + (sh[2][cl] + sh[3][cl]);
+        __syncthreads();
+        if (pass == 0) {
+            mean_b = tot * inv_cnt;
+        } else if (tl == 0 && ok) {
+            stats[(size_t)blockIdx.x * N + n] = make_float2(mean_b, tot);
+        }
+    }
+}
+
+// Output transform of tiles of 4x4 outputs from P x P positions: y = AT M AT^T + bias with AT [4][P] (F(4x4,3x3): P = 6,
+// polyphase down: P = 9).  Block = 64 channels x 4 tile lanes, 8 tiles (2 per thread) = 128 output pixels => one
+// (mean_b, M2_b) statistics partial per block.  Mm is [P*P][Tt][N] and its first T tile rows are this map's; y [Ho][Wo][N]
+// receives act(v) (the statistics see v).  sh: the block's __shared__ float [4][64].
+template <int P, class Act>
+__device__ __forceinline__ void output_transform_4x4(const double (&AT)[4][P], const float* Mm, const float* bias, float* y,
+                                                     float2* stats, int Ho, int Wo, int N, int TW, int T, int Tt,
+                                                     float (*sh)[64], Act act) {
+    const int cl = threadIdx.x & 63, tl = threadIdx.x >> 6;
+    const int n = blockIdx.y * 64 + cl;
+    const bool ok = n < N;
+    const float bv = (ok && bias) ? bias[n] : 0.f;
+    float out[32];
+    unsigned mask = 0;
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+        const long tile = (long)blockIdx.x * 8 + tl + 4 * i;
+        const bool tv = tile < T;
+        float r[4][P];   // r[i2][b] = sum_a AT[i2][a] m[a][b]
+#pragma unroll
+        for (int b = 0; b < P; ++b) {
+            float m[P];
+#pragma unroll
+            for (int a = 0; a < P; ++a) m[a] = (ok && tv) ? Mm[((long)(a * P + b) * Tt + tile) * N + n] : 0.f;
+#pragma unroll
+            for (int i2 = 0; i2 < 4; ++i2) r[i2][b] = cdot<P>(AT[i2], m);
+        }
+        const int ty = (int)(tile / TW), tx = (int)(tile - (long)ty * TW);
+#pragma unroll
+        for (int i2 = 0; i2 < 4; ++i2)
+#pragma unroll
+            for (int j2 = 0; j2 < 4; ++j2) {
+                const float v = cdot<P>(AT[j2], r[i2]) + bv;
+                out[i * 16 + i2 * 4 + j2] = v;
+                const int oy = 4 * ty + i2, ox = 4 * tx + j2;
+                if (tv && oy < Ho && ox < Wo) {
+                    mask |= 1u << (i * 16 + i2 * 4 + j2);
+                    if (ok) y[((long)oy * Wo + ox) * N + n] = act(v);
+                }
+            }
+    }
+    block_stats_128(out, mask, sh, tl, cl, ok, stats, N, n);
+}
+
+}  // namespace t2v

@@ -20,14 +20,12 @@
 #include "t2v_internal.h"
 #include "norm_pool.h"
 #include "winograd_f4_consts.h"
+#include "transform_common.h"
 
 namespace t2v {
 
-static inline int wg_grid(long n, int block) {
-    long g = (n + block - 1) / block;
-    if (g > 4096) g = 4096;
-    return g < 1 ? 1 : (int)g;
-}
+// at most 4096 blocks: the cap decides how many tiles a thread of the grid-stride transforms walks
+static inline int wg_grid(long n, int block) { return capped_grid(n, block, 4096); }
 
 // U[xi][n][c] = (G g G^T)[xi],  G = [[1,0,0],[.5,.5,.5],[.5,-.5,.5],[0,0,1]]
 // adjoint: w is the forward layer's weight [Cin][Cout][3][3]; the tap read is w[c][n][2-a][2-b] (the data gradient's filter)
@@ -133,50 +131,12 @@ __global__ __launch_bounds__(256) void winograd_input_kernel(const float4* __res
     }
 }
 int launch_winograd_input(hipStream_t s, const float* x, float* V, int H, int W, int C, int pad, int reflect) {
-    const int Ho = H + 2 * pad - 2, Wo = W + 2 * pad - 2;
-    const int TW = (Wo + 1) / 2, T = ((Ho + 1) / 2) * TW, Tp = wino_pad_tiles(T);
-    hipLaunchKernelGGL(winograd_input_kernel, dim3(wg_grid((long)Tp * (C / 4), 256)), dim3(256), 0, s,
-                       reinterpret_cast<const float4*>(x), reinterpret_cast<float4*>(V), H, W, C / 4, TW, T, Tp, pad,
+    const TileGrid tg = tile_grid(H + 2 * pad - 2, W + 2 * pad - 2, 2);
+    hipLaunchKernelGGL(winograd_input_kernel, dim3(wg_grid((long)tg.Tp * (C / 4), 256)), dim3(256), 0, s,
+                       reinterpret_cast<const float4*>(x), reinterpret_cast<float4*>(V), H, W, C / 4, tg.TW, tg.T, tg.Tp, pad,
                        reflect);
     T2V_HIP_CHECK(hipGetLastError());
     return T2V_OK;
-}
-
-// (mean, M2) of a block's <= 128 valid output pixels per channel: each of the 4 tile lanes holds 32 pixel
-// slots, `mask` marks the ones inside the image (all of them except in ragged / padding tiles).  Two passes,
-// tree-summed (exact for constant maps over power-of-two counts), written as the partial inorm_finalize
-// merges; the partial's pixel count is recomputed there from the geometry.
-__device__ __forceinline__ void block_stats_128(const float (&val)[32], unsigned mask, float (*sh)[64], int tl, int cl,
-                                                bool ok, float2* __restrict__ stats, int N, int n) {
-    if (stats == nullptr) return;
-    sh[tl][cl] = (float)__popc(mask);
-    __syncthreads();
-    const float cnt = (sh[0][cl] + sh[1][cl]) + (sh[2][cl] + sh[3][cl]);
-    __syncthreads();
-    const float inv_cnt = cnt > 0.f ? 1.f / cnt : 0.f;
-    float mean_b = 0.f;
-#pragma unroll
-    for (int pass = 0; pass < 2; ++pass) {
-        float v[32];
-#pragma unroll
-        for (int i = 0; i < 32; ++i) {
-            const float dlt = val[i] - mean_b;
-            v[i] = ((mask >> i) & 1u) ? (pass ? dlt * dlt : val[i]) : 0.f;
-        }
-#pragma unroll
-        for (int w = 16; w >= 1; w >>= 1)
-#pragma unroll
-            for (int i = 0; i < w; ++i) v[i] += v[i + w];
-        sh[tl][cl] = v[0];
-        __syncthreads();
-        const float tot = (sh[0][cl] + sh[1][cl]) + (sh[2][cl] + sh[3][cl]);
-        __syncthreads();
-        if (pass == 0) {
-            mean_b = tot * inv_cnt;
-        } else if (tl == 0 && ok) {
-            stats[(size_t)blockIdx.x * N + n] = make_float2(mean_b, tot);
-        }
-    }
 }
 
 // y = A^T M A + bias,  A^T = [[1,1,1,0],[0,1,-1,-1]];  block = 64 channels x 4 tile lanes, 32 tiles = 128
@@ -221,9 +181,9 @@ __global__ __launch_bounds__(256) void winograd_output_kernel(const float* __res
     block_stats_128(out, mask, sh, tl, cl, ok, stats, N, n);
 }
 int launch_winograd_output(hipStream_t s, const float* Mm, const float* bias, float* y, float* stats, int H, int W, int N) {
-    const int TW = (W + 1) / 2, T = ((H + 1) / 2) * TW, Tp = wino_pad_tiles(T);
-    hipLaunchKernelGGL(winograd_output_kernel, dim3(Tp / 32, (N + 63) / 64), dim3(256), 0, s, Mm, bias, y,
-                       reinterpret_cast<float2*>(stats), H, W, N, TW, T, Tp);
+    const TileGrid tg = tile_grid(H, W, 2);
+    hipLaunchKernelGGL(winograd_output_kernel, dim3(tg.Tp / 32, (N + 63) / 64), dim3(256), 0, s, Mm, bias, y,
+                       reinterpret_cast<float2*>(stats), H, W, N, tg.TW, tg.T, tg.Tp);
     T2V_HIP_CHECK(hipGetLastError());
     return T2V_OK;
 }
@@ -234,21 +194,6 @@ int launch_winograd_output(hipStream_t s, const float* Mm, const float* bias, fl
 // {0, +-1, +-2} cost ~2x the fp32 rounding error).  V / M shrink to 36/16 = 2.25x the activation (F(2x2): 4x),
 // so the memory-bound transforms get cheaper as well.  Same layouts: U [36][Cout_p][Cin_s], V [36][Tp][C],
 // M [36][Tp][N], T = ceil(H/4) * ceil(W/4) tiles padded to Tp (multiple of 128).
-template <int K>
-__device__ __forceinline__ float cdot(const double (&row)[K], const float (&v)[K]) {
-    float acc = 0.f;
-    bool first = true;
-#pragma unroll
-    for (int k = 0; k < K; ++k) {
-        if (row[k] != 0.0) {   // compile-time after unrolling: x * 0 is not foldable under IEEE rules
-            const float t = (float)row[k] * v[k];
-            acc = first ? t : acc + t;
-            first = false;
-        }
-    }
-    return acc;
-}
-
 __device__ __forceinline__ void winograd4_weight_store(const double (&g)[3][3], float* __restrict__ U, size_t at,
                                                         size_t pos_stride) {
     double t[6][3];
@@ -323,8 +268,8 @@ int launch_winograd4_weight(hipStream_t s, const float* w, float* U, int Cout, i
 // Tt / t0: V is [36][Tt][C] and this image's tiles start at row t0 (a batch of images shares one matrix)
 //
 // MODE 1 / 2: x is a conv output that has not been normalised yet.  The transform applies the consumer side of the
-// norm layer on the fly -- d = [relu]((x - mean) * rstd [* gamma + beta]) [+ res], the arithmetic of
-// inorm_apply_kernel in the same order, so the result is bit-identical to apply-then-transform.  MODE 1: with ReLU
+// norm layer on the fly -- d = [relu]((x - mean) * rstd [* gamma + beta]) [+ res], by norm_apply (transform_common.h), the
+// function inorm_apply_kernel calls, so the result is bit-identical to apply-then-transform.  MODE 1: with ReLU
 // (a ResnetBlock's first norm).  MODE 2: plus the residual, and the tile's own 4x4 pixels of d are written to `xout`
 // as well (every pixel belongs to exactly one tile): a ResnetBlock's output, which the next block needs again as
 // its residual.  All pointers are distinct buffers (restrict: the side stores must not fence the patch loads).
@@ -398,16 +343,8 @@ __global__ __launch_bounds__(256) void winograd4_input_kernel(const float2* __re
             for (int b = 0; b < 6; ++b) {
                 float2 v = d[b];
                 if (MODE && oky[a] && okx[b]) {
-                    v.x = (v.x - mr0.x) * mr0.y;
-                    v.y = (v.y - mr1.x) * mr1.y;
-                    if (gamma) {
-                        v.x = v.x * gm.x + bt.x;
-                        v.y = v.y * gm.y + bt.y;
-                    }
-                    if (MODE == 1) {
-                        v.x = fmaxf(v.x, 0.f);
-                        v.y = fmaxf(v.y, 0.f);
-                    }
+                    v.x = norm_apply(v.x, mr0.x, mr0.y, gamma != nullptr, gm.x, bt.x, MODE == 1);
+                    v.y = norm_apply(v.y, mr1.x, mr1.y, gamma != nullptr, gm.y, bt.y, MODE == 1);
                     if (MODE == 2) {
                         v.x += r[b].x;
                         v.y += r[b].y;
@@ -466,42 +403,35 @@ static inline unsigned xcd_slice_grid(long tiles, int C2) {
 // Slot layout (the weight gradient's batch workspace): the image at `x` goes to slot `image` of a V sized for `batch`
 // slots of Tp rows.  Packed layout (nimg > 0: a forward batch): the nimg images starting at `x` (img_stride floats apart)
 // own T rows each, the total padded to wino_pad_tiles(nimg * T).
+// lazy (packed layout only): x still has to go through its norm layer -- relu 1 = [ReLU](norm(x)); relu 0 = norm(x) + res
+// with the result also written to xout (both required)
 int launch_winograd4_input(hipStream_t s, const float* x, float* V, int H, int W, int C, int pad, int reflect, int batch,
-                           int image, int nimg, long img_stride) {
-    const int Ho = H + 2 * pad - 2, Wo = W + 2 * pad - 2;
-    const int TW = (Wo + 3) / 4, T = ((Ho + 3) / 4) * TW, Tp = wino_pad_tiles(T);
+                           int image, int nimg, long img_stride, const LazyNorm* lazy) {
+    const LazyNorm none{};
+    const LazyNorm& ln = lazy ? *lazy : none;
+    const int mode = !lazy ? 0 : ln.relu ? 1 : 2;
+    if (lazy) {
+        T2V_REQUIRE(nimg > 0, "winograd4_input_lazy: packed layout only");
+        T2V_REQUIRE(ln.mean_rstd && (ln.gamma == nullptr) == (ln.beta == nullptr), "winograd4_input_lazy: bad norm arguments");
+        T2V_REQUIRE(ln.relu ? (!ln.res && !ln.xout) : (ln.res && ln.xout), "winograd4_input_lazy: residual and side output go together");
+        // with another padding a tile's own 4x4 block would not tile the input map
+        T2V_REQUIRE(ln.relu || pad == 1, "winograd4_input_lazy: the side output needs pad == 1");
+    }
+    const TileGrid tg = tile_grid(H + 2 * pad - 2, W + 2 * pad - 2, 4);
+    const int T = tg.T, Tp = tg.Tp;
     const bool packed = nimg > 0;
     const int n = packed ? nimg : 1;
     const int Tt = packed ? wino_pad_tiles(n * T) : batch * Tp;
     const int img_tiles = packed ? T : Tp, last_tiles = packed ? Tt - (n - 1) * T : Tp, t0 = packed ? 0 : image * Tp;
-    const long most = last_tiles > img_tiles ? last_tiles : img_tiles;
+    const long most = last_tiles > img_tiles ? last_tiles : img_tiles;   // (packed: the image with the padding rows walks the most)
     const unsigned xg = xcd_slice_grid(most, C / 2);
-    auto kern = xg ? winograd4_input_kernel<0, true> : winograd4_input_kernel<0, false>;
-    hipLaunchKernelGGL(kern, dim3(xg ? xg : wg_grid(most * (C / 2), 256), n),
-                       dim3(256), 0, s, reinterpret_cast<const float2*>(x), reinterpret_cast<float2*>(V), H, W, C / 2, TW, T,
-                       img_tiles, pad, reflect, Tt, t0, nullptr, nullptr, nullptr, nullptr, nullptr, img_stride / 2, last_tiles);
-    T2V_HIP_CHECK(hipGetLastError());
-    return T2V_OK;
-}
-// relu_only: 1 = [ReLU](norm(x)); 0 = norm(x) + res with the result also written to xout (both required)
-int launch_winograd4_input_lazy(hipStream_t s, const float* x, float* V, int H, int W, int C, int pad, int reflect,
-                                const float* mean_rstd, const float* gamma, const float* beta, int relu_only,
-                                const float* res, float* xout, int nimg, long img_stride) {
-    T2V_REQUIRE(mean_rstd && (gamma == nullptr) == (beta == nullptr), "winograd4_input_lazy: bad norm arguments");
-    T2V_REQUIRE(relu_only ? (!res && !xout) : (res && xout), "winograd4_input_lazy: residual and side output go together");
-    // with another padding a tile's own 4x4 block would not tile the input map
-    T2V_REQUIRE(relu_only || pad == 1, "winograd4_input_lazy: the side output needs pad == 1");
-    const int Ho = H + 2 * pad - 2, Wo = W + 2 * pad - 2;
-    const int TW = (Wo + 3) / 4, T = ((Ho + 3) / 4) * TW;
-    const int Tt = wino_pad_tiles(nimg * T), last_tiles = Tt - (nimg - 1) * T;      // packed layout
-    const unsigned xg = xcd_slice_grid(last_tiles, C / 2);      // (last_tiles >= T: the image with the padding rows walks the most)
-    auto kern = xg ? (relu_only ? winograd4_input_kernel<1, true> : winograd4_input_kernel<2, true>)
-                   : (relu_only ? winograd4_input_kernel<1, false> : winograd4_input_kernel<2, false>);
-    hipLaunchKernelGGL(kern, dim3(xg ? xg : wg_grid((long)last_tiles * (C / 2), 256), nimg), dim3(256), 0, s,
-                       reinterpret_cast<const float2*>(x), reinterpret_cast<float2*>(V), H, W, C / 2, TW, T, T, pad, reflect, Tt, 0,
-                       reinterpret_cast<const float2*>(mean_rstd), reinterpret_cast<const float2*>(gamma),
-                       reinterpret_cast<const float2*>(beta), reinterpret_cast<const float2*>(res),
-                       reinterpret_cast<float2*>(xout), img_stride / 2, last_tiles);
+    auto kern = xg ? (mode == 0 ? winograd4_input_kernel<0, true> : mode == 1 ? winograd4_input_kernel<1, true> : winograd4_input_kernel<2, true>)
+                   : (mode == 0 ? winograd4_input_kernel<0, false> : mode == 1 ? winograd4_input_kernel<1, false> : winograd4_input_kernel<2, false>);
+    hipLaunchKernelGGL(kern, dim3(xg ? xg : wg_grid(most * (C / 2), 256), n), dim3(256), 0, s,
+                       reinterpret_cast<const float2*>(x), reinterpret_cast<float2*>(V), H, W, C / 2, tg.TW, T, img_tiles, pad,
+                       reflect, Tt, t0, reinterpret_cast<const float2*>(ln.mean_rstd), reinterpret_cast<const float2*>(ln.gamma),
+                       reinterpret_cast<const float2*>(ln.beta), reinterpret_cast<const float2*>(ln.res),
+                       reinterpret_cast<float2*>(ln.xout), img_stride / 2, last_tiles);
     T2V_HIP_CHECK(hipGetLastError());
     return T2V_OK;
 }
@@ -520,49 +450,17 @@ __global__ __launch_bounds__(256) void winograd4_output_kernel(const float* __re
         y += im * H * W * N;
         if (stats) stats += im * (Tp / 8) * N;
     }
-    const int cl = threadIdx.x & 63, tl = threadIdx.x >> 6;
-    const int n = blockIdx.y * 64 + cl;
-    const bool ok = n < N;
-    const float bv = (ok && bias) ? bias[n] : 0.f;
-    float out[32];
-    unsigned mask = 0;
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-        const long tile = (long)blockIdx.x * 8 + tl + 4 * i;
-        const bool tv = tile < T;
-        float r[4][6];   // r[i2][b] = sum_a A^T[i2][a] m[a][b]
-#pragma unroll
-        for (int b = 0; b < 6; ++b) {
-            float m[6];
-#pragma unroll
-            for (int a = 0; a < 6; ++a) m[a] = (ok && tv) ? Mm[((long)(a * 6 + b) * Tt + tile) * N + n] : 0.f;
-#pragma unroll
-            for (int i2 = 0; i2 < 4; ++i2) r[i2][b] = cdot<6>(f4::kAT[i2], m);
-        }
-        const int ty = (int)(tile / TW), tx = (int)(tile - (long)ty * TW);
-#pragma unroll
-        for (int i2 = 0; i2 < 4; ++i2)
-#pragma unroll
-            for (int j2 = 0; j2 < 4; ++j2) {
-                const float v = cdot<6>(f4::kAT[j2], r[i2]) + bv;
-                out[i * 16 + i2 * 4 + j2] = v;
-                const int oy = 4 * ty + i2, ox = 4 * tx + j2;
-                if (tv && oy < H && ox < W) {
-                    mask |= 1u << (i * 16 + i2 * 4 + j2);
-                    // (Leaky)ReLU of layers without a norm (the VGG19 loss network); never together with statistics
-                    if (ok) y[((long)oy * W + ox) * N + n] = (lrelu && v < 0.f) ? v * slope : v;
-                }
-            }
-    }
-    block_stats_128(out, mask, sh, tl, cl, ok, stats, N, n);
+    // (Leaky)ReLU of layers without a norm (the VGG19 loss network); never together with statistics
+    output_transform_4x4<6>(f4::kAT, Mm, bias, y, stats, H, W, N, TW, T, Tt, sh,
+                            [=](float v) { return (lrelu && v < 0.f) ? v * slope : v; });
 }
 // nimg images: M is [36][nimg*T padded][N]; y and stats hold the images back to back
 int launch_winograd4_output(hipStream_t s, const float* Mm, const float* bias, float* y, float* stats, int H, int W, int N,
                             int lrelu, float slope, int nimg) {
-    const int TW = (W + 3) / 4, T = ((H + 3) / 4) * TW, Tp = wino_pad_tiles(T);
-    const dim3 grid(Tp / 8, (N + 63) / 64, nimg);
+    const TileGrid tg = tile_grid(H, W, 4);
+    const dim3 grid(tg.Tp / 8, (N + 63) / 64, nimg);
     hipLaunchKernelGGL(winograd4_output_kernel, grid, dim3(256), 0, s, Mm, bias, y, reinterpret_cast<float2*>(stats), H, W, N,
-                       TW, T, Tp, lrelu, slope, wino_pad_tiles(nimg * T));
+                       tg.TW, tg.T, tg.Tp, lrelu, slope, wino_pad_tiles(nimg * tg.T));
     T2V_HIP_CHECK(hipGetLastError());
     return T2V_OK;
 }
@@ -575,19 +473,11 @@ int launch_winograd4_output(hipStream_t s, const float* Mm, const float* bias, f
 // the PADDED input, dxp [(H+2)][(W+2)][C] (the reflect-pad adjoint folds it afterwards).  One thread = one 4x4 block of padded
 // pixels x 2 channels: it gathers its 16 values from the (up to) four patches that cover them, each patch element computed
 // exactly once chip-wide, contributions added in a fixed order (own tile, left, top, top-left).  H % 4 == 0 == W % 4.
-struct F4B {   // B = (B^T)^T as a constexpr table: row i = the coefficients of patch row / column i
-    double m[6][6];
-    constexpr F4B() : m{} {
-        for (int r = 0; r < 6; ++r)
-            for (int c = 0; c < 6; ++c) m[c][r] = f4::kBT[r][c];
-    }
-};
-constexpr F4B kF4B{};
-
 template <int DY, int DX>   // source tile = (by - DY, bx - DX); it contributes its patch rows 4*DY.., columns 4*DX..
 __device__ __forceinline__ void dgrad_gather_tile(const float2* __restrict__ dV, long tile, int Tp, int C2, int c2,
                                                   float (&ox)[4][4], float (&oy)[4][4]) {
     constexpr int NR = DY ? 2 : 4, NS = DX ? 2 : 4;
+    // (B = (B^T)^T: patch row / column i takes column i of kBT)
     float tx[6][NS], ty[6][NS];      // stage 1: columns of the patch, per transform row a2
 #pragma unroll
     for (int a2 = 0; a2 < 6; ++a2) {
@@ -600,8 +490,8 @@ __device__ __forceinline__ void dgrad_gather_tile(const float2* __restrict__ dV,
         }
 #pragma unroll
         for (int sidx = 0; sidx < NS; ++sidx) {
-            tx[a2][sidx] = cdot<6>(kF4B.m[4 * DX + sidx], vx);
-            ty[a2][sidx] = cdot<6>(kF4B.m[4 * DX + sidx], vy);
+            tx[a2][sidx] = cdot_col(f4::kBT, 4 * DX + sidx, vx);
+            ty[a2][sidx] = cdot_col(f4::kBT, 4 * DX + sidx, vy);
         }
     }
 #pragma unroll
@@ -614,8 +504,8 @@ __device__ __forceinline__ void dgrad_gather_tile(const float2* __restrict__ dV,
         }
 #pragma unroll
         for (int r = 0; r < NR; ++r) {
-            ox[r][sidx] += cdot<6>(kF4B.m[4 * DY + r], cx);
-            oy[r][sidx] += cdot<6>(kF4B.m[4 * DY + r], cy);
+            ox[r][sidx] += cdot_col(f4::kBT, 4 * DY + r, cx);
+            oy[r][sidx] += cdot_col(f4::kBT, 4 * DY + r, cy);
         }
     }
 }
@@ -671,7 +561,7 @@ __global__ __launch_bounds__(256) void winograd4_dgrad_output_kernel(const float
 // dV [36][Tp][C] of an H x W map (H, W multiples of 4, pad 1) -> dxp [(H+2)][(W+2)][C]
 int launch_winograd4_dgrad_output(hipStream_t s, const float* dV, float* dxp, int H, int W, int C) {
     T2V_REQUIRE(H % 4 == 0 && W % 4 == 0 && C % 2 == 0, "winograd4_dgrad_output: H, W must be multiples of 4");
-    const int TH = H / 4, TW = W / 4, Tp = wino_pad_tiles(TH * TW), C2 = C / 2;
+    const int TH = H / 4, TW = W / 4, Tp = tile_grid(H, W, 4).Tp, C2 = C / 2;
     const long per_xcd = ((long)(C2 >> 9) * (TH + 1) * (TW + 1) + 3) / 4;
     if (C2 % 512 == 0 && options().xcd_slices && per_xcd * 8 <= 0x7fffffffL)
         hipLaunchKernelGGL(winograd4_dgrad_output_kernel<true>, dim3((unsigned)(per_xcd * 8)), dim3(256), 0, s,
@@ -692,8 +582,8 @@ int launch_winograd4_dgrad_output(hipStream_t s, const float* dV, float* dxp, in
 // on conv_wgrad_kernel unchanged (the transform position plays the role of the tap: row xi of a [36][T] "image").
 // winograd4_dy_kernel: Mdy[a*6+b][t0+tile][n] = (A dy A^T)[a][b], dy tile 4x4 (zero outside the map)
 // NORM: `dy` is the gradient behind the layer's norm (+ activation) and `nb.x` the conv's raw output: the gradient in front of
-// the norm -- rstd * gamma * (g - S0/N - xhat * S1/N), g = dy * act'(gamma * xhat + beta): the arithmetic of
-// inorm_bwd_apply_kernel (elementwise.hip) in the same order, the same bits -- is formed per loaded element and never
+// the norm -- rstd * gamma * (g - S0/N - xhat * S1/N), g = dy * act'(gamma * xhat + beta): norm_bwd_terms / norm_bwd_dx
+// (transform_common.h), the functions inorm_bwd_apply_kernel calls, so the same bits -- is formed per loaded element and never
 // written out (nothing else reads it where the data gradient takes A dy A^T from this workspace)
 struct DyNormBackward {
     const float2* x;           // the conv's raw output [Ho][Wo][cs2]
@@ -728,11 +618,8 @@ __global__ __launch_bounds__(256) void winograd4_dy_kernel(const float2* __restr
                 k1[k] = sm.y * nb.invn;
             }
         }
-        auto front = [&](float xv, float gv, int k) {     // (inorm_bwd_apply_kernel's `one`)
-            const float xh = (xv - mean[k]) * rstd[k];
-            const float pre = ga[k] * xh + be[k];
-            const float g = gv * (nb.relu == 1 ? (pre > 0.f ? 1.f : 0.f) : (nb.relu == 2 ? (pre > 0.f ? 1.f : 0.2f) : 1.f));
-            return rstd[k] * ga[k] * (g - k0[k] - xh * k1[k]);
+        auto front = [&](float xv, float gv, int k) {
+            return norm_bwd_dx(norm_bwd_terms(xv, gv, mean[k], rstd[k], ga[k], be[k], nb.relu), rstd[k], ga[k], k0[k], k1[k]);
         };
         if (tile >= T) {
 #pragma unroll
@@ -741,10 +628,10 @@ __global__ __launch_bounds__(256) void winograd4_dy_kernel(const float2* __restr
         }
         const int ty = (int)(tile / TW), tx = (int)(tile - (long)ty * TW);
         // rows first: r[i][b] = sum_j dy[i][j] A^T[j][b]
-        float rx[4][6], ry[4][6];
+        float2 r[4][6];
 #pragma unroll
         for (int i2 = 0; i2 < 4; ++i2) {
-            float vx[4], vy[4];
+            float2 v[4];
 #pragma unroll
             for (int j2 = 0; j2 < 4; ++j2) {
                 const int oy = 4 * ty + i2, ox = 4 * tx + j2;
@@ -755,49 +642,27 @@ __global__ __launch_bounds__(256) void winograd4_dy_kernel(const float2* __restr
                         d = make_float2(front(xv.x, d.x, 0), front(xv.y, d.y, 1));
                     }
                 }
-                vx[j2] = d.x;
-                vy[j2] = d.y;
+                v[j2] = d;
             }
 #pragma unroll
-            for (int b = 0; b < 6; ++b) {
-                float ax = 0.f, ay = 0.f;
-                bool first = true;
-#pragma unroll
-                for (int j2 = 0; j2 < 4; ++j2)
-                    if (f4::kAT[j2][b] != 0.0) {
-                        const float tx_ = (float)f4::kAT[j2][b] * vx[j2], ty_ = (float)f4::kAT[j2][b] * vy[j2];
-                        ax = first ? tx_ : ax + tx_;
-                        ay = first ? ty_ : ay + ty_;
-                        first = false;
-                    }
-                rx[i2][b] = ax;
-                ry[i2][b] = ay;
-            }
+            for (int b = 0; b < 6; ++b) r[i2][b] = cdot_col(f4::kAT, b, v);
         }
         // columns: m[a][b] = sum_i A^T[i][a] r[i][b]
 #pragma unroll
-        for (int b = 0; b < 6; ++b)
+        for (int b = 0; b < 6; ++b) {
+            float2 c[4];
 #pragma unroll
-            for (int a = 0; a < 6; ++a) {
-                float ax = 0.f, ay = 0.f;
-                bool first = true;
+            for (int i2 = 0; i2 < 4; ++i2) c[i2] = r[i2][b];
 #pragma unroll
-                for (int i2 = 0; i2 < 4; ++i2)
-                    if (f4::kAT[i2][a] != 0.0) {
-                        const float tx_ = (float)f4::kAT[i2][a] * rx[i2][b], ty_ = (float)f4::kAT[i2][a] * ry[i2][b];
-                        ax = first ? tx_ : ax + tx_;
-                        ay = first ? ty_ : ay + ty_;
-                        first = false;
-                    }
-                Md[((long)(a * 6 + b) * Tt + t0 + tile) * C2 + c2] = make_float2(ax, ay);
-            }
+            for (int a = 0; a < 6; ++a) Md[((long)(a * 6 + b) * Tt + t0 + tile) * C2 + c2] = cdot_col(f4::kAT, a, c);
+        }
     }
 }
 int launch_winograd4_dy(hipStream_t s, const float* dy, float* Md, int Ho, int Wo, int N, int dy_cs, int batch, int image) {
-    const int TW = (Wo + 3) / 4, T = ((Ho + 3) / 4) * TW, Tp = wino_pad_tiles(T);
-    hipLaunchKernelGGL(winograd4_dy_kernel<false>, dim3(wg_grid((long)Tp * (N / 2), 256)), dim3(256), 0, s,
-                       reinterpret_cast<const float2*>(dy), reinterpret_cast<float2*>(Md), Ho, Wo, N / 2, dy_cs / 2, TW, T, Tp,
-                       batch * Tp, image * Tp, DyNormBackward{});
+    const TileGrid tg = tile_grid(Ho, Wo, 4);
+    hipLaunchKernelGGL(winograd4_dy_kernel<false>, dim3(wg_grid((long)tg.Tp * (N / 2), 256)), dim3(256), 0, s,
+                       reinterpret_cast<const float2*>(dy), reinterpret_cast<float2*>(Md), Ho, Wo, N / 2, dy_cs / 2, tg.TW, tg.T,
+                       tg.Tp, batch * tg.Tp, image * tg.Tp, DyNormBackward{});
     T2V_HIP_CHECK(hipGetLastError());
     return T2V_OK;
 }
@@ -805,7 +670,7 @@ int launch_winograd4_dy(hipStream_t s, const float* dy, float* Md, int Ho, int W
 int launch_winograd4_dy_norm(hipStream_t s, const float* dy, const float* x, const float* mean_rstd, const float* gamma,
                              const float* beta, int relu, const float* sums, float* Md, int Ho, int Wo, int N, int batch,
                              int image) {
-    const int TW = (Wo + 3) / 4, T = ((Ho + 3) / 4) * TW, Tp = wino_pad_tiles(T);
+    const TileGrid tg = tile_grid(Ho, Wo, 4);
     DyNormBackward nb;
     nb.x = reinterpret_cast<const float2*>(x);
     nb.mean_rstd = reinterpret_cast<const float2*>(mean_rstd);
@@ -814,9 +679,9 @@ int launch_winograd4_dy_norm(hipStream_t s, const float* dy, const float* x, con
     nb.sums = reinterpret_cast<const float2*>(sums);
     nb.invn = 1.f / (float)((long)Ho * Wo);
     nb.relu = relu;
-    hipLaunchKernelGGL(winograd4_dy_kernel<true>, dim3(wg_grid((long)Tp * (N / 2), 256)), dim3(256), 0, s,
-                       reinterpret_cast<const float2*>(dy), reinterpret_cast<float2*>(Md), Ho, Wo, N / 2, N / 2, TW, T, Tp,
-                       batch * Tp, image * Tp, nb);
+    hipLaunchKernelGGL(winograd4_dy_kernel<true>, dim3(wg_grid((long)tg.Tp * (N / 2), 256)), dim3(256), 0, s,
+                       reinterpret_cast<const float2*>(dy), reinterpret_cast<float2*>(Md), Ho, Wo, N / 2, N / 2, tg.TW, tg.T, tg.Tp,
+                       batch * tg.Tp, image * tg.Tp, nb);
     T2V_HIP_CHECK(hipGetLastError());
     return T2V_OK;
 }
