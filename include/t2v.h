@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define T2V_ABI_VERSION 18
+#define T2V_ABI_VERSION 19
 
 typedef enum {
     T2V_OK = 0,
@@ -143,6 +143,16 @@ int t2v_conv2d_forward(t2v_ctx* ctx, void* stream, const t2v_conv_desc* d, const
  * images share a launch because the discriminators' layers of the train step fill a fraction of the chip each.) */
 int t2v_conv2d_forward_batch(t2v_ctx* ctx, void* stream, const t2v_conv_desc* d, int batch, const float* x, int x_cs,
                              const float* w_packed, const float* bias, float* y, int y_cs, float* stats_partial);
+/* A 7x7 generator head on the RAW output of the conv before it (ABI 19): x has not gone through its norm layer yet, and the
+ * head's halo-tile kernel applies [relu]((x - mean) * rstd [* gamma + beta]) to every halo plane it stages, with the
+ * arithmetic of t2v_instance_norm_apply -- y carries the bits of t2v_instance_norm_apply followed by t2v_conv2d_forward, without
+ * the pass over the map in between (what t2v_generator_forward* does with the last decoder layer's output unless
+ * T2V_CHAIN_LAZY=0).  d: 7x7, stride 1, ReflectionPad 3, Cout <= 3, x_cs % 16 == 0, H, W >= 4 (the shapes the halo-tile kernel
+ * takes; anything else is T2V_ERR_INVALID); mean_rstd [x_cs][2] as t2v_*_norm_finalize writes it; gamma, beta both or neither;
+ * relu must be 1 (the norm in front of a head is always followed by its ReLU). */
+int t2v_conv2d_forward_head_norm(t2v_ctx* ctx, void* stream, const t2v_conv_desc* d, const float* x, int x_cs,
+                                 const float* w_packed, const float* bias, float* y, int y_cs, const float* mean_rstd,
+                                 const float* gamma, const float* beta, int relu);
 
 /* Bit mask of the Winograd variants `d` (algo ignored) can run as: 1 = F(2x2,3x3), 2 = F(4x4,3x3).
  * Needs 3x3, stride 1, ReflectionPad 1 or zero padding 0..2 (pad 2: the data gradient of the pad-1 conv),

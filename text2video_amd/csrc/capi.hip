@@ -388,6 +388,27 @@ static int run_position_gemm(t2v_ctx* ctx, hipStream_t s, const PositionGemm& g,
     return launch_wino_gemm_sk(s, k);
 }
 
+bool conv_plan_is_head7x7(const ConvPlan& pl) {
+    const ConvKParams& q = pl.kp;
+    return q.nphases == 1 && q.ph[0].ntaps == 49 && q.KW == 7 && q.pad == 3 && q.stride == 1 && q.pad_mode == T2V_PAD_REFLECT &&
+           q.Cout <= 3 && q.Cin_s % 16 == 0 && q.Hin >= 4 && q.Win >= 4;
+}
+int run_head7x7(hipStream_t s, const ConvPlan& pl, const float* x, const float* w, const float* bias, float* y, int y_cs,
+                const LazyNorm* lazy) {
+    const ConvKParams& q = pl.kp;
+    T2V_REQUIRE(conv_plan_is_head7x7(pl), "head7x7: not a 7x7 reflect-padded conv with <= 3 output channels");
+    T2V_REQUIRE(!lazy || (lazy->mean_rstd && (lazy->gamma == nullptr) == (lazy->beta == nullptr) && !lazy->res && !lazy->xout),
+                "head7x7: a pending norm is (mean, rstd), gamma and beta or neither, no residual");
+    HeadParams h;
+    h.x = x; h.w = w; h.bias = bias; h.y = y;
+    h.H = q.Hin; h.W = q.Win; h.Cin_s = q.Cin_s; h.Kp = q.ph[0].Kp; h.Cout = q.Cout; h.Cout_s = y_cs;
+    h.act = q.act; h.act_scale = q.act_scale;
+    if (lazy) {
+        h.mean_rstd = lazy->mean_rstd; h.gamma = lazy->gamma; h.beta = lazy->beta; h.relu = lazy->relu;
+    }
+    return launch_conv_head7x7(s, h);
+}
+
 // `batch` images in one go (image b at x + b * x_stride, y + b * y_stride, statistics at stats + b * stats_stride, floats):
 // the implicit-GEMM kernel takes them as blockIdx.y of ONE launch -- the discriminators' layers of the train step are 67-552
 // blocks per image, a fraction of the 1024+ block slots of the chip; the dedicated stem / head / one-channel kernels are
@@ -399,20 +420,9 @@ int run_conv_batch(t2v_ctx* ctx, hipStream_t s, const ConvPlan& pl, int batch, c
     T2V_REQUIRE(y_cs >= pl.kp.Cout && y_cs <= pl.Cout_p, "conv: output channel storage %d out of range [%d,%d]", y_cs,
                 pl.kp.Cout, pl.Cout_p);
     T2V_REQUIRE((long)pl.Hout * pl.Wout * y_cs * 4 < 0x7fff0000L, "conv: output tensor too large for 32-bit buffer offsets");
-    {
-        // the generator heads: dedicated halo-tile kernel (conv_head.hip)
-        const ConvKParams& q = pl.kp;
-        if (!stats && q.nphases == 1 && q.ph[0].ntaps == 49 && q.KW == 7 && q.pad == 3 && q.stride == 1 &&
-            q.pad_mode == T2V_PAD_REFLECT && q.Cout <= 3 && q.Cin_s % 16 == 0 && q.Hin >= 4 && q.Win >= 4) {
-            for (int b = 0; b < batch; ++b) {
-                HeadParams h;
-                h.x = x + b * x_stride; h.w = w; h.bias = bias; h.y = y + b * y_stride;
-                h.H = q.Hin; h.W = q.Win; h.Cin_s = q.Cin_s; h.Kp = q.ph[0].Kp; h.Cout = q.Cout; h.Cout_s = y_cs;
-                h.act = q.act; h.act_scale = q.act_scale;
-                T2V_TRY(launch_conv_head7x7(s, h));
-            }
-            return T2V_OK;
-        }
+    if (!stats && conv_plan_is_head7x7(pl)) {      // the generator heads: dedicated halo-tile kernel (conv_head.hip)
+        for (int b = 0; b < batch; ++b) T2V_TRY(run_head7x7(s, pl, x + b * x_stride, w, bias, y + b * y_stride, y_cs, nullptr));
+        return T2V_OK;
     }
     {
         // one output channel, long K (the discriminators' last layer): a wave per output pixel (conv_head.hip)
@@ -475,6 +485,7 @@ int winograd_forward(t2v_ctx* ctx, hipStream_t s, const t2v_conv_desc* d, const 
     const bool keep = wb.keep_v != nullptr;
     T2V_REQUIRE(!keep || (f4 && nimg == 1 && wb.keep_slot >= 0 && wb.keep_slot < wb.keep_total),
                 "winograd: V is kept for the weight gradient of single F(4x4,3x3) images only");
+    T2V_REQUIRE(!wb.v_in || (f4 && !keep && !(stages & 1)), "winograd: a borrowed V replaces the input transform (F(4x4,3x3))");
     float* V = keep ? wb.keep_v + (size_t)wb.keep_slot * T * d->Cin : workspace;
     float* Mm = workspace + wino_pos(d->algo) * T * d->Cin;
     if (stages & 1) {
@@ -492,7 +503,7 @@ int winograd_forward(t2v_ctx* ctx, hipStream_t s, const t2v_conv_desc* d, const 
         g.T = (int)T; g.K = d->Cin; g.N = d->Cout;
         // (kept: slot keep_slot of [36][keep_total * Tp][Cin]; the positions are keep_total * Tp rows apart)
         if (keep) g.a_pitch = wb.keep_total * (int)T;
-        T2V_TRY(run_position_gemm(ctx, s, g, V, w_packed, Mm, f4 ? workspace + winograd_vm_floats(d, nimg) : nullptr));
+        T2V_TRY(run_position_gemm(ctx, s, g, wb.v_in ? wb.v_in : V, w_packed, Mm, f4 ? workspace + winograd_vm_floats(d, nimg) : nullptr));
     }
     if (stages & 4) {
         T2V_REQUIRE(d->act == T2V_ACT_NONE || !stats_partial, "winograd: an activation and norm statistics do not combine");
@@ -783,6 +794,21 @@ int t2v_conv2d_forward(t2v_ctx* ctx, void* stream, const t2v_conv_desc* d, const
     ConvPlan pl;
     T2V_TRY(build_conv_plan(d, x_cs, stats_partial != nullptr, &pl));
     return run_conv(ctx, (hipStream_t)stream, pl, x, w_packed, bias, y, y_cs, stats_partial);
+}
+
+int t2v_conv2d_forward_head_norm(t2v_ctx* ctx, void* stream, const t2v_conv_desc* d, const float* x, int x_cs,
+                                 const float* w_packed, const float* bias, float* y, int y_cs, const float* mean_rstd,
+                                 const float* gamma, const float* beta, int relu) {
+    T2V_REQUIRE(ctx && d && x && w_packed && y && mean_rstd, "conv2d_forward_head_norm: null pointer");
+    T2V_REQUIRE(d->algo == T2V_ALGO_DIRECT, "conv2d_forward_head_norm: direct convolutions only");
+    T2V_REQUIRE(relu == 1, "conv2d_forward_head_norm: the pending norm is norm + ReLU (relu must be 1)");
+    ConvPlan pl;
+    T2V_TRY(build_conv_plan(d, x_cs, false, &pl));
+    T2V_REQUIRE(y_cs >= pl.kp.Cout && y_cs <= pl.Cout_p, "conv2d_forward_head_norm: output channel storage %d out of range [%d,%d]",
+                y_cs, pl.kp.Cout, pl.Cout_p);
+    T2V_REQUIRE((long)pl.kp.Hin * pl.kp.Win * x_cs * 4 < 0x7fff0000L, "conv2d_forward_head_norm: input too large for 32-bit buffer offsets");
+    const LazyNorm ln{mean_rstd, gamma, beta, relu};
+    return run_head7x7((hipStream_t)stream, pl, x, w_packed, bias, y, y_cs, &ln);
 }
 
 int t2v_conv2d_forward_batch(t2v_ctx* ctx, void* stream, const t2v_conv_desc* d, int batch, const float* x, int x_cs,

@@ -11,6 +11,7 @@
 #include <stdlib.h>
 
 #include "t2v_internal.h"
+#include "transform_common.h"
 
 namespace t2v {
 
@@ -101,13 +102,46 @@ __global__ __launch_bounds__(256) void conv_head7x7_strip_kernel(const HeadParam
         // row loop the compiler's allocation went to 256 VGPRs + AGPR copies, one wave per SIMD: 822 us.  Left at the top.)
         stage(c0);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // this wave's plane has landed (nobody else reads it)
+        typedef float f32x4 __attribute__((ext_vector_type(4)));
+        typedef const __attribute__((address_space(4))) f32x4* cf4;
+        if (p.mean_rstd != nullptr) {
+            // x is the raw output of the conv before: the wave takes its own plane through that layer's norm where it lies --
+            // lane l owns the 8 slots its DMA lanes wrote, 4 channels each, the channels' (mean, rstd) [gamma, beta] wave-uniform
+            // scalars -- by norm_apply (transform_common.h), the function inorm_apply_kernel calls: the taps read the bits the
+            // stand-alone pass would have stored.  A reflected pixel is a copy of an in-range one and gets the same value; the
+            // pad slots (column 22, rows >= 22) turn from 0 into norm(0), and no tap reads them: a lane reads rows ty + kh <= 21,
+            // columns 4 * sx + j <= 21.
+            const f32x4 mr0 = *(cf4)(p.mean_rstd + 2 * c0), mr1 = *(cf4)(p.mean_rstd + 2 * c0 + 4);   // (m0,r0,m1,r1) (m2,r2,m3,r3)
+            f32x4 gm = {1.f, 1.f, 1.f, 1.f}, bt = {0.f, 0.f, 0.f, 0.f};
+            auto norm_plane = [&](bool aff) {      // (a constant where it is called: no select per value; the ReLU always on)
+#pragma unroll
+                for (int i = 0; i < 8; ++i) {
+                    float4* q = reinterpret_cast<float4*>(plane + (i * 64 + lane) * 16);
+                    float4 v = *q;
+                    v.x = norm_apply(v.x, mr0.x, mr0.y, aff, gm.x, bt.x, 1);
+                    v.y = norm_apply(v.y, mr0.z, mr0.w, aff, gm.y, bt.y, 1);
+                    v.z = norm_apply(v.z, mr1.x, mr1.y, aff, gm.z, bt.z, 1);
+                    v.w = norm_apply(v.w, mr1.z, mr1.w, aff, gm.w, bt.w, 1);
+                    *q = v;
+                }
+            };
+            if (p.gamma != nullptr) {
+                gm = *(cf4)(p.gamma + c0);
+                bt = *(cf4)(p.beta + c0);
+                norm_plane(true);
+            } else {
+                norm_plane(false);
+            }
+            // the other lanes of the wave read these slots: LDS serves a wave's accesses in order, the compiler must keep it so
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        }
         // A kernel row = 10 halo reads + 21 weight loads + 168 packed FMAs, software-pipelined by hand in phases.  Scalar loads return out of order, so ANY wait on them is lgkmcnt(0) -- for the LDS reads in flight as
         // well: a phase's operands are therefore requested one phase AHEAD, before the FMAs of the previous phase, and each
         // phase ends in one wait that those FMAs (288 / 192 issue cycles, plus the other waves of the SIMD) have covered.
         // wave-uniform weights: scalar loads through the constant address space (the memory clobbers of the waits would turn
         // plain loads into per-lane vector loads; nothing writes the weights while this kernel runs)
-        typedef float f32x4 __attribute__((ext_vector_type(4)));
-        typedef const __attribute__((address_space(4))) f32x4* cf4;
         // three phases per kernel row: taps 0-2 | 3-4 | 5-6 (36 + 24 + 24 weight scalars, two phases live at a time)
         f32x4 wa[3][3], wb[2][3], wc[2][3];
         float4 xv[2][10];
@@ -223,6 +257,7 @@ __global__ __launch_bounds__(256) void conv_head7x7_strip_kernel(const HeadParam
 }
 
 int launch_conv_head7x7(hipStream_t s, const HeadParams& p) {
+    T2V_REQUIRE(!p.mean_rstd || p.relu == 1, "conv_head7x7: a pending norm is norm + ReLU (what the decoder's last layer carries)");
     constexpr int lds = 4 * kHsPlane;
     const dim3 grid(((p.W + kHdTile - 1) / kHdTile) * ((p.H + kHdTile - 1) / kHdTile));
     if (p.Cin_s == 128) hipLaunchKernelGGL(conv_head7x7_strip_kernel<128>, grid, dim3(256), lds, s, p);

@@ -69,12 +69,20 @@ struct WinoBatch {
     // Winograd-domain weight gradient's workspace -- instead of the call's own workspace, and the GEMM reads it from there
     float* keep_v = nullptr;
     int keep_total = 1, keep_slot = 0;
+    // v_in != null: the GEMM reads a V that another call made of the same input (same geometry and batch) instead of the
+    // workspace's own; `stages` then leaves the input transform out
+    const float* v_in = nullptr;
 };
 int winograd_forward(t2v_ctx* ctx, hipStream_t s, const t2v_conv_desc* d, const float* x, const float* w_packed,
                      const float* bias, float* y, float* stats_partial, float* workspace, int stages,
                      const WinoBatch* batch = nullptr);
 int run_conv(t2v_ctx* ctx, hipStream_t s, const ConvPlan& pl, const float* x, const float* w, const float* bias,
              float* y, int y_cs, float* stats);
+// the plan is one the dedicated 7x7 head kernel takes (conv_head.hip) ...
+bool conv_plan_is_head7x7(const ConvPlan& pl);
+// ... and that launch; lazy != null: x is the previous layer's raw conv output, normalised inside the kernel
+int run_head7x7(hipStream_t s, const ConvPlan& pl, const float* x, const float* w, const float* bias, float* y, int y_cs,
+                const LazyNorm* lazy);
 // `batch` images a constant stride apart in one implicit-GEMM launch (blockIdx.y); strides in floats
 int run_conv_batch(t2v_ctx* ctx, hipStream_t s, const ConvPlan& pl, int batch, const float* x, long x_stride, const float* w,
                    const float* bias, float* y, int y_cs, long y_stride, float* stats, long stats_stride);

@@ -195,14 +195,38 @@ int launch_bn_running_update(hipStream_t s, const float* mean_rstd, float* runni
     return T2V_OK;
 }
 
+// One side of the encoder join, norm(y) + res per float4 (the arithmetic of an inorm_apply pass with relu 0 and one residual)
+__device__ __forceinline__ float4 join_side(const NormJoinSide& s, long im, long n4, int C4, long i, int c4) {
+    const float4* mr = reinterpret_cast<const float4*>(s.mean_rstd) + im * 2 * C4;
+    const float4 a = mr[2 * c4], b = mr[2 * c4 + 1];
+    float4 v = reinterpret_cast<const float4*>(s.y)[im * n4 + i];
+    v.x = norm_scale(v.x, a.x, a.y);
+    v.y = norm_scale(v.y, a.z, a.w);
+    v.z = norm_scale(v.z, b.x, b.y);
+    v.w = norm_scale(v.w, b.z, b.w);
+    if (s.gamma) {
+        const float4 gm = reinterpret_cast<const float4*>(s.gamma)[c4], bt = reinterpret_cast<const float4*>(s.beta)[c4];
+        v.x = norm_affine(v.x, gm.x, bt.x);
+        v.y = norm_affine(v.y, gm.y, bt.y);
+        v.z = norm_affine(v.z, gm.z, bt.z);
+        v.w = norm_affine(v.w, gm.w, bt.w);
+    }
+    const float4 r = reinterpret_cast<const float4*>(s.res)[im * n4 + i];
+    v.x += r.x; v.y += r.y; v.z += r.z; v.w += r.w;
+    return v;
+}
+
 // y = [relu]((x-mean)*rstd*gamma+beta) + res1 + res2 ; float4 over NHWC, C % 4 == 0
+// join.y != null: ... + (norm_j(join.y) + join.res), the second sum formed by itself and added last -- the encoder join
+// d = (norm_b(yb) + rb) + (norm_a(ya) + ra) in ONE pass: what two apply passes (relu 0, one residual each) and add_kernel
+// compute, value by value through the same functions in the same order, without writing and re-reading the two sums
 __global__ __launch_bounds__(256) void inorm_apply_kernel(const float4* __restrict__ x,
                                                           const float4* __restrict__ mean_rstd,
                                                           const float4* __restrict__ gamma,
                                                           const float4* __restrict__ beta,
                                                           const float4* __restrict__ res1,
                                                           const float4* __restrict__ res2, float4* __restrict__ y,
-                                                          long n4, int C4, int relu) {
+                                                          long n4, int C4, int relu, const NormJoinSide join) {
     {   // blockIdx.y = image of a batch: maps n4 float4 apart, (mean, rstd) tables 2*C4 float4 apart
         const long im = blockIdx.y;
         x += im * n4;
@@ -246,6 +270,10 @@ __global__ __launch_bounds__(256) void inorm_apply_kernel(const float4* __restri
             const float4 r = res2[i];
             v.x += r.x; v.y += r.y; v.z += r.z; v.w += r.w;
         }
+        if (join.y) {
+            const float4 r = join_side(join, blockIdx.y, n4, C4, i, c4);
+            v.x += r.x; v.y += r.y; v.z += r.z; v.w += r.w;
+        }
         y[i] = v;
     }
 }
@@ -260,7 +288,21 @@ int launch_inorm_apply(hipStream_t s, const float* x, const float* mean_rstd, co
                        reinterpret_cast<const float4*>(x), reinterpret_cast<const float4*>(mean_rstd),
                        reinterpret_cast<const float4*>(gamma), reinterpret_cast<const float4*>(beta),
                        reinterpret_cast<const float4*>(res1), reinterpret_cast<const float4*>(res2),
-                       reinterpret_cast<float4*>(y), n4, C / 4, relu);
+                       reinterpret_cast<float4*>(y), n4, C / 4, relu, NormJoinSide{});
+    T2V_HIP_CHECK(hipGetLastError());
+    return T2V_OK;
+}
+int launch_inorm_join(hipStream_t s, const NormJoinSide& a, const NormJoinSide& b, float* y, long npix, int C, int nimg) {
+    T2V_REQUIRE(C % 4 == 0, "inorm_join: C=%d must be a multiple of 4", C);
+    T2V_REQUIRE(a.y && a.mean_rstd && a.res && b.y && b.mean_rstd && b.res && y, "inorm_join: null pointer");
+    T2V_REQUIRE((a.gamma == nullptr) == (a.beta == nullptr) && (b.gamma == nullptr) == (b.beta == nullptr),
+                "inorm_join: gamma and beta must both be given or both NULL");
+    const long n4 = npix * (C / 4);
+    hipLaunchKernelGGL(inorm_apply_kernel, dim3(grid_for(n4, 256), nimg), dim3(256), 0, s,
+                       reinterpret_cast<const float4*>(a.y), reinterpret_cast<const float4*>(a.mean_rstd),
+                       reinterpret_cast<const float4*>(a.gamma), reinterpret_cast<const float4*>(a.beta),
+                       reinterpret_cast<const float4*>(a.res), (const float4*)nullptr, reinterpret_cast<float4*>(y), n4, C / 4,
+                       0, b);
     T2V_HIP_CHECK(hipGetLastError());
     return T2V_OK;
 }

@@ -108,6 +108,7 @@ struct Buffers {
     float* bt[4];              // bottleneck temporaries (resnet chains)
     float* bt2[4];             // ... of the branch that runs on the side stream
     float* d;                  // encoder sum
+    float* vshare;             // flow frames of the global generator: the F(4x4) input transform V of d, made once for both branches
     float *dimg, *dflow;       // local generator: d + coarse features
     float *decI[8], *decF[8];  // decoder activations per level
     float *raw, *fw;
@@ -134,6 +135,16 @@ void plan_buffers(const t2v_gen_desc& g, const std::vector<LayerSpec>& layers, i
     for (int i = 0; i < 4; ++i) b.bt[i] = a.alloc(N * lvl(n));
     for (int i = 0; i < 4; ++i) b.bt2[i] = a.alloc(N * lvl(n));
     b.d = a.alloc(N * lvl(n));
+    {   // the first conv of the image branch and of the flow branch read the same map d: one V, kept until both GEMMs are done
+        // (a slot of its own: the streams' own workspaces are overwritten by the branches' next convs)
+        const bool flow_global = !g.no_flow && !g.is_local && g.n_blocks / 2 > 0;
+        b.vshare = nullptr;
+        if (flow_global) {
+            const LayerSpec& L = layers[2 * (1 + n + 2 * (g.n_blocks - g.n_blocks / 2))];      // the branches' first conv
+            if (L.cd.algo == T2V_ALGO_WINOGRAD_F4)
+                b.vshare = a.alloc((size_t)wino_pos(L.cd.algo) * wino_rows_batch(&L.cd, L.cd.algo, nimg) * L.cd.Cin);
+        }
+    }
     b.dimg = a.alloc(N * lvl(n));
     b.dflow = a.alloc(N * lvl(n));
     for (int l = 0; l < n; ++l) {
@@ -237,6 +248,7 @@ struct Runner {
             const int wm = wino_m(L.cd.algo);
             WinoBatch wb;
             T2V_TRY(winograd_forward(ctx, s, &L.cd, x, w.w, w.bias, y, stats, b.wino[sc], 7, &wb));
+            T2V_REQUIRE(!lazy_in && !lazy_out, "internal: a Winograd layer outside a chain takes and leaves applied norms");
             T2V_TRY(launch_inorm_finalize_winograd(s, stats, wm, L.cd.H, L.cd.W, Cout, g.eps, mr, 1, fin_of(im)));
             return launch_inorm_apply(s, y, mr, gam, bet, res1, res2, y, (long)M, Cout, relu);
         }
@@ -270,16 +282,49 @@ struct Runner {
         ++li;
         return T2V_OK;
     }
-    // the layer after the current one is a polyphase layer that consumes this one's output and nothing else does
-    bool next_takes_raw() const { return options().chain_lazy && specs[li + 1].cd.algo == T2V_ALGO_POLYPHASE; }
+    // the layer after the current one consumes this one's output, nothing else does, and it applies a pending norm itself:
+    // a polyphase layer (in its input transform), or a 7x7 head on the halo-tile kernel (on its halo planes in LDS)
+    bool next_takes_raw() const {
+        if (!options().chain_lazy) return false;
+        const LayerSpec& nx = specs[li + 1];
+        if (nx.cd.algo == T2V_ALGO_POLYPHASE) return true;
+        ConvPlan pl;
+        return !nx.has_norm && build_conv_plan(&nx.cd, nx.x_cs, false, &pl) == T2V_OK && conv_plan_is_head7x7(pl);
+    }
 
-    int head(const Ptrs& x, const MutPtrs& y) {
+    // x_raw: x is the last decoder layer's raw conv output, its (mean, rstd) still in mr_of(im): the head normalises it
+    int head(const Ptrs& x, const MutPtrs& y, bool x_raw) {
         const LayerSpec& L = specs[li];
         const t2v_layer& w = layers[li];
+        const t2v_layer& prev = layers[li - 1];
         ++li;
         ConvPlan pl;
         T2V_TRY(build_conv_plan(&L.cd, L.x_cs, false, &pl));
-        for (int im = 0; im < nimg; ++im) T2V_TRY(run_conv(ctx, s, pl, x.p[im], w.w, w.bias, y.p[im], 4, nullptr));
+        for (int im = 0; im < nimg; ++im) {
+            if (x_raw) {
+                const LazyNorm ln{mr_of(im), g.norm_affine ? prev.gamma : nullptr, g.norm_affine ? prev.beta : nullptr, 1};
+                T2V_TRY(run_head7x7(s, pl, x.p[im], w.w, w.bias, y.p[im], 4, &ln));
+            } else {
+                T2V_TRY(run_conv(ctx, s, pl, x.p[im], w.w, w.bias, y.p[im], 4, nullptr));
+            }
+        }
+        return T2V_OK;
+    }
+    // The feature map a caller asked for (the two-scale path's img_feat / flow_feat): a copy of the decoder output, or, where
+    // the decoder left it raw for the head, the apply pass the decoder skipped, written into the caller's buffer (the same
+    // traffic as the copy).  The layer whose norm is pending is the one before the head just run.
+    int export_feat(const float* feat, size_t stride, float* const* dst, bool raw) {
+        const LayerSpec& L = specs[li - 2];
+        const t2v_layer& w = layers[li - 2];
+        const size_t floats = (size_t)g.H * g.W * L.cd.Cout;
+        for (int im = 0; im < nimg; ++im) {
+            if (!dst[im]) continue;
+            if (raw)
+                T2V_TRY(launch_inorm_apply(s, feat + im * stride, mr_of(im), g.norm_affine ? w.gamma : nullptr,
+                                           g.norm_affine ? w.beta : nullptr, nullptr, nullptr, dst[im], (long)g.H * g.W, L.cd.Cout, 1));
+            else
+                T2V_HIP_CHECK(hipMemcpyAsync(dst[im], feat + im * stride, floats * sizeof(float), hipMemcpyDeviceToDevice, s));
+        }
         return T2V_OK;
     }
 
@@ -299,7 +344,8 @@ struct Runner {
         const float* res;
         float* xout;
     };
-    int wino4_conv_stats(const float* x, const LazyIn* lz, float* y_raw) {
+    // v_in (lz == null only): the V of x that share_v() made; the input transform is left out
+    int wino4_conv_stats(const float* x, const LazyIn* lz, float* y_raw, const float* v_in = nullptr) {
         const LayerSpec& L = specs[li];
         const t2v_layer& w = layers[li];
         ++li;
@@ -315,8 +361,9 @@ struct Runner {
         WinoBatch wb;
         wb.nimg = nimg;
         wb.img_stride_x = (long)b.bott;
+        wb.v_in = lz ? nullptr : v_in;
         // the images' partials are packed back to back by the batched output transform: nparts*Cout*2 floats each
-        T2V_TRY(winograd_forward(ctx, s, &cd, x, w.w, w.bias, y_raw, b.stats[sc], b.wino[sc], lz ? 6 : 7, &wb));
+        T2V_TRY(winograd_forward(ctx, s, &cd, x, w.w, w.bias, y_raw, b.stats[sc], b.wino[sc], (lz || v_in) ? 6 : 7, &wb));
         const size_t per_img = (size_t)(wino_tiles_padded(&cd, cd.algo) / 8) * cd.Cout * 2;
         for (int im = 0; im < nimg; ++im)
             T2V_TRY(launch_inorm_finalize_winograd(s, b.stats[sc] + im * per_img, 4, cd.H, cd.W, cd.Cout, g.eps, mr_of(im), 1,
@@ -328,12 +375,19 @@ struct Runner {
     // the residual) on the fly, and writes the block output the following block needs as ITS residual on the side.
     // Only the last norm of the chain runs as an apply pass.  Per block: 8 launches instead of 10 for the WHOLE batch, and one read + one write of the map less
     // per conv.  tmp: raw conv1 / conv2 outputs, block outputs (alternating); all hold the batch back to back.
-    int res_chain_lazy(const float* x, int count, float* tmp[4], const float** out) {
+    // pend_out != null: the last norm is left to the caller as well (the encoder join applies both encoders' in one pass);
+    // v0: V of x, made by share_v()
+    struct PendingNorm {
+        const float* y;          // raw conv output
+        const float* res;        // the block input that is added to its norm
+        const t2v_layer* norm;
+    };
+    int res_chain_lazy(const float* x, int count, float* tmp[4], const float** out, PendingNorm* pend_out, const float* v0) {
         const float* cur = x;
         const t2v_layer* pend = nullptr;   // norm layer of the conv output waiting in tmp[1]
         for (int i = 0; i < count; ++i) {
             if (i == 0) {
-                T2V_TRY(wino4_conv_stats(x, nullptr, tmp[0]));
+                T2V_TRY(wino4_conv_stats(x, nullptr, tmp[0], v0));
             } else {
                 float* xi = tmp[2 + (i & 1)];
                 const LazyIn in{pend, 0, cur, xi};
@@ -344,19 +398,34 @@ struct Runner {
             T2V_TRY(wino4_conv_stats(tmp[0], &mid, tmp[1]));
             pend = &layers[li - 1];
         }
+        *out = tmp[1];
+        if (pend_out) {
+            *pend_out = {tmp[1], cur, pend};
+            return T2V_OK;
+        }
         const LayerSpec& L = specs[li - 1];
         T2V_TRY(launch_inorm_apply(s, tmp[1], b.mean_rstd[sc], g.norm_affine ? pend->gamma : nullptr,
                                    g.norm_affine ? pend->beta : nullptr, cur, nullptr, tmp[1], (long)L.cd.H * L.cd.W,
                                    L.cd.Cout, 0, nimg));
-        *out = tmp[1];
         return T2V_OK;
     }
 
     // chain of `count` resblocks starting from x (never written; the batch back to back, `bott` floats apart); result
     // pointer in *out.  tmp: 4 distinct buffers != x.
-    int res_chain(const float* x, int count, float* tmp[4], const float** out) {
-        if (options().chain_lazy && count > 0 && specs[li].cd.algo == T2V_ALGO_WINOGRAD_F4 && b.mr_stride == (size_t)2 * specs[li].cd.Cout)
-            return res_chain_lazy(x, count, tmp, out);
+    // a chain of `count` blocks starting at layer l takes the lazy form
+    bool chain_is_lazy(int l, int count) const {
+        return options().chain_lazy && count > 0 && specs[l].cd.algo == T2V_ALGO_WINOGRAD_F4 && b.mr_stride == (size_t)2 * specs[l].cd.Cout;
+    }
+    // V of the map the chain at layer l starts from (the batch back to back), into the shared slot
+    int share_v(int l, const float* x) {
+        const t2v_conv_desc& cd = specs[l].cd;
+        return launch_winograd4_input(s, x, b.vshare, cd.H, cd.W, cd.Cin, cd.pad, cd.pad_mode == T2V_PAD_REFLECT, nimg, 0, nimg,
+                                      (long)b.bott);
+    }
+    int res_chain(const float* x, int count, float* tmp[4], const float** out, PendingNorm* pend_out = nullptr,
+                  const float* v0 = nullptr) {
+        if (chain_is_lazy(li, count)) return res_chain_lazy(x, count, tmp, out, pend_out, v0);
+        T2V_REQUIRE(!pend_out && !v0, "internal: only the lazy chain leaves its last norm pending / borrows a V");
         const float* cur = x;
         for (int i = 0; i < count; ++i) {
             float* t = tmp[0];
@@ -369,7 +438,7 @@ struct Runner {
     }
 
     // c7,N,R, (d,N,R) x n, RB x nb
-    int encoder(const Ptrs& x, float** act, int nb, float* tmp[4], const float** out) {
+    int encoder(const Ptrs& x, float** act, int nb, float* tmp[4], const float** out, PendingNorm* pend_out) {
         const int n = g.is_local ? 1 : g.n_downsample;
         bool raw = n > 0 && next_takes_raw();      // (the stem's output feeds the first stride-2 layer only)
         T2V_TRY(conv_norm(x, at(act[0], b.lvl[0]), 1, Ptrs{}, false, raw));
@@ -379,13 +448,15 @@ struct Runner {
             raw = raw_out;
         }
         if (nb == 0) {
+            T2V_REQUIRE(!pend_out, "internal: an encoder without blocks ends in an applied norm");
             *out = act[n];
             return T2V_OK;
         }
-        return res_chain(act[n], nb, tmp, out);
+        return res_chain(act[n], nb, tmp, out, pend_out);
     }
 
-    int decoder(const float* x, float** dec, const float** out) {
+    // *out_raw: the last layer's output was left raw for the head (its (mean, rstd) in mr_of(im))
+    int decoder(const float* x, float** dec, const float** out, bool* out_raw) {
         const int n = g.is_local ? 1 : g.n_downsample;
         const float* cur = x;
         size_t cur_stride = b.bott;
@@ -393,13 +464,16 @@ struct Runner {
         for (int i = 0; i < n; ++i) {
             const int l = n - 1 - i;
             float* y = dec[l];
-            const bool raw_out = i + 1 < n && next_takes_raw();
+            // (the direct 128 <-> 256 layers load by LDS-DMA with hardware zero padding and take no pending norm: has_norm
+            // layers other than polyphase never answer next_takes_raw)
+            const bool raw_out = next_takes_raw();
             T2V_TRY(conv_norm(at(cur, cur_stride), at(y, b.lvl[l]), 1, Ptrs{}, raw, raw_out));
             raw = raw_out;
             cur = y;
             cur_stride = b.lvl[l];
         }
         *out = cur;
+        *out_raw = raw;
         return T2V_OK;
     }
 };
@@ -500,7 +574,7 @@ int t2v_generator_forward_batch(t2v_ctx* ctx, void* stream, const t2v_gen_desc* 
     const int branch_layers = 2 * nb_res + n + 1;              // res trunk + decoder + head of one branch
     Runner r{ctx, s, *d, specs, layers, b, batch};
     Runner r2{ctx, s2, *d, specs, layers, b, batch};
-    r2.sc = two_streams ? 1 : 0;
+    r2.sc = 1;      // (a scratch set of its own on one stream as well: the join reads both encoders' (mean, rstd) tables)
 
     Ptrs pose{}, prevp{};
     for (int im = 0; im < batch; ++im) {
@@ -513,10 +587,22 @@ int t2v_generator_forward_batch(t2v_ctx* ctx, void* stream, const t2v_gen_desc* 
     const float *segout, *imgout;
     T2V_TRY(fork());
     r2.li = enc_layers;
-    T2V_TRY(r2.encoder(prevp, b.encB, nb_enc, tmpB, &imgout));
-    T2V_TRY(r.encoder(pose, b.encA, nb_enc, tmpA, &segout));
+    // Both chains lazy (they have the same layers): their closing norms + residuals and the sum of the two run as ONE pass
+    // after the join instead of two apply passes and an add
+    const bool fused_join = r.chain_is_lazy(1 + n, nb_enc);
+    Runner::PendingNorm pendA{}, pendB{};
+    T2V_TRY(r2.encoder(prevp, b.encB, nb_enc, tmpB, &imgout, fused_join ? &pendB : nullptr));
+    T2V_TRY(r.encoder(pose, b.encA, nb_enc, tmpA, &segout, fused_join ? &pendA : nullptr));
     T2V_TRY(join());
-    T2V_TRY(launch_add(s, imgout, segout, b.d, (long)(batch * bott)));   // (norm + x) + seg: the order the fused form summed in
+    // (norm + x) + seg: the order the fused form summed in
+    if (fused_join) {
+        const bool aff = d->norm_affine != 0;
+        const NormJoinSide sb{pendB.y, b.mean_rstd[r2.sc], aff ? pendB.norm->gamma : nullptr, aff ? pendB.norm->beta : nullptr, pendB.res};
+        const NormJoinSide sa{pendA.y, b.mean_rstd[r.sc], aff ? pendA.norm->gamma : nullptr, aff ? pendA.norm->beta : nullptr, pendA.res};
+        T2V_TRY(launch_inorm_join(s, sb, sa, b.d, (long)(d->H >> n) * (d->W >> n), G << n, batch));
+    } else {
+        T2V_TRY(launch_add(s, imgout, segout, b.d, (long)(batch * bott)));
+    }
     const float* dsum = b.d;
     r.li = 2 * enc_layers;
 
@@ -539,27 +625,34 @@ int t2v_generator_forward_batch(t2v_ctx* ctx, void* stream, const t2v_gen_desc* 
         raw.p[im] = ios[im].raw ? ios[im].raw : (blend[im] ? b.raw + im * px4 : ios[im].out);
         fw.p[im] = ios[im].flow_w ? ios[im].flow_w : b.fw + im * px4;
     }
+    float *want_img_feat[kMaxBatch], *want_flow_feat[kMaxBatch];
+    for (int im = 0; im < batch; ++im) {
+        want_img_feat[im] = ios[im].img_feat;
+        want_flow_feat[im] = ios[im].flow_feat;
+    }
+    // Both branches of the global generator start from the same map d: where their chains are F(4x4) lazy chains, the input
+    // transform of d runs once, before the fork, and both first GEMMs read that V
+    const float* v0 = nullptr;
+    if (b.vshare && img_in == flow_in && r.chain_is_lazy(2 * enc_layers, nb_res)) {
+        T2V_TRY(r.share_v(2 * enc_layers, dsum));
+        v0 = b.vshare;
+    }
+    bool feat_raw = false;
     if (!d->no_flow) {
         // flow branch on the side stream (temporaries bt2: the encoders are done with them)
         T2V_TRY(fork());
         r2.li = 2 * enc_layers + branch_layers;
         const float *res_flow, *flow_feat;
-        T2V_TRY(r2.res_chain(flow_in, nb_res, tmpB, &res_flow));
-        T2V_TRY(r2.decoder(res_flow, b.decF, &flow_feat));
-        T2V_TRY(r2.head(r2.at(flow_feat, feat), fw));
-        for (int im = 0; im < batch; ++im)
-            if (ios[im].flow_feat)
-                T2V_HIP_CHECK(hipMemcpyAsync(ios[im].flow_feat, flow_feat + im * feat, feat * sizeof(float),
-                                             hipMemcpyDeviceToDevice, s2));
+        T2V_TRY(r2.res_chain(flow_in, nb_res, tmpB, &res_flow, nullptr, v0));
+        T2V_TRY(r2.decoder(res_flow, b.decF, &flow_feat, &feat_raw));
+        T2V_TRY(r2.head(r2.at(flow_feat, feat), fw, feat_raw));
+        T2V_TRY(r2.export_feat(flow_feat, feat, want_flow_feat, feat_raw));
     }
     const float *res_img, *img_feat;
-    T2V_TRY(r.res_chain(img_in, nb_res, tmpA, &res_img));
-    T2V_TRY(r.decoder(res_img, b.decI, &img_feat));
-    T2V_TRY(r.head(r.at(img_feat, feat), raw));
-    for (int im = 0; im < batch; ++im)
-        if (ios[im].img_feat)
-            T2V_HIP_CHECK(hipMemcpyAsync(ios[im].img_feat, img_feat + im * feat, feat * sizeof(float), hipMemcpyDeviceToDevice,
-                                         s));
+    T2V_TRY(r.res_chain(img_in, nb_res, tmpA, &res_img, nullptr, v0));
+    T2V_TRY(r.decoder(res_img, b.decI, &img_feat, &feat_raw));
+    T2V_TRY(r.head(r.at(img_feat, feat), raw, feat_raw));
+    T2V_TRY(r.export_feat(img_feat, feat, want_img_feat, feat_raw));
     if (!d->no_flow) {
         T2V_TRY(join());
         r.li += branch_layers;

@@ -73,11 +73,15 @@ int launch_polyphase_weight(hipStream_t s, const float* w, float* U, int Cout, i
 }
 
 // ---- input transform --------------------------------------------------------------------------------------------------------------
-// one thread = one tile x 2 channels.  DOWN: the tile's 9 x 9 patch starts at input (8 ty - 1, 8 tx - 1) (zero padding 1); its
+// UP: one thread = one tile x 2 channels; DOWN: one thread = one of the tile's four sub-blocks x 2 channels (below).
+// DOWN: the tile's 9 x 9 patch starts at input (8 ty - 1, 8 tx - 1) (zero padding 1); its
 // even patch indices 0, 2, .., 8 are the odd-phase samples (F(4,2) input, 5 of them), the odd indices 1, 3, 5, 7 the even-phase
 // samples (taken as they are).  UP: the 5 x 5 patch starts at input (4 ty, 4 tx) (zeros past the map); all five samples feed
 // F(4,2), the first four are also the 1-tap samples.  The four (transformed | plain) x (transformed | plain) sub-blocks are
-// done one after the other, so that at most 25 values per channel are live.
+// done one after the other, so that at most 25 values per channel are live.  The DOWN form gives each sub-block a thread of its
+// own (sub-block = bits above the channel pair of the flat index, uniform over a wave): four times the threads with 16-25 loads
+// each instead of 81 -- the 512 -> 1024 layer's 256 tiles x 256 channel pairs are 1024 blocks instead of 256 -- and every V
+// element comes from the same cdot calls on the same loads as before.
 // NORM: x is the previous layer's conv output that has not gone through its norm layer yet; the transform applies
 // relu((x - mean) * rstd [* gamma + beta]) on the fly -- by norm_apply (transform_common.h), the function inorm_apply_kernel
 // calls, so the result is bit-identical to apply-then-transform -- and that layer's apply pass (a read and a write of the map) is dropped.  The zero
@@ -88,14 +92,19 @@ __global__ __launch_bounds__(256) void polyphase_input_kernel(const float2* __re
                                                              const float2* __restrict__ mean_rstd,
                                                              const float2* __restrict__ gamma,
                                                              const float2* __restrict__ beta, int relu) {
-    const long total = (long)Tt * C2;
+    constexpr int NSUB = UP ? 1 : 4;
+    const long total = (long)Tt * NSUB * C2;
     const long stride = (long)gridDim.x * blockDim.x;
     for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += stride) {
-        const long tile = i / C2;
-        const int c2 = (int)(i - tile * C2);
-        if (tile >= T) {   // padding tiles: zeros
+        const long ts = i / C2;
+        const int c2 = (int)(i - ts * C2);
+        const long tile = ts / NSUB;
+        const int sub = (int)(ts - tile * NSUB);      // DOWN: 0 = (1), .., 3 = (4) below; UP: all four
+        auto mine = [&](int s) { return UP || sub == s; };
+        if (tile >= T) {   // padding tiles: zeros (each sub-block's thread its own positions)
 #pragma unroll 1
-            for (int pos = 0; pos < 81; ++pos) V[((long)pos * Tt + tile) * C2 + c2] = make_float2(0.f, 0.f);
+            for (int pos = 0; pos < 81; ++pos)
+                if (mine((pos / 9 >= 5 ? 2 : 0) + (pos % 9 >= 5 ? 1 : 0))) V[((long)pos * Tt + tile) * C2 + c2] = make_float2(0.f, 0.f);
             continue;
         }
         const int ty = (int)(tile / TW), tx = (int)(tile - (long)ty * TW);
@@ -122,7 +131,7 @@ __global__ __launch_bounds__(256) void polyphase_input_kernel(const float2* __re
         };
         auto store = [&](int pr, int pc, float vx, float vy) { V[((long)(pr * 9 + pc) * Tt + tile) * C2 + c2] = make_float2(vx, vy); };
         // (1) transformed rows x transformed columns: 5 x 5 -> 5 x 5
-        {
+        if (mine(0)) {
             float rx[5][5], ry[5][5];
 #pragma unroll
             for (int a = 0; a < 5; ++a) {
@@ -152,6 +161,7 @@ __global__ __launch_bounds__(256) void polyphase_input_kernel(const float2* __re
             }
         }
         // (2) transformed rows x plain columns: per plain column a 5-vector down the rows
+        if (mine(1))
 #pragma unroll
         for (int b = 0; b < 4; ++b) {
             float cx[5], cy[5];
@@ -165,6 +175,7 @@ __global__ __launch_bounds__(256) void polyphase_input_kernel(const float2* __re
             for (int p = 0; p < 5; ++p) store(p, 5 + b, cdot<5>(pp::kBU[p], cx), cdot<5>(pp::kBU[p], cy));
         }
         // (3) plain rows x transformed columns
+        if (mine(2))
 #pragma unroll
         for (int a = 0; a < 4; ++a) {
             float dx[5], dy[5];
@@ -178,6 +189,7 @@ __global__ __launch_bounds__(256) void polyphase_input_kernel(const float2* __re
             for (int q = 0; q < 5; ++q) store(5 + a, q, cdot<5>(pp::kBU[q], dx), cdot<5>(pp::kBU[q], dy));
         }
         // (4) plain x plain: copies
+        if (mine(3))
 #pragma unroll
         for (int a = 0; a < 4; ++a)
 #pragma unroll
@@ -195,7 +207,7 @@ int launch_polyphase_input(hipStream_t s, const float* x, float* V, int H, int W
     T2V_REQUIRE((ln.gamma == nullptr) == (ln.beta == nullptr) && (ln.relu == 0 || ln.relu == 1) && !ln.res && !ln.xout,
                 "polyphase_input: bad norm arguments");
     const TileGrid tg = up ? tile_grid(H, W, 4) : tile_grid(H / 2, W / 2, 4);
-    const int grid = pp_grid((long)Tt * (C / 2), 256);
+    const int grid = pp_grid((long)Tt * (up ? 1 : 4) * (C / 2), 256);
     auto kern = up ? (ln.mean_rstd ? polyphase_input_kernel<true, true> : polyphase_input_kernel<true, false>)
                    : (ln.mean_rstd ? polyphase_input_kernel<false, true> : polyphase_input_kernel<false, false>);
     hipLaunchKernelGGL(kern, dim3(grid), dim3(256), 0, s, reinterpret_cast<const float2*>(x), reinterpret_cast<float2*>(V), H, W,

@@ -245,6 +245,12 @@ struct HeadParams {
     float* y;
     int H, W, Cin_s, Kp, Cout, Cout_s, act;
     float act_scale;
+    // x is a conv output that has not gone through its norm layer yet (mean_rstd != null): every wave applies
+    // relu((x - mean) * rstd [* gamma + beta]) to its halo plane in LDS before the taps read it (relu == 1: the only form)
+    const float* mean_rstd = nullptr;
+    const float* gamma = nullptr;    // both or neither
+    const float* beta = nullptr;
+    int relu = 0;
 };
 int launch_conv_head7x7(hipStream_t s, const HeadParams& p);
 
@@ -342,6 +348,17 @@ int launch_inorm_finalize(hipStream_t s, const float* stats, int nparts, int mti
 int launch_inorm_apply(hipStream_t s, const float* x, const float* mean_rstd, const float* gamma,
                        const float* beta, const float* res1, const float* res2, float* y, long npix, int C,
                        int relu, int nimg = 1);
+// one side of the encoder join: norm(y) + res, the batch's maps back to back, the (mean, rstd) tables 2*C floats apart
+struct NormJoinSide {
+    const float* y = nullptr;
+    const float* mean_rstd = nullptr;
+    const float* gamma = nullptr;    // both or neither
+    const float* beta = nullptr;
+    const float* res = nullptr;
+};
+// y = (norm_a(a.y) + a.res) + (norm_b(b.y) + b.res): two inorm_apply passes and the add that joins them, in ONE launch of
+// inorm_apply_kernel
+int launch_inorm_join(hipStream_t s, const NormJoinSide& a, const NormJoinSide& b, float* y, long npix, int C, int nimg);
 int launch_bn_running_update(hipStream_t s, const float* mean_rstd, float* running_mean, float* running_var, long n,
                              float momentum, float eps, int C);
 int launch_pack_conv_weight(hipStream_t s, const float* w, float* packed, int Cout, int Cin, int KH, int KW,

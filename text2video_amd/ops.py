@@ -241,6 +241,22 @@ def conv2d(x, packed_w, bias, desc, y_cs=None, stats=None, out=None):
     return y
 
 
+def conv2d_head_norm(x, packed_w, bias, desc, mean_rstd, gamma=None, beta=None, relu=True, y_cs=None, out=None):  # relu: must be on
+    """A 7x7 head on the RAW output x [H,W,x_cs] of the conv before it: the kernel applies that layer's norm ((mean, rstd)
+    from instance_norm_finalize, gamma / beta, ReLU) to its halo planes.  Same bits as instance_norm_apply + conv2d."""
+    c = context()
+    _chk(x, "x")
+    _chk(mean_rstd, "mean_rstd")
+    x_cs = x.shape[-1]
+    ho, wo = conv_out_dims(desc)
+    y_cs = round_up(desc.Cout, 4) if y_cs is None else y_cs
+    y = out if out is not None else torch.empty(ho, wo, y_cs, dtype=torch.float32, device=x.device)
+    check(c.lib.t2v_conv2d_forward_head_norm(c.handle, _stream(), ctypes.byref(desc), _p(x), x_cs, _p(packed_w), _p(bias),
+                                             _p(y), y_cs, _p(mean_rstd), _p(gamma), _p(beta), int(relu)),
+          "conv2d_forward_head_norm")
+    return y
+
+
 def conv2d_batch(x, packed_w, bias, desc, y_cs=None, stats=None, out=None):
     """conv2d for a batch x: [B,H,W,x_cs] in ONE launch (direct algorithm) -> y [B,Hout,Wout,y_cs]; `stats` holds B
     consecutive per-image partial blocks (conv_stats_buffer(desc).numel() floats each).  Every image's result is
