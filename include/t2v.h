@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define T2V_ABI_VERSION 19
+#define T2V_ABI_VERSION 20
 
 typedef enum {
     T2V_OK = 0,
@@ -529,6 +529,33 @@ int t2v_generator_forward(t2v_ctx* ctx, void* stream, const t2v_gen_desc* d, con
 size_t t2v_generator_workspace_bytes_batch(const t2v_gen_desc* d, int batch);
 int t2v_generator_forward_batch(t2v_ctx* ctx, void* stream, const t2v_gen_desc* d, const t2v_layer* layers,
                                 int n_layers, const t2v_gen_io* ios, int batch, void* workspace, size_t ws_bytes);
+
+/* ------------------------------------------------------------------------------------------
+ * Dense optical flow (ABI 20): stands in for upstream's `flowNet(real_B, real_B_prev)` -- FlowNet2, whose code and weights
+ * are not in the reference tree -- as the producer of the train step's reference flow.  It is NOT FlowNet2: a classical
+ * coarse-to-fine iterative Lucas-Kanade estimate on the grey images, fully local (no global solve, no atomics: two calls
+ * give the same bits).  The flow lives on cur's grid and points into prev, cur(x, y) ~ prev(x + u, y + v), in pixels: what
+ * t2v_flow_warp_composite / upstream's resample take.
+ *   grey = (R + G + B) / 3 of the three channels from c0 of an NHWC fp32 tensor with channel stride cs;
+ *   pyramid: level l+1 = AvgPool2d(3, 2, 1, count_include_pad=False) of level l.  levels == 0: the default rule, start at 1
+ *     and halve while levels < 6 and min(ceil(h/2), ceil(w/2)) >= 16 (512x512: 6, 64x96: 3, 48x40: 2);
+ *   per level, coarsest first: the flow starts at zero (coarsest) or at 2 * bilinear(coarser flow; x/2, y/2); gx, gy =
+ *     central differences of cur (replicate border); with n = (2r+1)^2 and box = window SUM (zeros outside the image)
+ *     Sxx = box(gx^2) + lambda n, Syy = box(gy^2) + lambda n, Sxy = box(gx gy), det = Sxx Syy - Sxy^2 (>= (lambda n)^2);
+ *   per iteration: it = prev(x + u, y + v) - cur (bilinear, position clamped into the image); bx = -box(gx it),
+ *     by = -box(gy it); du = (Syy bx - Sxy by) / det, dv = (Sxx by - Sxy bx) / det; the step is cut to length 1
+ *     (divide by max(1, |(du, dv)|)); then u and v are replaced by their 3x3 mean over the taps inside the image.
+ * flow_out: [H][W][4] = (u, v, 0, 0).  workspace: t2v_optical_flow_workspace_floats(H, W, levels) floats (0 for a shape the
+ * call refuses), 8-byte aligned, any content.  Refused, with nothing launched: H or W < 8, radius outside 1..7, iters < 1,
+ * lambda <= 0, more than 8 levels.  No allocation, no host synchronisation and no atomics inside the call.  Every gather
+ * coordinate is clamped (fminf / fmaxf) before it becomes an index: a non-finite input cannot address outside a plane.
+ * Kernel launches per call, fixed by (levels, iters) alone:  levels * (iters + 1) + 1
+ *   = levels (grey + pyramid of both images) + levels * iters (one per level and iteration) + 1 (output).
+ * ------------------------------------------------------------------------------------------ */
+size_t t2v_optical_flow_workspace_floats(int H, int W, int levels);
+int t2v_optical_flow(t2v_ctx* ctx, void* stream, const float* cur, int cur_cs, int cur_c0, const float* prev, int prev_cs,
+                     int prev_c0, int H, int W, int levels, int iters, int radius, float lambda, float* workspace,
+                     float* flow_out);
 
 /* ------------------------------------------------------------------------------------------
  * Host plumbing (ABI 14): device buffers, pinned host buffers, copies, streams and events for a host that has no HIP

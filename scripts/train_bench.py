@@ -1,6 +1,6 @@
 """Time Vid2VidTrainer.train_step at config-5 size on one GPU (1 sequence per GPU, max_frames_per_gpu 2): generator
 (with the flow branch unless --no_flow) forward + backward, 2-scale discriminator (+ face discriminator), all losses,
-Adam.  Usage: train_bench.py [--size 512] [--iters 3] [--no_flow] [--vgg] [--no_face]"""
+Adam.  Usage: train_bench.py [--size 512] [--iters 3] [--no_flow] [--vgg] [--no_face] [--flow_ref lk]"""
 import argparse, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -14,6 +14,8 @@ ap.add_argument("--frames", type=int, default=2)
 ap.add_argument("--iters", type=int, default=3)
 ap.add_argument("--no_flow", action="store_true")
 ap.add_argument("--no_face", action="store_true")
+ap.add_argument("--flow_ref", default="zero", choices=["zero", "lk"], help="train.py's --flow_ref: lk = the reference flow of the "
+                "flow / warp losses is ops.optical_flow of the real frames (one call per frame) instead of zero")
 ap.add_argument("--vgg", action="store_true", help="add the VGG19 perceptual loss (seeded random weights)")
 ap.add_argument("--aten_stacks", action="store_true", help="one step under torch.profiler: where the ATen fills / adds / "
                 "copies of the step come from (python call sites, by count)")
@@ -40,6 +42,7 @@ argv = ["--name", "b", "--dataset_mode", "pose", "--input_nc", "3", "--openpose_
 argv += ["--vgg_random_init"] if args.vgg else ["--no_vgg"]
 argv += ["--no_flow"] if args.no_flow else []
 argv += [] if args.no_face else ["--add_face_disc"]
+argv += ["--flow_ref", args.flow_ref] if args.flow_ref != "zero" else []
 opt = TrainOptions().parse(argv)
 dev = "cuda:0"
 H = W = args.size
@@ -79,19 +82,25 @@ if args.host_time:
         _optD_step()
         host_marks.append(time.perf_counter())
     tr.optD.step = _marked
+from bench import ClockSampler
+clock = ClockSampler(0, period=0.01)      # core clock from sysfs during the timed steps
 t0 = time.perf_counter()
 starts = []
-for _ in range(args.iters):
-    starts.append(time.perf_counter())
-    losses = step()
-torch.cuda.synchronize()
+with clock:
+    for _ in range(args.iters):
+        starts.append(time.perf_counter())
+        losses = step()
+    torch.cuda.synchronize()
 dt = (time.perf_counter() - t0) / args.iters
+# each step ends in the losses' read-back, so the distance between two starts is one step: median beside the mean
+per_step = np.diff(np.array(starts + [t0 + dt * args.iters])) * 1e3
 if args.host_time:
     print("host has enqueued the step after %.1f ms on average (of %.1f ms per step)"
           % (1e3 * sum(m - s0 for m, s0 in zip(host_marks, starts)) / len(starts), dt * 1e3))
-print("train step %dx%d, %d frames, %s%s%s: %.1f ms/step, peak mem %.1f GB | %s"
+print("train step %dx%d, %d frames, %s%s%s%s: %.1f ms/step (median %.2f, min %.2f, max %.2f of %d; %s MHz), peak mem %.1f GB | %s"
       % (H, W, F, "no flow" if args.no_flow else "flow branch on", "" if args.no_face else " + face D", " + VGG" if args.vgg else "",
-         dt * 1e3, torch.cuda.max_memory_allocated() / 2**30, " ".join("%s %.3f" % kv for kv in losses.items())))
+         ", --flow_ref lk" if args.flow_ref == "lk" else "", dt * 1e3, np.median(per_step), per_step.min(), per_step.max(),
+         len(per_step), clock.mean_mhz(), torch.cuda.max_memory_allocated() / 2**30, " ".join("%s %.3f" % kv for kv in losses.items())))
 if args.cprofile:
     import cProfile, pstats, io
     pr = cProfile.Profile()

@@ -1441,6 +1441,25 @@ int t2v_copy_channels(t2v_ctx* ctx, void* stream, const float* src, int src_cs, 
     return launch_copy_channels((hipStream_t)stream, src, src_cs, src_c0, dst, dst_cs, dst_c0, nc, npix);
 }
 
+// ---- dense optical flow (ABI 20) ----
+size_t t2v_optical_flow_workspace_floats(int H, int W, int levels) {
+    return optical_flow_shape_ok(H, W, levels) ? optical_flow_workspace_floats(H, W, levels) : 0;
+}
+int t2v_optical_flow(t2v_ctx* ctx, void* stream, const float* cur, int cur_cs, int cur_c0, const float* prev, int prev_cs,
+                     int prev_c0, int H, int W, int levels, int iters, int radius, float lambda, float* workspace,
+                     float* flow_out) {
+    T2V_REQUIRE(ctx && cur && prev && workspace && flow_out, "optical_flow: null pointer");
+    T2V_REQUIRE(H >= 8 && W >= 8, "optical_flow: H, W must be >= 8 (got %d x %d)", H, W);
+    T2V_REQUIRE(optical_flow_shape_ok(H, W, levels), "optical_flow: unsupported size %d x %d or level count %d", H, W, levels);
+    T2V_REQUIRE(radius >= 1 && radius <= 7, "optical_flow: radius must be in 1..7 (got %d)", radius);
+    T2V_REQUIRE(iters >= 1, "optical_flow: iters must be >= 1 (got %d)", iters);
+    T2V_REQUIRE(lambda > 0.f, "optical_flow: lambda must be > 0");
+    T2V_REQUIRE(cur_c0 >= 0 && cur_c0 + 3 <= cur_cs && prev_c0 >= 0 && prev_c0 + 3 <= prev_cs,
+                "optical_flow: the three channels from c0 must lie inside the channel stride");
+    return launch_optical_flow((hipStream_t)stream, cur, cur_cs, cur_c0, prev, prev_cs, prev_c0, H, W, levels, iters, radius,
+                               lambda, workspace, flow_out);
+}
+
 // ---- host plumbing (ABI 14): buffers, copies, streams, events for a host without a HIP binding of its own ----
 int t2v_device_malloc(t2v_ctx* ctx, size_t bytes, void** out) {
     T2V_REQUIRE(ctx && out, "device_malloc: null pointer");

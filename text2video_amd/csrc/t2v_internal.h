@@ -395,6 +395,13 @@ int launch_u8_pose_to_f32(hipStream_t s, const uint8_t* src, float* dst, long np
 int launch_copy_channels(hipStream_t s, const float* src, int src_cs, int src_c0, float* dst, int dst_cs,
                          int dst_c0, int nc, long npix);
 
+// optical_flow.hip: dense coarse-to-fine Lucas-Kanade flow (t2v_optical_flow)
+int optical_flow_default_levels(int H, int W);
+bool optical_flow_shape_ok(int H, int W, int levels);
+size_t optical_flow_workspace_floats(int H, int W, int levels);
+int launch_optical_flow(hipStream_t s, const float* cur, int cur_cs, int cur_c0, const float* prev, int prev_cs, int prev_c0,
+                        int H, int W, int levels, int iters, int radius, float lambda, float* workspace, float* flow_out);
+
 }  // namespace t2v
 
 struct t2v_ctx {

@@ -359,6 +359,44 @@ def flow_warp_composite_backward(d_out, d_warp, raw, fw, prev, prev_c0, want_d_p
     return d_raw, d_fw, d_prev
 
 
+_flow_workspaces = {}      # (device, H, W, levels) -> workspace of optical_flow
+
+
+def optical_flow_workspace(H, W, levels=None, device=None):
+    """A workspace optical_flow accepts for this geometry (one call at a time may use it)."""
+    n = int(_lib.load().t2v_optical_flow_workspace_floats(H, W, int(levels or 0)))
+    if n == 0:
+        raise ValueError("optical_flow: unsupported size %d x %d or level count %r" % (H, W, levels))
+    return torch.empty(n, dtype=torch.float32, device=device)
+
+
+def optical_flow(cur, prev, cur_c0=0, prev_c0=0, levels=None, iters=3, radius=3, lam=1e-3, out=None, workspace=None):
+    """Dense optical flow from cur to prev (t2v_optical_flow: coarse-to-fine iterative Lucas-Kanade on the grey images):
+    cur [H,W,cs], prev [H,W,cs'] NHWC, three channels from cur_c0 / prev_c0 -> [H,W,4] = (u, v, 0, 0) in pixels with
+    cur(x, y) ~ prev(x + u, y + v), the flow flow_warp takes.  levels None: the default rule (include/t2v.h).  The
+    workspace is cached per geometry when none is given (calls on one stream follow each other, so they may share it)."""
+    c = context()
+    _chk(cur, "cur")
+    _chk(prev, "prev")
+    H, W = cur.shape[0], cur.shape[1]
+    if cur.dim() != 3 or prev.dim() != 3 or prev.shape[:2] != cur.shape[:2]:
+        raise ValueError("optical_flow: cur and prev must be [H,W,C] of one size")
+    lv = int(levels or 0)
+    if workspace is None:
+        key = (cur.device, H, W, lv)
+        workspace = _flow_workspaces.get(key)
+        if workspace is None and c.lib.t2v_optical_flow_workspace_floats(H, W, lv):
+            workspace = _flow_workspaces[key] = optical_flow_workspace(H, W, levels, cur.device)
+    elif workspace.numel() < c.lib.t2v_optical_flow_workspace_floats(H, W, lv):
+        raise ValueError("optical_flow: workspace too small")
+    if workspace is None:      # a shape the library refuses: let it say so (nothing is launched, the pointer is not read)
+        workspace = cur
+    out = torch.empty(H, W, 4, dtype=torch.float32, device=cur.device) if out is None else out
+    check(c.lib.t2v_optical_flow(c.handle, _stream(), _p(cur), cur.shape[-1], cur_c0, _p(prev), prev.shape[-1], prev_c0,
+                                 H, W, lv, int(iters), int(radius), float(lam), _p(workspace), _p(out)), "optical_flow")
+    return out
+
+
 def avgpool3x3s2(x):
     """AvgPool2d(3, 2, 1, count_include_pad=False) on [H,W,C]."""
     c = context()

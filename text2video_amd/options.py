@@ -159,6 +159,9 @@ class TrainOptions(BaseOptions):
         g("--lambda_T", type=float, default=10.0)
         g("--no_ganFeat", action="store_true")
         g("--no_vgg", action="store_true")
+        g("--flow_ref", type=str, default="zero", choices=["zero", "lk"], help="reference flow of the flow / warp losses and "
+          "the temporal discriminators' flow channels when the caller passes none (upstream: FlowNet2, not available): zero "
+          "flow, or lk = the dense Lucas-Kanade estimate between the real frames (ops.optical_flow)")
         g("--vgg_weights", type=str, default="", help="torchvision vgg19 state dict (.pth) for the perceptual loss; the "
           "reference lets torchvision download it, which this tree cannot")
         g("--vgg_random_init", action="store_true", help="run the VGG loss path on seeded random weights (timing / tests)")

@@ -1818,6 +1818,8 @@ class Vid2VidTrainer:
                                                                                   opt.norm, seed + 10 + s),
                                                   opt.ndf, opt.n_layers_D, opt.num_D, opt.norm, device))
         self._hist_real, self._hist_fake = [], []    # frames of the running sequence (fakes detached)
+        # where the reference flow comes from when the caller passes none: "zero", or "lk" = ops.optical_flow on the real frames
+        self.flow_ref_mode = getattr(opt, "flow_ref", "zero")
         d_params = list(self.D.parameters()) + (list(self.Df.parameters()) if self.Df else [])
         for dt in self.DT:
             d_params += list(dt.parameters())
@@ -1872,12 +1874,15 @@ class Vid2VidTrainer:
         #   W      = MaskedL1(weight, 0, conf)  (--no_first_img)    G_Warp = MaskedL1(fake_B, resample(fake_B_prev, flow_ref), conf) * lambda_T
         # flow_ref / conf_ref come from FlowNet2 upstream; here they are inputs (zero flow by default)
         with torch.no_grad():
+            if flow_ref is None and self.flow_ref_mode == "lk":
+                # --flow_ref lk: the dense Lucas-Kanade estimate between the real frames stands in for FlowNet2's
+                flow_ref = torch.stack([ops.optical_flow(real[i], real_prev[i]) for i in range(F_)])
             if flow_ref is None:
                 if not getattr(self, "_warned_zero_flow", False):
                     self._warned_zero_flow = True
                     print("warning: flow / warp / weight losses run against a synthetic ZERO reference flow (FlowNet2 is not "
-                          "in the reference tree; pass flow_ref / conf_ref, or --no_flow to train without the flow branch)",
-                          flush=True)
+                          "in the reference tree; pass flow_ref / conf_ref or --flow_ref lk, or --no_flow to train without the "
+                          "flow branch)", flush=True)
                 flow_ref = torch.zeros(F_, H, W, 4, dtype=torch.float32, device=dev)
                 real_prev_warp = real_prev
             else:
@@ -1899,6 +1904,34 @@ class Vid2VidTrainer:
         loss_G_warp = masked_l1(fake, fake_prev_warp, conf_ref, 3) * opt.lambda_T
         return (loss_F_flow + loss_F_warp + loss_W + loss_G_warp,
                 {"F_Flow": loss_F_flow, "F_Warp": loss_F_warp, "W": loss_W, "G_Warp": loss_G_warp})
+
+    def _temporal_flows(self, reals, ends, d):
+        """--flow_ref lk: the flows between consecutive REAL frames of every temporal window (frames t - (tD-1) d, ..., t - d,
+        t for t in ends) -> [len(ends),H,W,2*(tD-1)], channels 2k, 2k+1 = (u, v) of optical_flow(w[k+1], w[k]); the real
+        and the generated stack of a temporal discriminator both carry them (upstream: flow_ref_skipped).  None under
+        --flow_ref zero: those channels stay zero."""
+        if self.flow_ref_mode != "lk":
+            return None
+        with torch.no_grad():
+            rows = []
+            for t in ends:
+                w = [reals[t - (self.tD - 1 - k) * d] for k in range(self.tD)]
+                rows.append(torch.cat([ops.optical_flow(w[k + 1], w[k])[..., :2] for k in range(self.tD - 1)], -1))
+            return torch.stack(rows)
+
+    def _temporal_stack(self, frames, ends, d, dt, flows=None):
+        """Input of temporal discriminator dt: per window its tD frames' colour channels, then `flows` (_temporal_flows) or
+        zeros in the 2*(tD-1) flow channels, zero-padded to the storage width"""
+        H, W, dev = frames[0].shape[0], frames[0].shape[1], frames[0].device
+        rows = []
+        for j, t in enumerate(ends):
+            w = [frames[t - (self.tD - 1 - k) * d][..., :3] for k in range(self.tD)]
+            nz = ops.round_up(dt.input_nc, 4) - 3 * self.tD
+            if flows is not None:
+                w.append(flows[j])
+                nz -= flows.shape[-1]
+            rows.append(torch.cat(w + [torch.zeros(H, W, nz, dtype=torch.float32, device=dev)], -1))
+        return torch.stack(rows).contiguous()
 
     def _d_pass(self, net, inputs, book, names, face_weight=1.0):
         """One discriminator on its real input and its one or two generated inputs (fake, raw) as ONE batch of passes
@@ -2027,13 +2060,10 @@ class Vid2VidTrainer:
                 if not ends:
                     continue
 
+                flows = self._temporal_flows(reals, ends, d_)
+
                 def stack(frames):
-                    rows = []
-                    for t in ends:
-                        w = [frames[t - (self.tD - 1 - k) * d_][..., :3] for k in range(self.tD)]
-                        z = torch.zeros(H, W, ops.round_up(dt.input_nc, 4) - 3 * self.tD, dtype=torch.float32, device=dev)
-                        rows.append(torch.cat(w + [z], -1))
-                    return torch.stack(rows).contiguous()
+                    return self._temporal_stack(frames, ends, d_, dt, flows)
                 a, b_, c, d = self._d_pass(dt, [stack(reals), stack(fks)], book,
                                            ("D_T%d" % sc, "G_T_GAN%d" % sc, "G_T_GAN_Feat%d" % sc))
                 tG += a; sG += b_; tD += c; sD += d
@@ -2197,13 +2227,10 @@ class Vid2VidTrainer:
                 ends = [t for t in range(n_old, n_old + F_) if t - (self.tD - 1) * d >= 0]
                 if not ends:
                     continue
+                flows = self._temporal_flows(reals, ends, d)
+
                 def stack(frames):
-                    rows = []
-                    for t in ends:
-                        w = [frames[t - (self.tD - 1 - k) * d][..., :3] for k in range(self.tD)]
-                        z = torch.zeros(H, W, ops.round_up(dt.input_nc, 4) - 3 * self.tD, dtype=torch.float32, device=dev)
-                        rows.append(torch.cat(w + [z], -1))
-                    return torch.stack(rows).contiguous()
+                    return self._temporal_stack(frames, ends, d, dt, flows)
                 tr, tf = stack(reals), stack(fks)
                 pr_t = dt(tr)
                 pfd_t, pfg_t = d_fake(dt, tf)
