@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define T2V_ABI_VERSION 20
+#define T2V_ABI_VERSION 21
 
 typedef enum {
     T2V_OK = 0,
@@ -556,6 +556,38 @@ size_t t2v_optical_flow_workspace_floats(int H, int W, int levels);
 int t2v_optical_flow(t2v_ctx* ctx, void* stream, const float* cur, int cur_cs, int cur_c0, const float* prev, int prev_cs,
                      int prev_c0, int H, int W, int levels, int iters, int radius, float lambda, float* workspace,
                      float* flow_out);
+
+/* ------------------------------------------------------------------------------------------
+ * Image resampling for the training loader (ABI 21): PIL's `Image.resize` of a clip's frames, the crop and
+ * torchvision's ToTensor + Normalize(.5, .5) in ONE launch, bit for bit what the CPU path computes.
+ *   src: T uint8 frames [T][h][w][3] of one size (device memory).
+ *   The resampler is separable and table-driven; the tables are device pointers the host built (the library knows no
+ *   filter).  Per axis, for every coordinate i of the WHOLE resized image (out_w / out_h entries):
+ *     first[i], count[i]: the taps are source indices first[i] .. first[i] + count[i] - 1 (count[i] <= k);
+ *     coef[i][k] (int32): their weights, scaled by 2^22.
+ *   Arithmetic, Pillow's 8-bit resampler (int32 throughout), in this order:
+ *     horizontal:  b(x', y)  = clip8((2^21 + sum_j src(x_first[x'] + j, y) * x_coef[x'][j]) >> 22)
+ *     vertical:    u(x', y') = clip8((2^21 + sum_j   b(x', y_first[y'] + j) * y_coef[y'][j]) >> 22)
+ *   with an arithmetic shift and clip8 = saturation to [0, 255]: the vertical pass runs on the horizontal pass's BYTES.
+ *   An axis that keeps its size takes the identity table (one tap of 2^22), as Pillow skips that pass.
+ *   dst: fp32 [T][crop_h][crop_w][dst_cs]; pixel (x, y) of frame t receives u(crop_x + x, crop_y + y) in channels
+ *   [dst_c0, dst_c0 + 3) as (u * (1.0f / 255.0f) - 0.5f) / 0.5f; the other channels are not touched.  That is train.py's
+ *   (u8.float() / 255.0 - 0.5) / 0.5 as ATen evaluates it on the device (a division by a host scalar is a multiplication by
+ *   its fp32 reciprocal there), i.e. the numbers the default loader trains on; t2v_pose_u8_to_f32 forms the true quotient
+ *   u / 255.0f (torchvision's ToTensor on the CPU), which is one ulp away for some of the 256 bytes.
+ * Only the columns and source rows the crop window needs are computed.  One launch; no allocation, no host
+ * synchronisation, no atomics: two calls give the same bits.
+ * Limits: kx, ky <= T2V_RESAMPLE_MAX_TAPS (Pillow's bicubic down to 1/8 of the source size per axis; 17 taps = 1/4), and
+ * the taps of 8 consecutive output rows within 96 source rows, which every resampler table within the tap limit keeps.
+ * Refused with T2V_ERR_INVALID and nothing launched: more taps, T outside 1..65535, an empty frame, a crop window outside
+ * the resized image, dst_c0 + 3 > dst_cs -- the caller resizes on the CPU.  Table entries are clamped before they address
+ * memory: wrong tables give wrong values, not a fault.
+ * ------------------------------------------------------------------------------------------ */
+#define T2V_RESAMPLE_MAX_TAPS 33
+int t2v_resample_crop_normalize_u8(t2v_ctx* ctx, void* stream, const uint8_t* src, int T, int h, int w,
+                                   const int32_t* x_first, const int32_t* x_count, const int32_t* x_coef, int kx, int out_w,
+                                   const int32_t* y_first, const int32_t* y_count, const int32_t* y_coef, int ky, int out_h,
+                                   int crop_x, int crop_y, int crop_w, int crop_h, float* dst, int dst_cs, int dst_c0);
 
 /* ------------------------------------------------------------------------------------------
  * Host plumbing (ABI 14): device buffers, pinned host buffers, copies, streams and events for a host that has no HIP

@@ -15,7 +15,7 @@ LIB_PATH = os.environ.get("T2V_LIBRARY") or os.path.join(_HERE, "lib", "libt2v_h
 T2V_OK = 0
 PAD_ZERO, PAD_REFLECT = 0, 1
 ACT_NONE, ACT_TANH, ACT_FLOW_W, ACT_LRELU = 0, 1, 2, 3
-ABI_VERSION = 20
+ABI_VERSION = 21
 MAX_BATCH = 8     # T2V_MAX_BATCH
 ALGO_DIRECT, ALGO_WINOGRAD, ALGO_WINOGRAD_F4, ALGO_POLYPHASE = 0, 1, 2, 3
 
@@ -170,6 +170,10 @@ SIGNATURES = {
     "t2v_optical_flow_workspace_floats": (c_size_t, [c_int, c_int, c_int]),
     "t2v_optical_flow": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int,
                                  c_int, c_float, c_void_p, c_void_p]),
+    # image resampling for the training loader (ABI 21)
+    "t2v_resample_crop_normalize_u8": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
+                                               c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int,
+                                               c_int, c_void_p, c_int, c_int]),
     # host plumbing (ABI 14): what text2video_amd/leantorch.py allocates, copies and synchronises with
     "t2v_device_malloc": (c_int, [c_void_p, c_size_t, POINTER(c_void_p)]),
     "t2v_device_free": (c_int, [c_void_p, c_void_p]),

@@ -1460,6 +1460,25 @@ int t2v_optical_flow(t2v_ctx* ctx, void* stream, const float* cur, int cur_cs, i
                                lambda, workspace, flow_out);
 }
 
+// ---- image resampling for the training loader (ABI 21) ----
+int t2v_resample_crop_normalize_u8(t2v_ctx* ctx, void* stream, const uint8_t* src, int T, int h, int w,
+                                   const int32_t* x_first, const int32_t* x_count, const int32_t* x_coef, int kx, int out_w,
+                                   const int32_t* y_first, const int32_t* y_count, const int32_t* y_coef, int ky, int out_h,
+                                   int crop_x, int crop_y, int crop_w, int crop_h, float* dst, int dst_cs, int dst_c0) {
+    T2V_REQUIRE(ctx && src && x_first && x_count && x_coef && y_first && y_count && y_coef && dst,
+                "resample_crop_normalize_u8: null pointer");
+    T2V_REQUIRE(T >= 1 && T <= 65535, "resample_crop_normalize_u8: T must be in 1..65535 (got %d)", T);
+    T2V_REQUIRE(h >= 1 && w >= 1 && out_w >= 1 && out_h >= 1, "resample_crop_normalize_u8: empty frame");
+    T2V_REQUIRE(kx >= 1 && ky >= 1 && kx <= resample_max_taps() && ky <= resample_max_taps(),
+                "resample_crop_normalize_u8: %d x %d taps, the limit is %d (resize on the CPU)", kx, ky, resample_max_taps());
+    T2V_REQUIRE(crop_w >= 1 && crop_h >= 1 && crop_x >= 0 && crop_y >= 0 && crop_x <= out_w - crop_w && crop_y <= out_h - crop_h,
+                "resample_crop_normalize_u8: crop %dx%d at (%d, %d) outside the %dx%d resized image", crop_w, crop_h, crop_x,
+                crop_y, out_w, out_h);
+    T2V_REQUIRE(dst_c0 >= 0 && dst_c0 + 3 <= dst_cs, "resample_crop_normalize_u8: channels [c0, c0+3) outside the channel stride");
+    return launch_resample_crop_normalize_u8((hipStream_t)stream, src, T, h, w, x_first, x_count, x_coef, kx, y_first, y_count,
+                                             y_coef, ky, crop_x, crop_y, crop_w, crop_h, dst, dst_cs, dst_c0);
+}
+
 // ---- host plumbing (ABI 14): buffers, copies, streams, events for a host without a HIP binding of its own ----
 int t2v_device_malloc(t2v_ctx* ctx, size_t bytes, void** out) {
     T2V_REQUIRE(ctx && out, "device_malloc: null pointer");

@@ -402,6 +402,13 @@ size_t optical_flow_workspace_floats(int H, int W, int levels);
 int launch_optical_flow(hipStream_t s, const float* cur, int cur_cs, int cur_c0, const float* prev, int prev_cs, int prev_c0,
                         int H, int W, int levels, int iters, int radius, float lambda, float* workspace, float* flow_out);
 
+// image_resample.hip: table-driven 8-bit resampling + crop + normalise (t2v_resample_crop_normalize_u8)
+int resample_max_taps();
+int launch_resample_crop_normalize_u8(hipStream_t s, const uint8_t* src, int T, int h, int w, const int* x_first,
+                                      const int* x_count, const int* x_coef, int kx, const int* y_first, const int* y_count,
+                                      const int* y_coef, int ky, int crop_x, int crop_y, int crop_w, int crop_h, float* dst,
+                                      int dst_cs, int dst_c0);
+
 }  // namespace t2v
 
 struct t2v_ctx {

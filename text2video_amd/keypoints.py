@@ -287,6 +287,21 @@ def render_person(person, size, basic_point_only=False, exact_fit=True, hand_dis
     return img
 
 
+def skip_drop_draws(rng, n_people, drop_prob, remove_face_labels=False, basic_point_only=False):
+    """Advance `rng` by exactly the draws read_keypoints makes for a frame of `n_people` persons (render_person: the
+    jitter draws, then one keep() per limb, hand and face, drawn whether or not the part is valid), without rasterising:
+    the training loader hands a rasteriser process a copy of the generator's state and moves its own generator on."""
+    if drop_prob <= 0:
+        return
+    for _ in range(n_people):
+        if remove_face_labels:
+            rng.standard_normal((5, 2))
+            rng.standard_normal()
+            rng.standard_normal()
+        for _ in range(min(len(POSE_LIMBS), len(POSE_RGB)) + (0 if basic_point_only else 3)):
+            rng.random()
+
+
 def read_keypoints(json_input, size, random_drop_prob=0, remove_face_labels=False, basic_point_only=False,
                    exact_fit=True, hand_discs=True, rng=None):
     """Same call signature as the reference routine (+ keyword extras).  size = (w, h).

@@ -438,6 +438,94 @@ def pose_u8_to_f32(src_u8, dst, c0):
     return dst
 
 
+def _bicubic(x):
+    """Pillow's bicubic_filter (a = -0.5), evaluated in its operation order"""
+    import numpy as np
+    a = -0.5
+    x = np.abs(x)
+    return np.where(x < 1.0, ((a + 2.0) * x - (a + 3.0)) * x * x + 1.0,
+                    np.where(x < 2.0, (((x - 5.0) * x + 8.0) * x - 4.0) * a, 0.0))
+
+
+def pillow_bicubic_tables(in_size, out_size):
+    """The tap table of Pillow's 8-bit BICUBIC resampler along one axis (precompute_coeffs + normalize_coeffs_8bpc of
+    Resample.c, in float64): -> (first [out] int32, count [out] int32, coef [out, ksize] int32 scaled by 2^22, zero past
+    count).  An axis that keeps its size gets the identity table (one tap of 2^22): Pillow skips that pass, and the
+    bicubic coefficients at scale 1 are not the identity."""
+    import numpy as np
+    in_size, out_size = int(in_size), int(out_size)
+    if in_size < 1 or out_size < 1:
+        raise ValueError("pillow_bicubic_tables: sizes must be positive")
+    if in_size == out_size:
+        return (np.arange(out_size, dtype=np.int32), np.ones(out_size, np.int32),
+                np.full((out_size, 1), 1 << 22, np.int32))
+    scale = in_size / out_size
+    fs = max(scale, 1.0)
+    support = 2.0 * fs
+    ksize = int(np.ceil(support)) * 2 + 1
+    c = (np.arange(out_size, dtype=np.float64) + 0.5) * scale
+    first = np.maximum(0, np.trunc(c - support + 0.5).astype(np.int64))
+    end = np.minimum(in_size, np.trunc(c + support + 0.5).astype(np.int64))
+    count = end - first
+    j = np.arange(ksize, dtype=np.int64)[None, :]
+    w = _bicubic((j + first[:, None] - c[:, None] + 0.5) * (1.0 / fs))
+    w = np.where(j < count[:, None], w, 0.0)
+    ww = np.cumsum(w, axis=1)[:, -1:]              # a left-to-right sum, as the C loop's (np.sum adds pairwise)
+    w = np.where(ww != 0.0, w / np.where(ww != 0.0, ww, 1.0), w)
+    coef = np.trunc(np.where(w < 0, -0.5, 0.5) + w * float(1 << 22)).astype(np.int32)
+    return first.astype(np.int32), count.astype(np.int32), np.ascontiguousarray(coef)
+
+
+def pillow_bicubic_taps(in_size, out_size):
+    """ksize of pillow_bicubic_tables(in_size, out_size): what t2v_resample_crop_normalize_u8's limit is stated in"""
+    import math
+    return 1 if in_size == out_size else 2 * math.ceil(2.0 * max(in_size / out_size, 1.0)) + 1
+
+
+RESAMPLE_MAX_TAPS = 33      # T2V_RESAMPLE_MAX_TAPS
+_resample_tables = {}       # (device, in, out) -> (first, count, coef) on the device
+
+
+def resample_tables_device(in_size, out_size, device):
+    """pillow_bicubic_tables(in, out) as int32 device tensors, cached per (device, in, out)"""
+    key = (str(device), int(in_size), int(out_size))
+    t = _resample_tables.get(key)
+    if t is None:
+        if len(_resample_tables) > 256:            # random scales: a few dozen geometries per dataset
+            _resample_tables.clear()
+        t = _resample_tables[key] = tuple(torch.from_numpy(a).to(device) for a in pillow_bicubic_tables(in_size, out_size))
+    return t
+
+
+def resample_crop_normalize_u8(src_u8, new_size, crop_pos, crop_size, out=None, c0=0, x_tables=None, y_tables=None):
+    """Image.resize(new_size, BICUBIC) of T uint8 frames [T,h,w,3] on the device, cropped to crop_size = (w, h) at
+    crop_pos = (x, y) and normalised as (v/255-0.5)/0.5 into channels [c0, c0+3) of out [T,crop_h,crop_w,cs] (default: a
+    new [..., 4] tensor whose pad channel is zero); the other channels of `out` keep their values.  One launch
+    (t2v_resample_crop_normalize_u8), bit-equal to Pillow + crop + the torch expression.  x_tables / y_tables: (first,
+    count, coef) int32 device tensors instead of Pillow's bicubic ones.  A geometry over the tap limit raises (status
+    T2V_ERR_INVALID, nothing launched)."""
+    c = context()
+    if not (src_u8.is_cuda and src_u8.dtype == torch.uint8 and src_u8.is_contiguous() and src_u8.dim() == 4
+            and src_u8.shape[-1] == 3):
+        raise ValueError("src_u8 must be a contiguous uint8 device tensor [T,h,w,3]")
+    T, h, w, _ = src_u8.shape
+    (nw, nh), (cx, cy), (cw, ch) = new_size, crop_pos, crop_size
+    xt = x_tables if x_tables is not None else resample_tables_device(w, nw, src_u8.device)
+    yt = y_tables if y_tables is not None else resample_tables_device(h, nh, src_u8.device)
+    if xt[0].numel() != nw or yt[0].numel() != nh:
+        raise ValueError("resample_crop_normalize_u8: the tables do not cover new_size")
+    if out is None:
+        out = torch.zeros(T, ch, cw, 4, dtype=torch.float32, device=src_u8.device)
+    _chk(out, "out")
+    if tuple(out.shape[:3]) != (T, ch, cw):
+        raise ValueError("resample_crop_normalize_u8: out must be [T,crop_h,crop_w,cs]")
+    check(c.lib.t2v_resample_crop_normalize_u8(c.handle, _stream(), _p(src_u8), T, h, w, _p(xt[0]), _p(xt[1]), _p(xt[2]),
+                                               xt[2].shape[1], nw, _p(yt[0]), _p(yt[1]), _p(yt[2]), yt[2].shape[1], nh,
+                                               int(cx), int(cy), int(cw), int(ch), _p(out), out.shape[-1], int(c0)),
+          "resample_crop_normalize_u8")
+    return out
+
+
 def tensor2im_u8(x):
     """util.tensor2im on the device: uint8 of (x+1)/2*255, same layout."""
     c = context()

@@ -162,6 +162,13 @@ class TrainOptions(BaseOptions):
         g("--flow_ref", type=str, default="zero", choices=["zero", "lk"], help="reference flow of the flow / warp losses and "
           "the temporal discriminators' flow channels when the caller passes none (upstream: FlowNet2, not available): zero "
           "flow, or lk = the dense Lucas-Kanade estimate between the real frames (ops.optical_flow)")
+        g("--train_loader", type=str, default="sync", choices=["sync", "prefetch"], help="sync: every clip is read, "
+          "rasterised and resized on the main thread between optimiser steps; prefetch: the same clips prepared ahead by "
+          "--nThreads rasteriser processes and decoder threads (TrainPoseDataset.iter_clips) and uploaded from pinned "
+          "memory on a copy stream")
+        g("--gpu_resize", action="store_true", help="with --train_loader prefetch: the frames' BICUBIC resize, crop and "
+          "normalisation run on the GPU in one launch per clip (ops.resample_crop_normalize_u8, Pillow's bytes); a geometry "
+          "over the kernel's tap limit is resized on the CPU")
         g("--vgg_weights", type=str, default="", help="torchvision vgg19 state dict (.pth) for the perceptual loss; the "
           "reference lets torchvision download it, which this tree cannot")
         g("--vgg_random_init", action="store_true", help="run the VGG loss path on seeded random weights (timing / tests)")

@@ -72,6 +72,34 @@ def _render_job(job):
     return np.ascontiguousarray(m)
 
 
+def _render_train_job(job):
+    """top-level (picklable) worker of the training loader: what TrainPoseDataset.sample() does for one pose map --
+    rasterise (with the clip generator's state at this frame when --random_drop_prob draws from it), NEAREST-resize, crop
+    -> uint8 [crop_h,crop_w,3]"""
+    (_, path, size, new_size, box, drop_prob, remove_face_labels, basic_point_only, exact_fit, hand_discs, rng_state) = job
+    rng = None
+    if rng_state is not None:
+        rng = np.random.default_rng()
+        rng.bit_generator.state = rng_state
+    m = keypoints.read_keypoints(path, size, drop_prob, remove_face_labels, basic_point_only, exact_fit=exact_fit,
+                                 hand_discs=hand_discs, rng=rng)
+    a = Image.fromarray(m).resize(new_size, Image.NEAREST)
+    return np.ascontiguousarray(np.asarray(a.crop(box)))
+
+
+def _decode_frame(path, new_size, box, out):
+    """JPEG -> RGB uint8 into `out` (a thread: Pillow releases the GIL while it decodes and resamples).  new_size None:
+    the raw decoded frame (the GPU resizes); else sample()'s BICUBIC resize + crop."""
+    with Image.open(path) as im:
+        b = im.convert("RGB")
+        if new_size is not None:
+            b = b.resize(new_size, Image.BICUBIC).crop(box)
+        b = np.asarray(b)
+    if b.shape != out.shape:
+        raise ValueError("%s: decoded to %s, the clip's other frames to %s" % (path, b.shape, out.shape))
+    out[...] = b
+
+
 class PoseDataset:
     def __init__(self, opt):
         self.opt = opt
@@ -421,3 +449,128 @@ class TrainPoseDataset:
             A.append(np.asarray(a.crop(box)))
             B.append(np.asarray(b.crop(box)))
         return {"A": np.stack(A), "B": np.stack(B), "seq": seq, "start": start, "t_step": step, "params": prm}
+
+    def iter_clips(self, indices, ahead=2, workers=None, gpu_resize=False, alloc=None):
+        """The clips sample() would return for `indices`, in that order and from the same generator, prepared ahead of
+        the consumer.  An entry of `indices` is an index, or (index, n_frames_total) for a clip drawn ahead of an epoch
+        boundary at which update_training_batch changes the clip length: it gets the length it would have had.
+
+        A pump thread draws every clip's parameters in index order (nothing else may use the generator meanwhile) and
+        hands the work out: pose maps to the rasteriser processes of raster_pool (fresh interpreters, not forks of a
+        process that may hold a GPU), JPEGs to decoder threads.  With --random_drop_prob > 0 the rasteriser draws from
+        the generator: each job carries the generator's state at its frame and the pump advances its own generator by
+        the same draws (keypoints.skip_drop_draws), so the draws stay in order.  At most `ahead` clips are in flight.
+
+        Yields sample()'s dict.  gpu_resize: instead of "B" the clip carries "raw", the decoded frames uint8 [T,h,w,3] in
+        ONE buffer, and "size" = (w, h); ops.resample_crop_normalize_u8(raw, **params) finishes them on the device.
+        alloc(shape) -> uint8 array: where "A" and "B" / "raw" are assembled (pinned host memory in train.py).
+        workers: rasteriser processes and decoder threads, default --nThreads; 0 rasterises in the pump thread.
+        An unreadable file or a dead worker ends the iteration with the file's name; nothing is retried here."""
+        import queue
+        import threading
+        from concurrent.futures import ThreadPoolExecutor
+        opt = self.opt
+        if workers is None:
+            workers = max(1, int(getattr(opt, "nThreads", 2)))
+        alloc = alloc or (lambda shape: np.empty(shape, np.uint8))
+        pool = None
+        if workers > 0:
+            from .raster_pool import get_pool
+            pool = get_pool(workers)
+        decoders = ThreadPoolExecutor(max_workers=max(1, workers), thread_name_prefix="decode")
+        q = queue.Queue(maxsize=max(1, ahead))
+        stop = threading.Event()
+
+        def put(item):
+            while not stop.is_set():
+                try:
+                    q.put(item, timeout=0.1)
+                    return True
+                except queue.Full:
+                    pass
+            return False
+
+        def draw(entry):
+            index, nft = entry if isinstance(entry, tuple) else (entry, self.n_frames_total)
+            rng = self.rng
+            seq = self.seqs[index % len(self.seqs)]
+            n, start, step = get_video_params(opt, nft, len(self.op[seq]), rng)
+            with Image.open(self.img[seq][0]) as im:
+                size = im.size
+            prm = get_train_img_params(opt, size, rng)
+            (nw, nh), (cw, ch), (cx, cy) = prm["new_size"], prm["crop_size"], prm["crop_pos"]
+            box = (cx, cy, cx + cw, cy + ch)
+            B = alloc((n, size[1], size[0], 3)) if gpu_resize else alloc((n, ch, cw, 3))
+            drop = opt.random_drop_prob
+            poses, frames = [], []
+            for i in range(n):
+                t = start + i * step
+                src = os.path.abspath(self.op[seq][t])      # the rasteriser workers do not share this working directory
+                if pool is None:
+                    a = keypoints.read_keypoints(src, size, drop, opt.remove_face_labels, opt.basic_point_only,
+                                                 exact_fit=not opt.fast_pose, hand_discs=not opt.no_hand_discs, rng=rng)
+                    poses.append((src, np.asarray(Image.fromarray(a).resize((nw, nh), Image.NEAREST).crop(box))))
+                else:
+                    state = None
+                    if drop > 0:
+                        import json
+                        state = rng.bit_generator.state
+                        with open(src, encoding="utf-8") as fh:
+                            people = len(json.load(fh)["people"])
+                        keypoints.skip_drop_draws(rng, people, drop, opt.remove_face_labels, opt.basic_point_only)
+                    poses.append((src, pool.submit(("train", src, size, (nw, nh), box, drop, opt.remove_face_labels,
+                                                    opt.basic_point_only, not opt.fast_pose, not opt.no_hand_discs, state))))
+                img = self.img[seq][t]
+                frames.append((img, decoders.submit(_decode_frame, img, None if gpu_resize else (nw, nh), box, B[i])))
+            meta = {"seq": seq, "start": start, "t_step": step, "params": prm}
+            if gpu_resize:
+                meta["size"] = size
+            return meta, poses, frames, B
+
+        def pump():
+            try:
+                for entry in indices:
+                    if stop.is_set() or not put(draw(entry)):
+                        return
+                put(None)
+            except BaseException as e:      # noqa: BLE001 -- handed to the consumer, which raises it
+                put(e)
+
+        th = threading.Thread(target=pump, name="clip-pump", daemon=True)
+        th.start()
+        try:
+            while True:
+                item = q.get()
+                if item is None:
+                    return
+                if isinstance(item, BaseException):
+                    raise item
+                meta, poses, frames, B = item
+                (cw, ch) = meta["params"]["crop_size"]
+                A = alloc((len(poses), ch, cw, 3))
+                for i, (path, a) in enumerate(poses):
+                    try:
+                        A[i] = a if isinstance(a, np.ndarray) else a.result()
+                    except Exception as e:      # noqa: BLE001
+                        raise RuntimeError("train loader: pose map of %s: %s: %s" % (path, type(e).__name__, e)) from e
+                for path, f in frames:
+                    try:
+                        f.result()
+                    except Exception as e:      # noqa: BLE001
+                        raise RuntimeError("train loader: frame %s: %s: %s" % (path, type(e).__name__, e)) from e
+                meta["A"] = A
+                meta["raw" if gpu_resize else "B"] = B
+                yield meta
+        finally:
+            stop.set()
+            while True:         # let a pump blocked on the full queue leave, drop what was drawn ahead
+                try:
+                    item = q.get_nowait()
+                except queue.Empty:
+                    break
+                if isinstance(item, tuple):
+                    for _, f in item[1] + item[2]:
+                        if not isinstance(f, np.ndarray):
+                            f.cancel()
+            th.join(timeout=5)
+            decoders.shutdown(wait=True)

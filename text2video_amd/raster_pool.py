@@ -33,7 +33,7 @@ def _read_exact(f, n):
 def _worker_main():
     """child side: job tuple in, (h, w, c) + bytes out; an exception travels back as text"""
     import numpy as np  # noqa: F401
-    from text2video_amd.pose_dataset import _render_job
+    from text2video_amd.pose_dataset import _render_job, _render_train_job
     inp, out = sys.stdin.buffer, sys.stdout.buffer
     sys.stdout = sys.stderr            # stray prints must not corrupt the result stream
     while True:
@@ -42,7 +42,7 @@ def _worker_main():
             return
         job = pickle.loads(_read_exact(inp, struct.unpack("<I", head)[0]))
         try:
-            m = _render_job(job)
+            m = _render_train_job(job) if job[0] == "train" else _render_job(job)      # (else job[0] is a path or a dict)
             out.write(struct.pack("<iii", *m.shape) + m.tobytes())
         except Exception as e:        # noqa: BLE001 -- reported to the caller, which raises
             msg = ("%s: %s" % (type(e).__name__, e)).encode()

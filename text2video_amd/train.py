@@ -2343,6 +2343,115 @@ class Vid2VidTrainer:
             torch.save(state_dict(dt), os.path.join(d, "%s_net_D_T%d.pth" % (epoch_label, sc)))
 
 
+class _ClipFeeder:
+    """--train_loader prefetch: clips from TrainPoseDataset.iter_clips, assembled in pinned host memory, uploaded on a
+    copy stream one clip ahead of the compute stream (an event orders the two), and finished on the device once per clip:
+    real_all [T,H,W,4] = the normalised frames, of which every chunk's `real` and `real_prev` are slices.  Under
+    --gpu_resize the loader hands over the decoded frames and ONE launch (ops.resample_crop_normalize_u8) resizes, crops
+    and normalises them; a geometry over the kernel's tap limit is resized with Pillow here instead.  real_all is kept
+    per geometry and its pad channel zeroed when it is created; the upload buffers alternate between two slots."""
+
+    def __init__(self, ds, opt, dev, schedule):
+        import collections
+        import threading
+        self.opt, self.dev = opt, dev
+        self.gpu_resize = bool(getattr(opt, "gpu_resize", False))
+        self.copy_stream = torch.cuda.Stream(device=dev)
+        self._free = collections.defaultdict(list)      # shape -> pinned tensors not in use
+        self._pinned = {}                                 # address of a handed-out array -> its pinned tensor
+        self._slots = {}                                  # (slot, what, shape) -> device uint8 buffer
+        self._slot_done = [None, None]                    # compute-stream event: the slot's last clip has been consumed
+        self._real_all = {}                               # (T, H, W) -> [T,H,W,4] fp32
+        self._n = 0
+        self._staged = None
+        self._held = []                                   # pinned tensors of the clip being consumed
+        self._lock = threading.Lock()
+        self._it = ds.iter_clips(schedule, ahead=2, gpu_resize=self.gpu_resize, alloc=self._alloc)
+
+    def _alloc(self, shape):      # called from the loader's threads
+        shape = tuple(int(v) for v in shape)
+        with self._lock:
+            t = self._free[shape].pop() if self._free[shape] else None
+        if t is None:
+            t = torch.empty(shape, dtype=torch.uint8, pin_memory=True)
+        a = t.numpy()
+        with self._lock:
+            self._pinned[a.ctypes.data] = t
+        return a
+
+    def _upload(self, arr, slot, what):
+        with self._lock:
+            t = self._pinned.pop(arr.ctypes.data)
+        key = (slot, what, tuple(t.shape))      # (a clip's pose maps and resized frames have one shape)
+        d = self._slots.get(key)
+        if d is None:
+            d = self._slots[key] = torch.empty(t.shape, dtype=torch.uint8, device=self.dev)
+        d.copy_(t, non_blocking=True)
+        return t, d
+
+    def stage(self):
+        """take the next clip from the loader (waits for it if the loader is behind) and start its upload"""
+        if self._staged is not None:
+            return
+        clip = next(self._it, None)
+        if clip is None:
+            return
+        slot = self._n % 2
+        self._n += 1
+        if self._slot_done[slot] is not None:
+            self.copy_stream.wait_event(self._slot_done[slot])
+        with torch.cuda.stream(self.copy_stream):
+            pa, A = self._upload(clip["A"], slot, "A")
+            pb, Bu = self._upload(clip["raw"] if self.gpu_resize else clip["B"], slot, "B")
+            ev = torch.cuda.Event()
+            ev.record(self.copy_stream)
+        self._staged = (clip, slot, A, Bu, ev, [pa, pb])
+
+    def take(self):
+        """-> (clip, A uint8 [T,H,W,3] on the device, real_all fp32 [T,H,W,4]); None when the schedule is exhausted"""
+        from . import ops as _ops
+        self.stage()
+        if self._staged is None:
+            return None
+        clip, slot, A, Bu, ev, pinned = self._staged
+        self._staged = None
+        with self._lock:      # the previous clip is done with its host arrays (its uploads completed long ago)
+            for t in self._held:
+                self._free[tuple(t.shape)].append(t)
+        self._held = pinned
+        torch.cuda.current_stream().wait_event(ev)
+        T_, H, W = A.shape[0], A.shape[1], A.shape[2]
+        real_all = self._real_all.get((T_, H, W))
+        if real_all is None:
+            real_all = self._real_all[(T_, H, W)] = torch.zeros(T_, H, W, 4, device=self.dev)
+        prm = clip["params"]
+        if self.gpu_resize:
+            (w, h), (nw, nh) = clip["size"], prm["new_size"]
+            if max(_ops.pillow_bicubic_taps(w, nw), _ops.pillow_bicubic_taps(h, nh)) <= _ops.RESAMPLE_MAX_TAPS:
+                _ops.resample_crop_normalize_u8(Bu, prm["new_size"], prm["crop_pos"], prm["crop_size"], out=real_all)
+            else:      # over the kernel's limit (a very strong downscale): the CPU path, on the frames as decoded
+                import numpy as np
+                from PIL import Image
+                ev.synchronize()
+                (cx, cy), (cw, ch) = prm["crop_pos"], prm["crop_size"]
+                B = np.stack([np.asarray(Image.fromarray(f).resize((nw, nh), Image.BICUBIC).crop((cx, cy, cx + cw, cy + ch)))
+                              for f in clip["raw"]])
+                real_all[..., :3] = (torch.from_numpy(B).to(self.dev).float() / 255.0 - 0.5) / 0.5
+        else:
+            real_all[..., :3] = (Bu.float() / 255.0 - 0.5) / 0.5
+        self._slot = slot
+        return clip, A, real_all
+
+    def consumed(self):
+        """the clip's last chunk has been launched: its upload slot may be overwritten once the compute stream gets here"""
+        ev = torch.cuda.Event()
+        ev.record()
+        self._slot_done[self._slot] = ev
+
+    def close(self):
+        self._it.close()
+
+
 def run_train(opt, steps=None):
     """train.py main: one process per GPU under torchrun (the reference used nn.DataParallel threads).
 
@@ -2395,6 +2504,22 @@ def run_train(opt, steps=None):
 
     rng = np.random.default_rng(100 + rank)          # synthetic data: every rank has its own sequence
     tG = opt.n_frames_G
+    feeder = None
+    if ds is not None and getattr(opt, "train_loader", "sync") == "prefetch":
+        def schedule():
+            """(clip index, n_frames_total) of every iteration from the resume point on: clips are drawn ahead of the
+            epoch ends at which update_training_batch doubles the clip length, so each carries the length of its epoch"""
+            cap = getattr(opt, "max_frames_total", 10 ** 9)
+            first_k = epoch_iter // world
+            for e in range(start_epoch, opt.niter + opt.niter_decay + 1):
+                ratio = (e - 1) // max(1, opt.niter_step)
+                nft = min(cap, opt.n_frames_total * 2 ** ratio) if ratio > 0 else opt.n_frames_total
+                for kk in range(first_k, per_epoch):
+                    yield (((e - 1) * per_epoch + kk) * world + rank, nft)
+                first_k = 0
+        feeder = _ClipFeeder(ds, opt, dev, schedule())
+    elif ds is not None and getattr(opt, "gpu_resize", False) and rank == 0:
+        print("warning: --gpu_resize has no effect without --train_loader prefetch", flush=True)
     last_pos = (start_epoch, epoch_iter)
     stats, it, total_samples = [], 0, (start_epoch - 1) * per_epoch * world + epoch_iter
     last_epoch = opt.niter + opt.niter_decay
@@ -2423,9 +2548,14 @@ def run_train(opt, steps=None):
                 # one clip per rank per iteration, walked in chunks of max_frames_per_gpu frames with the generated
                 # frames carried over (detached) from chunk to chunk, one optimiser step per chunk -- upstream's
                 # truncated recurrence
-                clip = ds.sample(((epoch - 1) * per_epoch + k) * world + rank)
-                A = torch.from_numpy(clip["A"]).to(dev)                      # [T,H,W,3] uint8
-                B = torch.from_numpy(clip["B"]).to(dev)
+                real_all = None
+                if feeder is not None:
+                    # the same clip, prepared ahead; real_all [T,H,W,4]: its frames normalised once, pad channel zero
+                    clip, A, real_all = feeder.take()
+                else:
+                    clip = ds.sample(((epoch - 1) * per_epoch + k) * world + rank)
+                    A = torch.from_numpy(clip["A"]).to(dev)                      # [T,H,W,3] uint8
+                    B = torch.from_numpy(clip["B"]).to(dev)
                 T_, H, W = A.shape[0], A.shape[1], A.shape[2]
                 if world > 1:   # every rank must run the same number of chunks (one gradient all-reduce per chunk)
                     import torch.distributed as dist
@@ -2439,12 +2569,17 @@ def run_train(opt, steps=None):
                     for j, t in enumerate(fr):
                         for f in range(tG):                                    # window: oldest frame first
                             ops.pose_u8_to_f32(A[t - tG + 1 + f], pose[j], 3 * f)
-                    real = torch.zeros(len(fr), H, W, 4, device=dev)
-                    real[..., :3] = (B[fr].float() / 255.0 - 0.5) / 0.5
                     real_prev = None
-                    if not trainer.spec.no_flow:
-                        real_prev = torch.zeros(len(fr), H, W, 4, device=dev)
-                        real_prev[..., :3] = (B[[t - 1 for t in fr]].float() / 255.0 - 0.5) / 0.5
+                    if real_all is not None:      # slices of the clip's frames: no arithmetic per chunk
+                        real = real_all[fr[0]:fr[-1] + 1]
+                        if not trainer.spec.no_flow:
+                            real_prev = real_all[fr[0] - 1:fr[-1]]
+                    else:
+                        real = torch.zeros(len(fr), H, W, 4, device=dev)
+                        real[..., :3] = (B[fr].float() / 255.0 - 0.5) / 0.5
+                        if not trainer.spec.no_flow:
+                            real_prev = torch.zeros(len(fr), H, W, 4, device=dev)
+                            real_prev[..., :3] = (B[[t - 1 for t in fr]].float() / 255.0 - 0.5) / 0.5
                     boxes = None
                     if opt.add_face_disc:      # one region for the chunk (upstream boxes the whole batch of frames)
                         box = get_face_region(clip["A"][fr], opt.fineSize)
@@ -2459,6 +2594,10 @@ def run_train(opt, steps=None):
                                 box = None
                         boxes = [box] * len(fr) if box is not None else None
                     losses, prev = trainer.train_step(pose, real, boxes, prev, real_prev=real_prev)
+                if feeder is not None:
+                    feeder.consumed()
+                    if steps is None or it + 1 < steps:
+                        feeder.stage()      # the next clip's upload runs beside this clip's chunks
                 what = ", seq %s, %d frames %dx%d step %d" % (clip["seq"], T_ - tG + 1, H, W, clip["t_step"])
             torch.cuda.synchronize()
             stats.append(time.perf_counter() - ts)
@@ -2484,6 +2623,8 @@ def run_train(opt, steps=None):
                 ds.update_training_batch(epoch // max(1, opt.niter_step))
             continue
         break   # the step cap was reached
+    if feeder is not None:
+        feeder.close()
     if world > 1:
         # the replicas started from the same seed and applied the same averaged gradients: their weights must still be
         # equal -- a cheap end-of-run check that the exchange reached every parameter on every rank
