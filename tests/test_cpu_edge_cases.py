@@ -192,12 +192,13 @@ def test_packed_weight_cache_remembers_what_the_last_step_used(monkeypatch):
     b1 = T.cached_pack(w, "b", maker("b"))
     assert a1 is a2 and calls == ["a", "b"] and torch.equal(b1, w.detach() * 2)
     T.invalidate_packs(w)
-    assert w._t2v_packs is None and sorted(w._t2v_repack) == ["a", "b"]
+    st = T.param_state(w)
+    assert st.packs is None and sorted(st.repack) == ["a", "b"]
     T.prefetch_packs([w])                     # CPU tensor: nothing is made ahead, the list is dropped
-    assert w._t2v_repack is None and getattr(w, "_t2v_pack_event", None) is None
+    assert st.repack is None and st.packs is None       # (no copies: no event of a batch made ahead either)
     T.cached_pack(w, "a", maker("a2"))        # next "step" uses only "a"
     T.invalidate_packs(w)
-    assert list(w._t2v_repack) == ["a"] and calls == ["a", "b", "a2"]
+    assert list(st.repack) == ["a"] and calls == ["a", "b", "a2"]
     # a view that names its owner shares the owner's cache
     v = w.detach()
     v._t2v_owner = w
@@ -246,20 +247,20 @@ def test_collected_weight_gradient_bookkeeping(monkeypatch):
     w = torch.nn.Parameter(torch.zeros(3, 2))
     # (1) without a bucket slot: the gradient comes back from the last node, None from the earlier ones
     with T.batched_weight_gradients([w]):
-        w._t2v_dw_uses = 3
+        T.param_state(w).dw_uses = 3
         parts = [pair(2), pair(2), pair(2)]
         outs = [T._paired_direct_wgrad(w, x, dy, "desc", None) for x, dy in parts]
         assert [o[0] for o in outs] == [True, True, True] and outs[0][1] is None and outs[1][1] is None
         assert torch.allclose(outs[2][1], want(parts)) and calls == [("batch", 6)]
-        assert w._t2v_dw_stash is None and w._t2v_dw_uses == 0
+        assert T.param_state(w).dw_stash is None and T.param_state(w).dw_uses == 0
         # two single images: the two-pointer entry, no copy
         del calls[:]
-        w._t2v_dw_uses = 2
+        T.param_state(w).dw_uses = 2
         parts = [pair(1), pair(1)]
         outs = [T._paired_direct_wgrad(w, x, dy, "desc", None) for x, dy in parts]
         assert torch.allclose(outs[1][1], want(parts)) and calls == [("pair", 2)]
         # one use: not taken, the caller reduces the node alone
-        w._t2v_dw_uses = 1
+        T.param_state(w).dw_uses = 1
         assert T._paired_direct_wgrad(w, *pair(2), "desc", None) == (False, None)
     # (2) with a bucket slot: every node counts once, the slot is written once
     gb = T.GradBuckets([w], bucket_mb=1, register=True)
@@ -268,7 +269,7 @@ def test_collected_weight_gradient_bookkeeping(monkeypatch):
         for _ in range(3):
             T.expect_gradient(w)
         gb.seal()
-        w._t2v_dw_uses = 3
+        T.param_state(w).dw_uses = 3
         sl = T.grad_slot(w)
         parts = [pair(2), pair(1), pair(2)]          # (ragged batches are concatenated all the same)
         del calls[:]
@@ -281,16 +282,158 @@ def test_collected_weight_gradient_bookkeeping(monkeypatch):
         assert torch.allclose(w.grad, want(parts))
     # (3) a pass that never comes back: the flush reduces what arrived; leaving the scope without it raises
     with T.batched_weight_gradients([w]):
-        w._t2v_dw_uses = 3
+        T.param_state(w).dw_uses = 3
         parts = [pair(2), pair(2)]
         for x, dy in parts:
             assert T._paired_direct_wgrad(w, x, dy, "desc", None) == (True, None)
         out = T.flush_pending_weight_gradients([w], [None])
-        assert torch.allclose(out[0], want(parts)) and w._t2v_dw_stash is None
+        assert torch.allclose(out[0], want(parts)) and T.param_state(w).dw_stash is None
     with pytest.raises(RuntimeError, match="flush_pending_weight_gradients"):
         with T.batched_weight_gradients([w]):
-            w._t2v_dw_uses = 2
+            T.param_state(w).dw_uses = 2
             T._paired_direct_wgrad(w, *pair(1), "desc", None)
+
+
+def test_collected_winograd_weight_gradient_bookkeeping(monkeypatch):
+    """The Winograd-domain collections (gradients._batched_winograd_wgrad / _keep_v_slot + _kept_winograd_wgrad; host logic, no
+    GPU): the kernels are stand-ins that write a per-image marker m into the slot they are given (V and A dy A^T both hold m;
+    the reduction returns sum of m^2 over the slots) on a workspace born full of NaN.  A layer counted N times reduces ONCE,
+    by its N-th node, every node is counted exactly once; the un-kept path fills the slots 0, 1, ... as the nodes arrive, the
+    kept path hands them out from the top so that the reverse arrival gives the same layout; with fewer nodes than counted the
+    flush zeroes every slot nobody filled, in both regions, before its single reduction; a scope left without it raises."""
+    import types
+    import pytest
+    import torch
+    from text2video_amd import ops
+    from text2video_amd import train as T
+    Cin, Cout = 2, 4
+    desc = types.SimpleNamespace(H=4, W=4, Cin=Cin, Cout=Cout, kH=3, stride=1, pad=1, pad_mode=0, transposed=0, output_padding=0, algo=0)
+    reduces = []
+
+    def regions(ws, total):      # tile pitch 1: V [36, total, Cin], A dy A^T [36, total, Cout]
+        nv = 36 * total * Cin
+        return ws[:nv].view(36, total, Cin), ws[nv:].view(36, total, Cout)
+
+    def workspace(d, xcs, batch, device):
+        return torch.full((36 * batch * (xcs + d.Cout),), float("nan"))
+
+    def reduce(d, ws, batch, xcs, ycs, out=None, accumulate=False):
+        reduces.append(ws.clone())
+        v, md = regions(ws, batch)
+        dw = torch.full((Cout, Cin, 3, 3), float((v[0, :, 0] * md[0, :, 0]).sum()))
+        if out is None:
+            return dw
+        out.copy_(out + dw if accumulate else dw)
+        return out
+
+    def stages(x, dy, d, ws, batch, b0, red, out=None, accumulate=False):
+        v, md = regions(ws, batch)
+        for i in range(x.shape[0]):
+            v[:, b0 + i] = x[i].flatten()[0]
+            md[:, b0 + i] = dy[i].flatten()[0]
+        return reduce(d, ws, batch, x.shape[-1], dy.shape[-1], out, accumulate) if red else None
+
+    def dy_only(dy, d, ws, batch, slot, xcs):
+        regions(ws, batch)[1][:, slot] = dy.flatten()[0]
+    monkeypatch.setattr(ops, "backward_weight_winograd_workspace", workspace)
+    monkeypatch.setattr(ops, "winograd_tile_rows", lambda d: 1)
+    monkeypatch.setattr(ops, "conv2d_backward_weight_winograd_stages", stages)
+    monkeypatch.setattr(ops, "conv2d_backward_weight_winograd_dy", dy_only)
+    monkeypatch.setattr(ops, "conv2d_backward_weight_winograd_reduce", reduce)
+
+    def image(m):       # (x, dy) of one image, both marked m
+        return torch.full((1, 4, 4, Cin), float(m)), torch.full((1, 4, 4, Cout), float(m))
+
+    def layout(ws, total):
+        v, md = regions(ws, total)
+        assert torch.equal(v[0, :, 0], md[0, :, 0])
+        return v[0, :, 0].tolist()
+    w = torch.nn.Parameter(torch.zeros(Cout, Cin, 3, 3))
+    st = T.param_state(w)
+    gb = T.GradBuckets([w], bucket_mb=1, register=True)
+
+    def begin(uses):
+        gb.begin_step()
+        for _ in range(uses):
+            T.expect_gradient(w)
+        gb.seal()
+        del reduces[:]
+        return T.grad_slot(w)
+
+    def forward_keeping_v(markers):      # what _ConvBlock.forward does per use: ask for a slot, write V there, count the image
+        kept = []
+        for m in markers:
+            kept.append(T._keep_v_slot(w, image(m)[0], desc, Cin, Cout))
+            ws, total, k = kept[-1]
+            regions(ws, total)[0][:, k] = float(m)
+            st.images += 1
+            st.seen += 1
+        return kept
+    # (1) un-kept, N = 3 nodes of one image each: the slots fill in arrival order, the third node reduces, each is counted once
+    with T.batched_weight_gradients([w]):
+        sl = begin(3)
+        st.images = st.seen = 3
+        for i, m in enumerate((5, 6, 7)):
+            dw, where = T._batched_winograd_wgrad(w, *image(m), desc, sl)
+            assert dw is None and where[1:] == (3, i) and sl.got == i + 1 and len(reduces) == (i == 2) and sl.filled is (i == 2)
+        assert layout(reduces[0], 3) == [5.0, 6.0, 7.0] and torch.all(sl.view == 25 + 36 + 49)
+        assert st.wino is None and st.images == 0
+        # ... without a bucket slot the last node returns the gradient
+        st.images = 2
+        assert T._batched_winograd_wgrad(w, *image(2), desc)[0] is None
+        assert torch.all(T._batched_winograd_wgrad(w, *image(3), desc)[0] == 4 + 9)
+    assert st.expect == 3          # what this step saw is what the next one prepares for
+    # (2) kept: the forward passes of frames 0, 1, 2 take the slots 2, 1, 0 of a workspace sized by the step before; the nodes
+    # arrive in reverse and land in the un-kept path's layout; one reduction, by the last node
+    with T.batched_weight_gradients([w]):
+        sl = begin(3)
+        kept = forward_keeping_v((5, 6, 7))
+        assert [k[2] for k in kept] == [2, 1, 0] and st.wino.kept
+        for i, m in enumerate((7, 6, 5)):
+            dw, where = T._kept_winograd_wgrad(w, image(m)[1], desc, kept[2 - i], sl)
+            assert dw is None and where == kept[2 - i] and sl.got == i + 1 and len(reduces) == (i == 2)
+        assert layout(reduces[0], 3) == [7.0, 6.0, 5.0] and torch.all(sl.view == 25 + 36 + 49) and st.wino is None
+    # ... a step that uses the layer less often than expected: the slot whose V was never written is zeroed by the last node
+    with T.batched_weight_gradients([w]):
+        sl = begin(2)
+        kept = forward_keeping_v((5, 6))
+        for i, m in enumerate((6, 5)):
+            T._kept_winograd_wgrad(w, image(m)[1], desc, kept[1 - i], sl)
+        assert len(reduces) == 1 and layout(reduces[0], 3) == [0.0, 6.0, 5.0] and sl.got == 2 and torch.all(sl.view == 25 + 36)
+    assert st.expect == 2
+    gb.absorb([None])
+    gb.finish()
+    assert torch.all(w.grad == 25 + 36) and T.grad_slot(w) is None          # (from here on without a bucket slot)
+    # (3) fewer nodes than counted: the flush leaves no NaN in either region before its single reduction
+    with T.batched_weight_gradients([w]):         # un-kept (T2V_WGRAD_KEEP_V=0): the slots [done:] of both regions
+        monkeypatch.setenv("T2V_WGRAD_KEEP_V", "0")
+        assert T._keep_v_slot(w, image(1)[0], desc, Cin, Cout) is None
+        monkeypatch.delenv("T2V_WGRAD_KEEP_V")
+        del reduces[:]
+        st.images = st.seen = 3
+        assert T._batched_winograd_wgrad(w, *image(4), desc) == (None, (st.wino.ws, 3, 0)) and not reduces
+        out = T.flush_pending_weight_gradients([w], [None])
+        assert len(reduces) == 1 and not torch.isnan(reduces[0]).any() and layout(reduces[0], 3) == [4.0, 0.0, 0.0]
+        assert torch.all(out[0] == 16) and st.wino is None
+    with T.batched_weight_gradients([w]):         # kept: frame 1's node never comes -- its slot holds V, no A dy A^T
+        del reduces[:]
+        kept = forward_keeping_v((5, 6, 7))
+        for f in (2, 0):
+            assert T._kept_winograd_wgrad(w, image(5 + f)[1], desc, kept[f]) == (None, kept[f])
+        assert not reduces and st.wino.filled == [True, False, True]
+        out = T.flush_pending_weight_gradients([w], [torch.ones(Cout, Cin, 3, 3)])
+        assert len(reduces) == 1 and not torch.isnan(reduces[0]).any() and layout(reduces[0], 3) == [7.0, 0.0, 5.0]
+        assert torch.all(out[0] == 1 + 49 + 25) and st.wino is None
+    # (4) a scope left with transformed slots nobody reduced raises
+    for keep in (True, False):
+        with pytest.raises(RuntimeError, match="flush_pending_weight_gradients"):
+            with T.batched_weight_gradients([w]):
+                if keep:
+                    T._kept_winograd_wgrad(w, image(7)[1], desc, forward_keeping_v((5, 6, 7))[2])
+                else:
+                    st.images = st.seen = 2
+                    T._batched_winograd_wgrad(w, *image(1), desc)
+        assert st.wino is None and st.expect == (3 if keep else 2)
 
 
 def test_direct_weight_gradient_splits_a_batch_that_passes_the_kernels_offset_limit(monkeypatch):
@@ -299,7 +442,7 @@ def test_direct_weight_gradient_splits_a_batch_that_passes_the_kernels_offset_li
     chunks that accumulate -- host logic, the kernel replaced by a stand-in."""
     import torch
     from text2video_amd import ops
-    from text2video_amd import train as T
+    from text2video_amd import gradients, train as T
     calls = []
 
     def fake(x, dy, desc, accumulate_into=None):
@@ -311,11 +454,11 @@ def test_direct_weight_gradient_splits_a_batch_that_passes_the_kernels_offset_li
     whole = T.direct_weight_gradient(x, dy, None)
     assert calls == [(6, False)]
     del calls[:]
-    monkeypatch.setattr(T, "_WGRAD_MAX_BYTES", 4 * (5 + 8) * (7 + 8) * 4 * 2 + 1)       # room for two (padded) images per launch
+    monkeypatch.setattr(gradients, "_WGRAD_MAX_BYTES", 4 * (5 + 8) * (7 + 8) * 4 * 2 + 1)       # room for two (padded) images per launch
     chunked = T.direct_weight_gradient(x, dy, None)
     assert calls == [(2, False), (2, True), (2, True)] and torch.allclose(chunked, whole, atol=1e-5)
     del calls[:]
-    monkeypatch.setattr(T, "_WGRAD_MAX_BYTES", 16)                                      # not even one: one image per launch
+    monkeypatch.setattr(gradients, "_WGRAD_MAX_BYTES", 16)                                      # not even one: one image per launch
     assert torch.allclose(T.direct_weight_gradient(x, dy, None), whole, atol=1e-5) and [c[0] for c in calls] == [1] * 6
 
 

@@ -220,7 +220,7 @@ def test_trainer_batches_the_frames_winograd_weight_gradients(tmp_path, monkeypa
         if mode == "1":
             # n_blocks 2 -> one ResnetBlock in each encoder tail + one in the trunk: 3 blocks x 2 convs, 2 frames
             assert len(calls) - n0 == 2 * 6, "every ResnetBlock conv of both frames takes the batched path"
-            assert all(getattr(p, "_t2v_wg_state", None) is None for p in tr.optG.params), "every reduction was flushed"
+            assert all(T.param_state(p).wino is None for p in tr.optG.params), "every reduction was flushed"
         else:
             assert len(calls) == n0
     worst = 0.0

@@ -368,7 +368,7 @@ def test_flow_branch_gets_its_weight_gradients_when_a_new_sequence_has_no_flow_l
                 if flush:
                     g = T.flush_pending_weight_gradients(params, g)
         if passes > 1:
-            assert max(getattr(p, "_t2v_wg_expect", 0) for p in params) == 2
+            assert max(T.param_state(p).expect for p in params) == 2
         return {k: gi for (k, _), gi in zip(G.named_upstream_parameters().items(), g)}
 
     ref = grads(False, False)
@@ -574,8 +574,8 @@ def test_weight_gradients_on_the_side_stream_leave_the_step_unchanged(t2v_env):
         nets = [tr.G, tr.D, tr.Df]
         runs[mode] = (ls, [p.detach().clone() for n in nets for p in n.parameters()])
         if mode == "1":
-            assert T._WG_SIDE["stream"] is not None
-            ahead = [p for p in tr.G.parameters() if getattr(p, "_t2v_pack_event", None) is not None]
+            assert T.STEP.stream is not None
+            ahead = [p for p in tr.G.parameters() if T.param_state(p).packs is not None and T.param_state(p).packs.event is not None]
             assert len(ahead) > 10            # the generator's packed weights for the next step are already under way
     for la, lb in zip(runs["1"][0], runs["0"][0]):
         assert la.keys() == lb.keys() and all(la[k] == lb[k] for k in la), [(k, la[k], lb[k]) for k in la if la[k] != lb[k]]
@@ -689,7 +689,7 @@ def test_kept_workspaces_when_a_step_uses_a_layer_more_or_less_often_than_the_on
     G = T.TrainableGenerator(spec, sd, "cuda:0")
     run(G, first)
     res = [p for k, p in G.named_upstream_parameters().items() if k.startswith("model_res") and p.dim() == 4]
-    assert res and all(getattr(p, "_t2v_wg_expect", 0) == first for p in res)
+    assert res and all(T.param_state(p).expect == first for p in res)
     got = run(G, second)
     ref = run(T.TrainableGenerator(spec, sd, "cuda:0"), second)
     keys = [k for k in ref if k.startswith("model_res") and ref[k] is not None and ref[k].dim() == 4]
@@ -738,7 +738,7 @@ def test_kept_input_transforms_and_in_place_forward_weights_leave_the_step_uncha
             ls.append(l)
         runs[mode] = (ls, [p.detach().clone() for n in (tr.G, tr.D) for p in n.parameters()], dict(calls))
         if mode == "1":
-            assert max(getattr(p, "_t2v_wg_expect", 0) for p in tr.G.parameters()) == 2      # two frames per step
+            assert max(T.param_state(p).expect for p in tr.G.parameters()) == 2      # two frames per step
     kept, plain = runs["1"][2], runs["0"][2]
     # steps 2 and 3 kept V (the first has no expectation yet); with both off nothing more was added
     assert kept["dy"] > 0 and kept["dy"] % 4 == 0 and plain["dy"] == kept["dy"], (kept, plain)

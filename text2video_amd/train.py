@@ -15,6 +15,7 @@ flow / warp / weight losses against a SUPPLIED reference flow (zero flow + its c
 FlowNet2, which produces it upstream, is not in the reference tree -- SURVEY 8d config 5), Adam(lr 2e-4,
 beta1 0.5), data-parallel gradient all-reduce.
 """
+import collections
 import contextlib
 import os
 import time
@@ -24,480 +25,17 @@ import torch
 from . import ops
 from .backward import ConvDataGrad
 from .generator import GeneratorSpec, layer_keys, synthetic_state_dict  # noqa: F401
+from .gradients import (STEP, GradBuckets, GradientExchange, GradSlot, ParamState, _acc, _batched_winograd_wgrad,  # noqa: F401
+                        _desc_key, _keep_v_slot, _kept_winograd_wgrad, _paired_direct_wgrad, allreduce_gradients,
+                        allreduce_gradients_begin, batched_weight_gradients, cached_pack, check_presence_across_ranks,
+                        deliver, deliver_direct, deliver_into, direct_weight_gradient, expect_gradient,
+                        flush_pending_weight_gradients, grad_slot, invalidate_packs, owner, param_state, prefetch_packs,
+                        side_gemm_hint, switch, wgrad_fork, wgrad_join, wgrad_stream_on, winograd_weight_gradient)
 
 
 # ------------------------------------------------------------------------------------------------
 # differentiable building blocks
 # ------------------------------------------------------------------------------------------------
-def cached_pack(w, key, make):
-    """Packed (or Winograd-transformed) layout of parameter `w`, kept until the optimiser next writes it: a step
-    runs every generator layer once per frame and every discriminator layer on real and fake inputs, all with the
-    same weights.  The cache lives on the parameter object itself (freed with it; autograd hands the same object to
-    backward).  T2V_TRAIN_PACK_CACHE=0 re-packs per call (saves the memory of the transformed copies)."""
-    if os.environ.get("T2V_TRAIN_PACK_CACHE", "1") == "0":
-        return make()
-    w = getattr(w, "_t2v_owner", w)    # a detached view of a parameter (frozen passes) shares its parameter's cache
-    ent = getattr(w, "_t2v_packs", None)
-    if ent is None or ent[0] != w._version:
-        ent = (w._version, {}, {}, set())       # version, copies, how each was made, which were used since the last write
-        w._t2v_packs = ent
-        w._t2v_pack_event = None
-        w._t2v_pack_made = {}
-    elif getattr(w, "_t2v_pack_event", None) is not None:
-        # packed ahead on the side stream (prefetch_packs): a use waits for that batch (on whichever stream it runs; a wait
-        # for an event that has completed costs nothing)
-        torch.cuda.current_stream().wait_event(w._t2v_pack_event)
-    if key not in ent[1]:
-        ent[1][key] = make()
-        ent[2][key] = make
-        if w.is_cuda:      # made on the spot (a first step, T2V_PACK_PREFETCH=0): by whom, and when it is complete
-            cur = torch.cuda.current_stream()
-            made = getattr(w, "_t2v_pack_made", None)
-            if made is None:
-                made = w._t2v_pack_made = {}
-            made[key] = (cur, cur.record_event())
-    elif w.is_cuda:
-        # the discriminators' layers are used from two streams in one step (their own backward pass on the trainer's
-        # `_d_stream`, the generator's pass through them on the current one): a copy made on the other stream is waited for
-        m = (getattr(w, "_t2v_pack_made", None) or {}).get(key)
-        if m is not None and m[0] != torch.cuda.current_stream():
-            torch.cuda.current_stream().wait_event(m[1])
-    ent[3].add(key)
-    return ent[1][key]
-
-
-def invalidate_packs(p):
-    """the optimiser has written `p` (through its raw pointer: no version bump): drop the packed copies, remember how
-    they were made"""
-    ent = getattr(p, "_t2v_packs", None)
-    # (only the copies the last step actually used: a geometry or mode that is gone is not made again for ever)
-    p._t2v_repack = {k: ent[2][k] for k in ent[3]} if (ent is not None and ent[3]) else None
-    p._t2v_packs = None
-    p._t2v_pack_event = None
-    p._t2v_pack_made = None
-
-
-def prefetch_packs(params):
-    """After the optimiser step: every packed / Winograd-transformed / transposed copy the last step used is made again
-    from the new weights NOW, on the side stream -- ~150 small memory-bound kernels per step (36 filter transforms of
-    151 MB each among them) that depend on nothing but the weights and would otherwise sit in front of each layer's
-    first use on the critical path; here they run under the next step's first convs.  T2V_PACK_PREFETCH=0: lazily."""
-    todo = [(p, p._t2v_repack) for p in params if getattr(p, "_t2v_repack", None)]
-    if not todo or os.environ.get("T2V_PACK_PREFETCH", "1") == "0" or not todo[0][0].is_cuda:
-        for p, _ in todo:
-            p._t2v_repack = None
-        return
-    with wgrad_fork(gemm=False):
-        for p, makers in todo:
-            p._t2v_packs = (p._version, {k: mk() for k, mk in makers.items()}, dict(makers), set())
-            p._t2v_repack = None
-        ev = torch.cuda.current_stream().record_event()
-    for p, _ in todo:
-        p._t2v_pack_event = ev
-
-
-# ------------------------------------------------------------------------------------------------
-# gradient slots: every trainable parameter owns a slice ("slot") of a persistent flat exchange bucket
-# (GradBuckets below).  Inside a train step the backward nodes DELIVER their weight / bias / affine gradients
-# straight into the slot -- the first node of a step writes, later nodes of the same parameter add (kernels with
-# an accumulate flag) -- and return None to autograd: no AccumulateGrad adds, no torch.cat / copy-back around the
-# collective, and a bucket's all-reduce starts the moment its last gradient has landed.
-# ------------------------------------------------------------------------------------------------
-class GradSlot:
-    __slots__ = ("owner", "bucket", "idx", "view", "expect", "got", "_filled", "zero_valid")
-
-    def __init__(self, owner, bucket, idx, view):
-        self.owner, self.bucket, self.idx, self.view = owner, bucket, idx, view
-        self.expect = self.got = 0
-        self._filled = False      # the slot holds this step's (partial) gradient
-        # the slot's memory holds exact zeros put there by deliver(zero=True) and nothing has written it since: the ~100
-        # biases in front of norm layers get that delivery every step -- one 4 KB memset each, once, instead of per step
-        # (an exchange averages zeros with the other ranks' zeros: the same layers are zero-delivered on every rank)
-        self.zero_valid = False
-
-    @property
-    def filled(self):
-        return self._filled
-
-    @filled.setter
-    def filled(self, v):
-        self._filled = bool(v)
-        if v:                     # every writer of the slot's memory marks it filled: the zeros are gone
-            self.zero_valid = False
-
-
-def grad_slot(p):
-    """the slot of parameter `p` if its buckets are collecting (inside a train step), else None"""
-    sl = getattr(p, "_t2v_gslot", None)
-    return sl if (sl is not None and sl.owner.collecting) else None
-
-
-def expect_gradient(p):
-    """forward side: one more backward node will deliver a gradient for `p` in this step"""
-    sl = grad_slot(p) if p is not None and p.requires_grad else None
-    if sl is not None:
-        sl.expect += 1
-
-
-def deliver(sl, tensor=None, zero=False):
-    """backward side: add `tensor` (or nothing / an exact zero) to slot `sl` and count the node as done"""
-    if tensor is not None:
-        _acc(sl.view, tensor, not sl.filled)
-        sl.filled = True
-    elif zero and not sl.filled:
-        if not sl.zero_valid:
-            _zero(sl.view)
-        sl._filled, sl.zero_valid = True, True
-    sl.owner.node_done(sl)
-
-
-_WG_BATCH = [False]
-_DW_PAIR = [False]     # inside a train-step scope: a direct-kernel layer used by exactly two frames reduces both in one launch
-
-
-def _paired_direct_wgrad(w, x, dc, fdesc, slot):
-    """Direct (non-Winograd) weight gradient of a layer that ran several times in this step's graph (counted in forward:
-    `w._t2v_dw_uses`): the backward nodes leave their (x, dY) on the weight, the LAST one to arrive launches ONE reduction over
-    all of them -- the kernel pays a fixed ~8 stage times per block, so one long reduction beats several short ones:
-      * two uses of one image each (the generator's stride-2 / transposed layers on the clip's two frames):
-        ops.conv2d_backward_weight_pair -- two base pointers, no copy; blocks 36 -> 73 stages, 0.64 -> 0.73 of peak;
-      * anything else (the discriminators' layers: real, fake and raw pass of two frames each -- round 5): the operands are
-        concatenated (a few MB per layer) and reduced as one batch: 3 launches of ~180 us at 0.39 of peak -> one.
-    Returns (taken, dW or None): not taken -> the caller reduces this node alone."""
-    uses = getattr(w, "_t2v_dw_uses", 0)
-    if not _DW_PAIR[0] or uses < 2:
-        return False, None
-    st = getattr(w, "_t2v_dw_stash", None)
-    if st is None:
-        st = w._t2v_dw_stash = [fdesc]
-    st.append((x, dc))
-    if len(st) - 1 < uses:
-        if slot is not None:
-            slot.owner.node_done(slot)
-        return True, None
-    parts = st[1:]
-    w._t2v_dw_stash, w._t2v_dw_uses = None, 0
-    return True, _reduce_stashed(parts, fdesc, slot)
-
-
-_WGRAD_MAX_BYTES = 0x7fff0000        # the weight-gradient kernel addresses its operands with 32-bit byte offsets (capi.hip)
-
-
-def direct_weight_gradient(x, dc, fdesc):
-    """packed dW of a batch [B,...] in as few launches as the kernel's 2 GiB operand limit allows: ONE for every shape of the
-    512 / 1024 configs; a batch whose x or dY (or padded x) would pass the limit -- many frames per GPU at 2048x1024 -- is
-    reduced in chunks of images, accumulating (three passes in one batch are 3x the single pass)."""
-    B = x.shape[0]
-    padded = (x.shape[1] + 8) * (x.shape[2] + 8) * x.shape[3] if x.dim() == 4 else x[0].numel()     # (the kernel pads x by <= 3 px)
-    per = 4 * max(padded, dc[0].numel(), 1)
-    step = max(1, min(B, (_WGRAD_MAX_BYTES - 1) // per))
-    dwp = None
-    for i in range(0, B, step):
-        dwp = ops.conv2d_backward_weight(x[i:i + step], dc[i:i + step], fdesc, accumulate_into=dwp)
-    return dwp
-
-
-def _reduce_stashed(parts, fdesc, slot, from_node=True):
-    """one weight-gradient launch over the stashed (x, dY) of a layer; into the bucket slot (-> None) or returned.
-    from_node: called by the backward node that brought the last operands (side stream, the node counts as delivered);
-    False: the flush after the backward pass (current stream; every node has been counted already)"""
-    flat = [t for pr in parts for t in pr]
-    xcs = parts[0][0].shape[-1]
-    with (wgrad_fork(*flat) if (from_node and slot is not None and wgrad_stream_on(parts[0][0])) else contextlib.nullcontext()):
-        if len(parts) == 2 and all(pr[0].shape[0] == 1 for pr in parts) and \
-                ops.backward_weight_strided_supported(fdesc, xcs, parts[0][1].shape[-1]):
-            (x0, dc0), (x1, dc1) = parts
-            dwp = ops.conv2d_backward_weight_pair(x0[0], dc0[0], x1[0], dc1[0], fdesc)
-        elif len(parts) == 1:
-            dwp = direct_weight_gradient(parts[0][0], parts[0][1], fdesc)
-        else:
-            dwp = direct_weight_gradient(torch.cat([pr[0] for pr in parts]), torch.cat([pr[1] for pr in parts]), fdesc)
-        if slot is not None:
-            ops.unpack_conv_weight_into(dwp, fdesc, xcs, slot.view, slot.filled)
-    if slot is not None:
-        slot.filled = True
-        if from_node:
-            slot.owner.node_done(slot)
-        return None
-    return ops.unpack_conv_weight(dwp, fdesc, xcs)
-
-
-@contextlib.contextmanager
-def batched_weight_gradients(params):
-    """Scope of one train step (forward and backward inside): layers that run once per frame reduce their
-    Winograd-domain weight gradients over all frames at once.  The per-weight counters are cleared on entry, so a
-    graph that was built but never back-propagated cannot leave a stale count behind.  T2V_WGRAD_BATCH=0: off."""
-    for p in params:
-        p._t2v_wg_images, p._t2v_wg_state = 0, None
-        p._t2v_wg_seen = 0
-        p._t2v_dw_uses, p._t2v_dw_stash = 0, None
-    _WG_BATCH[0] = os.environ.get("T2V_WGRAD_BATCH", "1") != "0"
-    _DW_PAIR[0] = os.environ.get("T2V_WGRAD_PAIR", "1") != "0"
-    _WG_SIDE["gemm"] = False
-    if params and params[0].is_cuda:
-        side_gemm_hint()
-    try:
-        yield
-    except BaseException:
-        _WG_BATCH[0] = False
-        _DW_PAIR[0] = False
-        _WG_SIDE["gemm"] = False
-        # an exception inside the step (OOM, an asynchronous error): let go of what the nodes parked on the weights -- operand
-        # lists, kept-V workspaces: GPU memory a retry needs (ADVICE r5)
-        for p in params:
-            p._t2v_dw_stash, p._t2v_dw_uses, p._t2v_wg_state, p._t2v_wg_images, p._t2v_wg_seen = None, 0, None, 0, 0
-        raise
-    _WG_BATCH[0] = False
-    _DW_PAIR[0] = False
-    _WG_SIDE["gemm"] = False
-    if params and params[0].is_cuda:
-        side_gemm_hint()
-    # a backward pass inside this scope that did not end with flush_pending_weight_gradients() would silently lose the
-    # gradients still parked on the weights (the first half of a pair, transformed slots waiting for their reduction)
-    left = [i for i, p in enumerate(params) if getattr(p, "_t2v_dw_stash", None) is not None
-            or (getattr(p, "_t2v_wg_state", None) is not None and p._t2v_wg_state[1] > 0)]
-    for p in params:
-        p._t2v_dw_stash, p._t2v_dw_uses, p._t2v_wg_state, p._t2v_wg_images = None, 0, None, 0
-        # what the layer saw in this step is what the next one prepares for (_keep_v_slot)
-        p._t2v_wg_expect = getattr(p, "_t2v_wg_seen", 0)
-    if left:
-        raise RuntimeError("batched_weight_gradients: %d parameter(s) (first: #%d) left the scope with an unreduced weight "
-                           "gradient -- call flush_pending_weight_gradients(params, grads) after the backward pass" % (len(left), left[0]))
-
-
-# ---- weight gradients on a second stream ---------------------------------------------------------------------------
-# Nothing in the backward pass waits for a weight gradient: the chain that has to run in order is dy -> norm backward ->
-# data gradient -> the next layer's dy.  With gradients delivered straight into bucket slots (GradBuckets) the weight-
-# gradient kernels of a node can therefore run on a side stream, next to the data-gradient kernels of the following
-# layers: the tails of one launch (4.5-round grids, split-K partial combines, transforms of 36 small matrices) are
-# filled by the other stream's blocks, as in the two-stream inference frames.  The side stream waits for the node's dc;
-# the main stream waits for the side stream before anything reads a slot (bucket collectives, absorb, finish).
-# T2V_WGRAD_STREAM=0: everything on one stream.
-# From the step's first weight gradient on the side stream to the end of the step BOTH streams carry fixed-grid GEMMs (data
-# gradient | Winograd-domain weight gradient).  A two-per-CU grid keeps every CU full until its last block leaves: the other
-# stream's launch -- and the bandwidth-bound kernels between two of the main stream's GEMMs -- queue behind it, the step was
-# the sum of its kernels (585 us per ResnetBlock layer of the second frame's backward pass against 591 us of kernels).  With
-# the overlap hint 2 (ops.set_overlap_hint) those kernels launch ONE block per CU and are resident side by side: 513 us per
-# layer, the same bits (profiles/r06_train_two_queues_{two,one}_per_cu.txt).  The hint is per thread and the backward nodes run on the
-# autograd engine's thread: every node (and the flush on the calling thread) sets it from the shared flag.
-# T2V_TRAIN_SK_HINT=0: two blocks per CU throughout.
-_WG_SIDE = {"stream": None, "pending": False, "gemm": False}
-
-
-def wgrad_stream_on(t):
-    return t.is_cuda and not _WG_SIDE.get("inline") and os.environ.get("T2V_WGRAD_STREAM", "1") != "0"
-
-
-def side_gemm_hint():
-    """this thread's launches from here on: one block per CU for the fixed-grid GEMMs while the side stream has GEMMs of its
-    own in this step, the library's default otherwise"""
-    ops.set_overlap_hint(2 if _WG_SIDE["gemm"] else 0)
-
-
-@contextlib.contextmanager
-def wgrad_fork(*tensors, gemm=True):
-    """kernels launched in this scope run on the side stream, after everything the current stream holds so far; the
-    tensors named (inputs allocated on the current stream) stay allocated until the side stream is done with them.
-    gemm: the scope launches weight-gradient GEMMs (not the repacking of weights after the optimiser step)"""
-    if _WG_SIDE["stream"] is None:
-        _WG_SIDE["stream"] = torch.cuda.Stream()
-    side = _WG_SIDE["stream"]
-    side.wait_stream(torch.cuda.current_stream())
-    for t in tensors:
-        if t is not None:
-            t.record_stream(side)
-    _WG_SIDE["pending"] = True
-    if gemm and not _WG_SIDE["gemm"] and os.environ.get("T2V_TRAIN_SK_HINT", "1") != "0":
-        _WG_SIDE["gemm"] = True
-        side_gemm_hint()
-    with torch.cuda.stream(side):
-        yield
-
-
-def wgrad_join():
-    """the current stream waits for the weight gradients in flight on the side stream"""
-    if _WG_SIDE["pending"]:
-        torch.cuda.current_stream().wait_stream(_WG_SIDE["stream"])
-        _WG_SIDE["pending"] = False
-
-
-def _keep_v_slot(w, x, ddesc, xcs, ycs):
-    """Forward side of a batched Winograd-domain weight gradient (use number `w._t2v_wg_images` of this step, not counted
-    yet): from a layer's second step on, the workspace of its weight gradient exists BEFORE the forward pass -- sized for
-    the images the previous step counted (`_t2v_wg_expect`) -- and the forward conv writes its input transform V straight
-    into a slot of it: backward transforms dy only (72 input transforms of 13.5 us fewer per step of the 512x512 config).
-    The slots are handed out from the top, so that the backward nodes -- which arrive in reverse -- fill them in the order
-    the un-kept path would: the same reduction order, the same bits.  Returns (workspace, slots, slot) or None: not kept
-    (first step, a batch, more uses than expected, T2V_WGRAD_KEEP_V=0)."""
-    expect = getattr(w, "_t2v_wg_expect", 0)
-    idx = getattr(w, "_t2v_wg_images", 0)
-    if x.shape[0] != 1 or expect < 1 or idx >= expect or xcs != ddesc.Cin or os.environ.get("T2V_WGRAD_KEEP_V", "1") == "0":
-        return None
-    st = getattr(w, "_t2v_wg_state", None)
-    if st is None:
-        if idx != 0:
-            return None       # an earlier use of this step went without: stay on that path
-        st = [ops.backward_weight_winograd_workspace(ddesc, xcs, expect, x.device), 0, _desc_key(ddesc, xcs), ddesc, xcs, ycs,
-              expect, [False] * expect]
-        w._t2v_wg_state = st
-    if len(st) < 8 or st[2] != _desc_key(ddesc, xcs):
-        return None
-    return st[0], expect, expect - 1 - idx
-
-
-def _kept_winograd_wgrad(w, dc, fdesc, kept, slot=None, info=None, lazy_dc=None):
-    """backward side of _keep_v_slot: A dy A^T of this node's image into ITS slot; the node that completes the set -- every
-    use the forward pass counted has come back -- zeroes the slots nobody filled (a step with fewer uses than expected)
-    and runs the one reduction.  lazy_dc = (conv output, gradient behind the norm, mean_rstd, gamma, beta, relu, sums)
-    instead of dc: the gradient in front of the norm is formed inside the transform."""
-    ws, total, k = kept
-    st = w._t2v_wg_state
-    assert st is not None and st[0] is ws and not st[7][k]
-    if info is not None:
-        info[:] = [ws, total, k]
-    if lazy_dc is not None:
-        ops.conv2d_backward_weight_winograd_dy_norm(*lazy_dc, fdesc, ws, total, k, st[4])
-    else:
-        ops.conv2d_backward_weight_winograd_dy(dc, fdesc, ws, total, k, st[4])
-    st[7][k] = True
-    st[1] += 1
-    last = st[1] == min(getattr(w, "_t2v_wg_images", 0), total)
-    dw = None
-    if last:
-        _zero_unfilled_slots(st)
-        if slot is not None:
-            with (wgrad_fork(ws) if wgrad_stream_on(ws) else contextlib.nullcontext()):
-                ops.conv2d_backward_weight_winograd_reduce(fdesc, ws, total, st[4], st[5], out=slot.view, accumulate=slot.filled)
-            slot.filled = True
-        else:
-            dw = ops.conv2d_backward_weight_winograd_reduce(fdesc, ws, total, st[4], st[5])
-        w._t2v_wg_state, w._t2v_wg_images = None, 0
-    if slot is not None:
-        slot.owner.node_done(slot)
-    return dw
-
-
-def _zero_unfilled_slots(st):
-    """slots of a kept-V workspace whose A dy A^T never came (and whose V may never have been written): zero both -- a zero
-    image contributes nothing, whatever bit pattern the allocation held would"""
-    ws, fdesc, xcs, total, filled = st[0], st[3], st[4], st[6], st[7]
-    if all(filled):
-        return
-    tp = ops.winograd_tile_rows(fdesc)
-    nv = 36 * total * tp * xcs
-    v = ws[:nv].view(36, total, tp * xcs)
-    md = ws[nv:nv + 36 * total * tp * fdesc.Cout].view(36, total, tp * fdesc.Cout)
-    for k, f in enumerate(filled):
-        if not f:
-            v[:, k].zero_()
-            md[:, k].zero_()
-
-
-def _batched_winograd_wgrad(w, x, dc, fdesc, slot=None, info=None):
-    """Weight gradient of one use of a layer whose forward counted `w._t2v_wg_images` images in this graph: the
-    images are transformed into their slots of a workspace kept on the weight; the node that brings the last ones
-    runs the single reduction over all of them and returns dW, the earlier ones return None (a zero gradient --
-    autograd sums the nodes' results).  One K = images x tiles reduction instead of one short one per frame."""
-    total = getattr(w, "_t2v_wg_images", 0)
-    st0 = getattr(w, "_t2v_wg_state", None)
-    if st0 is not None and len(st0) >= 8:
-        total = 0     # this step's workspace belongs to the uses that kept their V (_keep_v_slot); this one did not
-    if total < x.shape[0]:     # no count on this object: reduce on the spot
-        if slot is not None:
-            with (wgrad_fork(x, dc) if wgrad_stream_on(x) else contextlib.nullcontext()):
-                ops.conv2d_backward_weight_winograd(x, dc, fdesc, accumulate_into=slot.view if slot.filled else None,
-                                                    out=slot.view)
-            slot.filled = True
-            slot.owner.node_done(slot)
-            return None
-        return ops.conv2d_backward_weight_winograd(x, dc, fdesc)
-    st = getattr(w, "_t2v_wg_state", None)
-    if st is None:
-        st = [ops.backward_weight_winograd_workspace(fdesc, x.shape[-1], total, x.device), 0, _desc_key(fdesc, x.shape[-1]),
-              fdesc, x.shape[-1], dc.shape[-1]]
-        w._t2v_wg_state = st
-    assert st[2] == _desc_key(fdesc, x.shape[-1]), "one layer, two geometries in one step: set T2V_WGRAD_BATCH=0"
-    ws, done = st[0], st[1]
-    if info is not None:      # where this node's A dy A^T sits: the data gradient reads it too (transposed algorithm)
-        info[:] = [ws, total, done]
-    last = done + x.shape[0] == total
-    if slot is not None:     # the reduction writes (adds to) the parameter's bucket slot; every node counts as delivered
-        if wgrad_stream_on(x):
-            # transforms here (the data gradient of this node reads A dy A^T), the reduction over all slots on the side
-            ops.conv2d_backward_weight_winograd_stages(x, dc, fdesc, ws, total, done, False)
-            if last:
-                with wgrad_fork(ws):
-                    ops.conv2d_backward_weight_winograd_reduce(fdesc, ws, total, x.shape[-1], dc.shape[-1], out=slot.view,
-                                                               accumulate=slot.filled)
-        else:
-            ops.conv2d_backward_weight_winograd_stages(x, dc, fdesc, ws, total, done, last, out=slot.view,
-                                                       accumulate=slot.filled)
-        dw = None
-        if last:
-            slot.filled = True
-    else:
-        dw = ops.conv2d_backward_weight_winograd_stages(x, dc, fdesc, ws, total, done, last)
-    if last:
-        w._t2v_wg_state, w._t2v_wg_images = None, 0
-    else:
-        st[1] = done + x.shape[0]
-    if slot is not None:
-        slot.owner.node_done(slot)
-    return dw
-
-
-def flush_pending_weight_gradients(params, grads):
-    """After the backward pass: a layer whose forward counted more images than its backward nodes delivered (part of
-    the graph fed no loss -- e.g. the flow head of a raw-only first frame when no flow loss is on) has transformed
-    slots waiting for a reduction that no node will run.  Reduce what is there: the slots that were never filled are
-    zeroed (a zero image contributes nothing) and the reduction runs over the whole workspace.  Returns `grads` with
-    those gradients filled in."""
-    out = list(grads)
-    wgrad_join()
-    if params and params[0].is_cuda:
-        side_gemm_hint()       # (this thread: the backward nodes set theirs on the autograd engine's)
-    for i, p in enumerate(params):
-        half = getattr(p, "_t2v_dw_stash", None)
-        if half is not None:        # a layer whose remaining uses never came back: reduce the ones that did
-            dw = _reduce_stashed(half[1:], half[0], grad_slot(p), from_node=False)
-            if dw is not None:
-                out[i] = dw if out[i] is None else out[i] + dw
-        p._t2v_dw_stash, p._t2v_dw_uses = None, 0
-        st = getattr(p, "_t2v_wg_state", None)
-        if st is None:
-            continue
-        if len(st) >= 8:      # kept V (_keep_v_slot): the slots that did come back, the others zeroed
-            if st[1] > 0:
-                _zero_unfilled_slots(st)
-                ws, fdesc, xcs, dycs, total = st[0], st[3], st[4], st[5], st[6]
-                sl = grad_slot(p)
-                if sl is not None:
-                    ops.conv2d_backward_weight_winograd_reduce(fdesc, ws, total, xcs, dycs, out=sl.view, accumulate=sl.filled)
-                    sl.filled = True
-                else:
-                    dw = ops.conv2d_backward_weight_winograd_reduce(fdesc, ws, total, xcs, dycs)
-                    out[i] = dw if out[i] is None else out[i] + dw
-            p._t2v_wg_state, p._t2v_wg_images = None, 0
-            continue
-        ws, done, _, fdesc, xcs, dycs = st
-        total = p._t2v_wg_images
-        if done > 0:
-            tp = ops.winograd_tile_rows(fdesc)      # slot pitch of the batch-wide tile lists
-            nv = 36 * total * tp * xcs
-            ws[:nv].view(36, total, tp * xcs)[:, done:].zero_()
-            # (their A dy A^T slots too: 0 x whatever the allocation held is not 0 for a NaN / Inf bit pattern)
-            ws[nv:nv + 36 * total * tp * fdesc.Cout].view(36, total, tp * fdesc.Cout)[:, done:].zero_()
-            sl = grad_slot(p)
-            if sl is not None:
-                ops.conv2d_backward_weight_winograd_reduce(fdesc, ws, total, xcs, dycs, out=sl.view, accumulate=sl.filled)
-                sl.filled = True
-            else:
-                dw = ops.conv2d_backward_weight_winograd_reduce(fdesc, ws, total, xcs, dycs)
-                out[i] = dw if out[i] is None else out[i] + dw
-        p._t2v_wg_state, p._t2v_wg_images = None, 0
-    return out
-
-
 BN_MOMENTUM = 0.1     # nn.BatchNorm2d default ($SP/torch/nn/modules/batchnorm.py:16)
 _BN_UPDATES = [1]     # running-statistics updates per forward (a forward that stands for two upstream forwards: 2)
 _NO_PARAM_GRAD = set()   # ids of parameters whose gradients the backward pass under way must not produce
@@ -521,7 +59,7 @@ def input_gradients_off():
 def param_gradients_off(params):
     """Scope of a backward pass that runs THROUGH layers whose parameters belong to another loss: their nodes only
     propagate the data gradient (no weight-gradient kernels, nothing delivered to their gradient slots)."""
-    ids = {id(getattr(p, "_t2v_owner", p)) for p in params}
+    ids = {id(owner(p)) for p in params}
     _NO_PARAM_GRAD.update(ids)
     try:
         yield
@@ -542,13 +80,13 @@ def bn_updates(n):
 def running_stats(gamma, create=True):
     """[running_mean, running_var, num_batches_tracked] of the BatchNorm2d whose weight is `gamma` (kept on the parameter
     object; created at torch's initial values 0 / 1 / 0)."""
-    owner = getattr(gamma, "_t2v_owner", gamma)
-    rs = getattr(owner, "_t2v_running", None)
-    if rs is None and create:
-        rs = [torch.zeros(owner.numel(), dtype=torch.float32, device=owner.device),
-              torch.ones(owner.numel(), dtype=torch.float32, device=owner.device), 0]
-        owner._t2v_running = rs
-    return rs
+    st = param_state(gamma, create)
+    if st is None:
+        return None
+    if st.running is None and create:
+        st.running = [torch.zeros(gamma.numel(), dtype=torch.float32, device=gamma.device),
+                      torch.ones(gamma.numel(), dtype=torch.float32, device=gamma.device), 0]
+    return st.running
 
 
 def running_update_args(gamma, n, times=None):
@@ -578,8 +116,130 @@ def _zeros(n, device):
     return z
 
 
-def _desc_key(d, xcs):
-    return (d.H, d.W, d.Cin, d.Cout, d.kH, d.stride, d.pad, d.pad_mode, d.transposed, d.output_padding, d.algo, xcs)
+# how a node makes its weight gradient (ConvMeta.wgrad)
+WGRAD_DIRECT = 0                # the direct kernel (several uses of one layer in one launch: _paired_direct_wgrad)
+WGRAD_WINOGRAD = 1              # in the Winograd domain, this node alone
+WGRAD_WINOGRAD_COLLECTED = 2    # in the Winograd domain, counted on the weight: one reduction over every use of the step
+
+
+# What _ConvBlock.forward leaves for its backward node.  ddesc: the layer's geometry with the direct algorithm (the weight- and
+# data-gradient kernels' descriptor);  need_dx: 0 / 1 / 2 (an input layer: input_gradients_off);  mrs: the norm's (mean, rstd)
+# per image or per pass;  wgrad: WGRAD_*;  kept: (workspace, slots, slot) where forward kept its input transform, or None
+ConvMeta = collections.namedtuple("ConvMeta", "desc ddesc norm relu act need_dx mrs affine wgrad slope groups pt_skip kept")
+# The gradient in front of a norm that is not written out: the norm backward has delivered its two sums, the one reader -- the
+# weight gradient's transform of dy -- forms it per loaded element (ops.conv2d_backward_weight_winograd_dy_norm's leading arguments)
+LazyDc = collections.namedtuple("LazyDc", "c dy mean_rstd gamma beta relu sums")
+
+
+def _norm_adjoint(m, c, dy, y_act, gamma, beta, want_affine, sl_g, sl_bt, lazy, g0, gB, img0):
+    """dy behind act(norm(.)) -> (dc in front of it, or None with a LazyDc in its place; d gamma; d beta).  The affine
+    gradients are delivered by the norm backward's final pass where both have bucket slots (-> None)."""
+    both = sl_g is not None and sl_bt is not None
+    dgamma = dbeta = None
+
+    def norm_backward(ci, dyi, mr, **kw):
+        nonlocal dgamma, dbeta
+        into = None
+        if both:
+            into = (sl_bt.view, sl_g.view, not sl_g.filled)
+            sl_g.filled = sl_bt.filled = True
+        dci, sums = ops.instance_norm_backward(ci, dyi, mr, gamma, beta, m.relu, affine_into=into, **kw)
+        if want_affine and not both:       # [C,2] = (sum g, sum g*xhat) -> d beta, d gamma
+            db_, dg_ = sums.t().contiguous().unbind(0)
+            dbeta = db_ if dbeta is None else dbeta + db_
+            dgamma = dg_ if dgamma is None else dgamma + dg_
+        return dci, sums
+
+    lazy_dc = None
+    if lazy:
+        _, sums = norm_backward(c[0], dy[0], m.mrs[0], sums_only=True)
+        dc, lazy_dc = None, LazyDc(c[0], dy[0], m.mrs[0], gamma, beta, m.relu, sums)
+    elif m.norm is None:
+        # (act_backward's mode 2 is a plain sigmoid; the fused flow / weight head is its mode 4)
+        dc = ops.act_backward(dy, y_act, 4 if m.act == ops.ACT_FLOW_W else m.act, m.slope) if m.act != ops.ACT_NONE else dy
+    elif m.norm == "batch" and m.groups > 1:
+        dc = torch.empty_like(c)
+        for gi in range(g0, m.groups):       # statistics per pass: the norm's adjoint per pass
+            sl = slice((gi - g0) * gB, (gi - g0 + 1) * gB)
+            norm_backward(c[sl], dy[sl], m.mrs[gi], out=dc[sl])
+    elif m.norm == "batch":
+        dc, _ = norm_backward(c, dy, m.mrs[0])
+    else:
+        dc = torch.empty_like(c)
+        for i in range(c.shape[0]):
+            norm_backward(c[i], dy[i], m.mrs[img0 + i], out=dc[i])
+    if both:
+        deliver(sl_g)
+        deliver(sl_bt)
+    return dc, lazy_dc, dgamma, dbeta
+
+
+def _bias_gradient(m, dc, slot, device):
+    """a bias in front of a norm layer has an exactly zero gradient (the norm removes the channel mean)"""
+    C = m.desc.Cout
+    if m.norm is not None:
+        if slot is None:
+            return _zeros(C, device)
+        deliver(slot, zero=True)
+        return None
+
+    def launch(out, accumulate):
+        if out is None:
+            return ops.channel_sum(dc, C)
+        if accumulate:
+            _acc(out, ops.channel_sum(dc, C), False)
+        else:
+            ops.channel_sum(dc, C, out=out)
+    return deliver_into(slot, (dc,), launch)       # (off the dy -> dx chain too)
+
+
+def _weight_gradient(m, w, x, dc, lazy_dc, slot):
+    """-> (dW, or None: delivered into `slot` / left to the layer's last node; where the Winograd-domain collection holds this
+    node's A dy A^T, or None)"""
+    if m.wgrad == WGRAD_WINOGRAD_COLLECTED:
+        if m.kept is not None:
+            return _kept_winograd_wgrad(w, dc, m.ddesc, m.kept, slot, lazy_dc)
+        return _batched_winograd_wgrad(w, x, dc, m.ddesc, slot)
+    if m.wgrad == WGRAD_WINOGRAD:
+        return winograd_weight_gradient(x, dc, m.ddesc, slot), None
+    paired, dw = _paired_direct_wgrad(w, x, dc, m.ddesc, slot)
+    if not paired:
+        dw = deliver_direct(slot, (x, dc), lambda: direct_weight_gradient(x, dc, m.ddesc), m.ddesc, x.shape[-1])
+    return dw, None
+
+
+def _data_gradient(m, w, x, x_full, img0, dc, ycs, where):
+    """dx of the images `x` = x_full[img0:] (the leading ones carry no gradient: exact zeros).  where: the weight gradient
+    has just put A dy A^T of these images into its workspace and the transposed Winograd algorithm has the shape."""
+    fdesc, xcs, B = m.ddesc, x.shape[-1], x.shape[0]
+    if where is not None:
+        # The data gradient by the TRANSPOSED Winograd algorithm reads A dy A^T from there -- U^T dM on the layer's own 256
+        # tiles instead of the full-correlation form's 289 -> 320, no second transform of dy, no flipped filter transform
+        ws, total, first = where
+        # ... and where the fixed-grid GEMM has its [K][N] form for the shape, U^T is the forward pass's own packing read in
+        # place (T2V_DGRAD_FORWARD_WEIGHTS=0: the transposed copy, same bits)
+        fw = switch("T2V_DGRAD_FORWARD_WEIGHTS") and ops.backward_data_winograd_takes_forward_weights(fdesc, xcs, ycs)
+        if fw:
+            # (the forward pass ran this layer as F(4x4) and holds that packing under this key)
+            f4 = ops.with_algo(fdesc, ops.ALGO_WINOGRAD_F4)
+            ut = cached_pack(w, ("fwd",) + _desc_key(f4, xcs), lambda: ops.pack_conv_weight(w.detach().contiguous(), f4, xcs))
+        else:
+            ut = cached_pack(w, ("dgradT",) + _desc_key(fdesc, xcs), lambda: ops.pack_conv_weight_transposed(w.detach(), fdesc, xcs))
+        dx = torch.empty_like(x)
+        for i in range(B):
+            ops.conv2d_backward_data_winograd(fdesc, total, first + i, ws, xcs, ut, out=dx[i], forward_weights=fw)
+        return dx
+    dg = ConvDataGrad(fdesc)
+    dg.packed = cached_pack(w, ("dgrad",) + _desc_key(fdesc, xcs), lambda: dg.refresh(w.detach()).packed)
+    if ops.round_up(fdesc.Cin, 4) == xcs:
+        dx = torch.empty_like(x_full)
+        if img0:
+            ops.zero_(dx[:img0])
+        dg.batch(dc, dx[img0:])
+    else:   # x carries more channel storage than the layer reads: zero gradient there
+        dx = torch.zeros_like(x_full)
+        dx[img0:, ..., :ops.round_up(fdesc.Cin, 4)] = torch.stack([dg(dc[i]) for i in range(B)])
+    return dx
 
 
 class _ConvBlock(torch.autograd.Function):
@@ -624,9 +284,9 @@ class _ConvBlock(torch.autograd.Function):
         mrs = None
         # weight gradient in the Winograd domain where the forward took F(4x4,3x3) (a quarter of the FLOPs)
         wino_wgrad = fdesc.algo == ops.ALGO_WINOGRAD_F4 and ops.backward_weight_winograd_supported(ddesc, xcs, ycs) \
-            and os.environ.get("T2V_WGRAD_WINOGRAD", "1") != "0"
+            and switch("T2V_WGRAD_WINOGRAD")
         # ... whose workspace, from the layer's second step on, takes this conv's input transform right now (_keep_v_slot)
-        kept = _keep_v_slot(w, x, ddesc, xcs, ycs) if (wino_wgrad and ctx.needs_input_grad[1] and _WG_BATCH[0]) else None
+        kept = _keep_v_slot(w, x, ddesc, xcs, ycs) if (wino_wgrad and ctx.needs_input_grad[1] and STEP.wg_batch) else None
         # (a batch of a direct-algorithm layer -- the discriminators' -- is ONE launch: ops.conv2d_auto_batch)
         if norm is None:
             if kept is not None:
@@ -670,185 +330,64 @@ class _ConvBlock(torch.autograd.Function):
             y = y + res   # residual add (plumbing-level elementwise; its gradient is the identity)
         # every use of the layer in this graph (one per frame of the clip) is counted on the weight: their Winograd-
         # domain gradients are reduced together by the last backward node to run (T2V_WGRAD_BATCH=0: one by one)
-        if wino_wgrad and w.requires_grad and _WG_BATCH[0]:
-            w._t2v_wg_images = getattr(w, "_t2v_wg_images", 0) + B
-            w._t2v_wg_seen = getattr(w, "_t2v_wg_seen", 0) + B
-            wino_wgrad = 2
-        elif not wino_wgrad and w.requires_grad and _DW_PAIR[0] and \
+        wgrad = WGRAD_WINOGRAD if wino_wgrad else WGRAD_DIRECT
+        if wino_wgrad and w.requires_grad and STEP.wg_batch:
+            st = param_state(w)
+            st.images += B
+            st.seen += B
+            wgrad = WGRAD_WINOGRAD_COLLECTED
+        elif not wino_wgrad and w.requires_grad and STEP.dw_pair and \
                 (B > 1 or ops.backward_weight_strided_supported(ddesc, xcs, ycs)):
-            w._t2v_dw_uses = getattr(w, "_t2v_dw_uses", 0) + 1      # (two or more uses: _paired_direct_wgrad)
+            param_state(w).dw_uses += 1      # (two or more uses: _paired_direct_wgrad)
         for prm in (w, b, gamma, beta):
             expect_gradient(prm)
         # (an input nobody differentiates -- the discriminators' real pass -- needs no data-gradient conv)
         need_dx = int(need_dx) if (need_dx and ctx.needs_input_grad[0]) else 0      # 2: an input layer (input_gradients_off)
-        ctx.meta = (desc, ddesc, norm, relu, act, need_dx, mrs, gamma is not None, wino_wgrad, slope)
-        ctx.groups, ctx.pt_skip = groups, int(pt_skip)
-        ctx.kept = kept
+        ctx.meta = ConvMeta(desc, ddesc, norm, relu, act, need_dx, mrs, gamma is not None, wgrad, slope, groups, int(pt_skip), kept)
         ctx.save_for_backward(x, w, c, gamma, beta, y if (norm is None and act != ops.ACT_NONE) else None, b)
         return y
 
     @staticmethod
     def backward(ctx, dy):
-        desc, fdesc, norm, relu, act, need_dx, mrs, affine, wino_wgrad, slope = ctx.meta
+        m = ctx.meta
         x, w, c, gamma, beta, y_act, b = ctx.saved_tensors
         dy = dy.contiguous()
-        dgamma = dbeta = None
         if dy.is_cuda:
             side_gemm_hint()
-        # a backward pass that only passes THROUGH this layer (param_gradients_off): data gradient only
         want = [bool(v) for v in ctx.needs_input_grad]
-        if need_dx == 2 and _NO_INPUT_DX[0]:
-            need_dx = 0
-        groups, g0, img0, x_full = ctx.groups, 0, 0, x
-        gB = x.shape[0] // groups
-        if _NO_PARAM_GRAD and id(getattr(w, "_t2v_owner", w)) in _NO_PARAM_GRAD:
+        need_dx = 0 if (m.need_dx == 2 and _NO_INPUT_DX[0]) else m.need_dx
+        g0, img0, x_full = 0, 0, x
+        gB = x.shape[0] // m.groups
+        # a backward pass that only passes THROUGH this layer (param_gradients_off): data gradient only
+        if _NO_PARAM_GRAD and id(owner(w)) in _NO_PARAM_GRAD:
             want[1] = want[2] = want[3] = want[4] = False
-            if ctx.pt_skip:
+            if m.pt_skip:
                 # ... and only through the passes the loss reaches: the leading `pt_skip` images (the real pass) carry no
                 # gradient in this backward -- their rows of dy are never read, their rows of dx are exact zeros
-                img0 = ctx.pt_skip
-                assert not wino_wgrad and 0 < img0 < x.shape[0] and (groups == 1 or img0 % gB == 0)
-                g0 = img0 // gB if groups > 1 else 0
+                img0 = m.pt_skip
+                assert m.wgrad == WGRAD_DIRECT and 0 < img0 < x.shape[0] and (m.groups == 1 or img0 % gB == 0)
+                g0 = img0 // gB if m.groups > 1 else 0
                 x, c, dy = x[img0:], c[img0:], dy[img0:]
                 y_act = y_act[img0:] if y_act is not None else None
-        B = x.shape[0]
         # parameters with a bucket slot get their gradients delivered in place (and None goes back to autograd)
         sl_w = grad_slot(w) if want[1] else None
         sl_b = grad_slot(b) if want[2] else None
-        sl_g = grad_slot(gamma) if (affine and want[3]) else None
-        sl_bt = grad_slot(beta) if (affine and want[4]) else None
-        both = sl_g is not None and sl_bt is not None
-
-        def into_slots():           # both affine gradients have bucket slots: the norm backward's final pass fills them
-            if not (both and affine and (want[3] or want[4])):
-                return None
-            first = not sl_g.filled
-            sl_g.filled = sl_bt.filled = True
-            return (sl_bt.view, sl_g.view, first)
-
-        def affine_sums(sums):       # [C,2] = (sum g, sum g*xhat) -> d beta, d gamma
-            nonlocal dbeta, dgamma
-            if both:
-                return               # (delivered by the kernel: into_slots)
-            else:
-                db_, dg_ = sums.t().contiguous().unbind(0)
-                dbeta = db_ if dbeta is None else dbeta + db_
-                dgamma = dg_ if dgamma is None else dgamma + dg_
-
+        sl_g = grad_slot(gamma) if (m.affine and want[3]) else None
+        sl_bt = grad_slot(beta) if (m.affine and want[4]) else None
         # Where this node's gradient in front of the norm would be read by nothing but the transform A dy A^T (the weight
         # gradient's workspace holds V already, the data gradient takes A dy A^T from there), it is not written at all: the
         # norm backward delivers its two sums, the transform forms the gradient per loaded element (T2V_DY_NORM_FUSED=0: off)
-        dgrad_t = wino_wgrad == 2 and os.environ.get("T2V_DGRAD_TRANSPOSED", "1") != "0" and \
-            ops.backward_data_winograd_supported(fdesc, x.shape[-1], c.shape[-1])
-        lazy_dc = None
-        if norm is not None and B == 1 and wino_wgrad == 2 and want[1] and ctx.kept is not None and (dgrad_t or not need_dx) \
-                and os.environ.get("T2V_DY_NORM_FUSED", "1") != "0":
-            _, sums = ops.instance_norm_backward(c[0], dy[0], mrs[0], gamma, beta, relu, affine_into=into_slots(), sums_only=True)
-            if affine and (want[3] or want[4]):
-                affine_sums(sums)
-            lazy_dc = (c[0], dy[0], mrs[0], gamma, beta, relu, sums)
-            dc = None
-        elif norm is None:
-            # (act_backward's mode 2 is a plain sigmoid; the fused flow / weight head is its mode 4)
-            dc = ops.act_backward(dy, y_act, 4 if act == ops.ACT_FLOW_W else act, slope) if act != ops.ACT_NONE else dy
-        elif norm == "batch" and groups > 1:
-            dc = torch.empty_like(c)
-            for gi in range(g0, groups):       # statistics per pass: the norm's adjoint per pass
-                sl = slice((gi - g0) * gB, (gi - g0 + 1) * gB)
-                _, s_i = ops.instance_norm_backward(c[sl], dy[sl], mrs[gi], gamma, beta, relu, out=dc[sl], affine_into=into_slots())
-                if affine and (want[3] or want[4]):
-                    affine_sums(s_i)
-        elif norm == "batch":
-            dc, sums = ops.instance_norm_backward(c, dy, mrs[0], gamma, beta, relu, affine_into=into_slots())
-            if affine and (want[3] or want[4]):
-                affine_sums(sums)
-        else:
-            dc = torch.empty_like(c)
-            for i in range(B):
-                _, s_i = ops.instance_norm_backward(c[i], dy[i], mrs[img0 + i], gamma, beta, relu, out=dc[i], affine_into=into_slots())
-                if affine and (want[3] or want[4]):
-                    affine_sums(s_i)
-        if both:
-            sl_g.owner.node_done(sl_g)
-            sl_bt.owner.node_done(sl_bt)
-        # a bias in front of a norm layer has an exactly zero gradient (the norm removes the channel mean)
-        db = None
-        if want[2]:
-            if sl_b is not None:
-                if norm is None:
-                    with (wgrad_fork(dc) if wgrad_stream_on(dc) else contextlib.nullcontext()):   # (off the dy -> dx chain too)
-                        if sl_b.filled:
-                            _acc(sl_b.view, ops.channel_sum(dc, desc.Cout), False)
-                        else:
-                            ops.channel_sum(dc, desc.Cout, out=sl_b.view)
-                    sl_b.filled = True
-                    sl_b.owner.node_done(sl_b)      # (outside the scope: a bucket launch must see the MAIN stream as current)
-                else:
-                    deliver(sl_b, zero=True)
-            else:
-                db = ops.channel_sum(dc, desc.Cout) if norm is None else _zeros(desc.Cout, x.device)
-        if not want[1]:      # frozen weights (the VGG19 feature extractor) / a pass-through backward: data gradient only
-            dw = None
-        elif wino_wgrad == 2:
-            wg_info = []
-            if ctx.kept is not None:
-                dw = _kept_winograd_wgrad(w, dc, fdesc, ctx.kept, sl_w, wg_info, lazy_dc)
-            else:
-                dw = _batched_winograd_wgrad(w, x, dc, fdesc, sl_w, wg_info)
-        elif wino_wgrad:
-            if sl_w is not None:
-                with (wgrad_fork(x, dc) if wgrad_stream_on(x) else contextlib.nullcontext()):
-                    ops.conv2d_backward_weight_winograd(x, dc, fdesc, accumulate_into=sl_w.view if sl_w.filled else None,
-                                                        out=sl_w.view)
-                sl_w.filled = True
-                sl_w.owner.node_done(sl_w)
-                dw = None
-            else:
-                dw = ops.conv2d_backward_weight_winograd(x, dc, fdesc)
-        else:
-            paired, dw = _paired_direct_wgrad(w, x, dc, fdesc, sl_w)
-            if paired:
-                pass
-            elif sl_w is not None:
-                with (wgrad_fork(x, dc) if wgrad_stream_on(x) else contextlib.nullcontext()):
-                    dwp = direct_weight_gradient(x, dc, fdesc)
-                    ops.unpack_conv_weight_into(dwp, fdesc, x.shape[-1], sl_w.view, sl_w.filled)
-                sl_w.filled = True
-                sl_w.owner.node_done(sl_w)
-                dw = None
-            else:
-                dw = ops.unpack_conv_weight(direct_weight_gradient(x, dc, fdesc), fdesc, x.shape[-1])
+        dgrad_t = m.wgrad == WGRAD_WINOGRAD_COLLECTED and ops.backward_data_winograd_supported(m.ddesc, x.shape[-1], c.shape[-1])
+        lazy = m.norm is not None and x.shape[0] == 1 and m.wgrad == WGRAD_WINOGRAD_COLLECTED and want[1] and m.kept is not None \
+            and (dgrad_t or not need_dx) and switch("T2V_DY_NORM_FUSED")
+        dc, lazy_dc, dgamma, dbeta = _norm_adjoint(m, c, dy, y_act, gamma, beta, m.affine and (want[3] or want[4]), sl_g, sl_bt,
+                                                   lazy, g0, gB, img0)
+        db = _bias_gradient(m, dc, sl_b, x.device) if want[2] else None
+        # (frozen weights -- the VGG19 feature extractor -- / a pass-through backward: data gradient only)
+        dw, where = _weight_gradient(m, w, x, dc, lazy_dc, sl_w) if want[1] else (None, None)
         dx = None
-        xcs_ = x.shape[-1]
-        if need_dx and wino_wgrad == 2 and want[1] and len(wg_info) == 3 and dgrad_t:
-            # The weight gradient has just put A dy A^T of these images into its workspace: the data gradient by the
-            # TRANSPOSED Winograd algorithm reads it from there -- U^T dM on the layer's own 256 tiles instead of the
-            # full-correlation form's 289 -> 320, no second transform of dy, no flipped filter transform
-            ws_, total_, done_ = wg_info
-            # ... and where the fixed-grid GEMM has its [K][N] form for the shape, U^T is the forward pass's own packing read in
-            # place (T2V_DGRAD_FORWARD_WEIGHTS=0: the transposed copy, same bits)
-            fw = os.environ.get("T2V_DGRAD_FORWARD_WEIGHTS", "1") != "0" \
-                and ops.backward_data_winograd_takes_forward_weights(fdesc, xcs_, c.shape[-1])
-            if fw:
-                # (wino_wgrad: the forward pass ran this layer as F(4x4) and holds that packing under this key)
-                f4 = ops.with_algo(fdesc, ops.ALGO_WINOGRAD_F4)
-                ut = cached_pack(w, ("fwd",) + _desc_key(f4, xcs_), lambda: ops.pack_conv_weight(w.detach().contiguous(), f4, xcs_))
-            else:
-                ut = cached_pack(w, ("dgradT",) + _desc_key(fdesc, xcs_), lambda: ops.pack_conv_weight_transposed(w.detach(), fdesc, xcs_))
-            dx = torch.empty_like(x)
-            for i in range(B):
-                ops.conv2d_backward_data_winograd(fdesc, total_, done_ + i, ws_, xcs_, ut, out=dx[i], forward_weights=fw)
-        elif need_dx:
-            dg = ConvDataGrad(fdesc)
-            dg.packed = cached_pack(w, ("dgrad",) + _desc_key(fdesc, x.shape[-1]), lambda: dg.refresh(w.detach()).packed)
-            if ops.round_up(fdesc.Cin, 4) == x.shape[-1]:
-                dx = torch.empty_like(x_full)
-                if img0:
-                    ops.zero_(dx[:img0])
-                dg.batch(dc, dx[img0:])
-            else:   # x carries more channel storage than the layer reads: zero gradient there
-                dx = torch.zeros_like(x_full)
-                dx[img0:, ..., :ops.round_up(fdesc.Cin, 4)] = torch.stack([dg(dc[i]) for i in range(B)])
+        if need_dx:
+            dx = _data_gradient(m, w, x, x_full, img0, dc, c.shape[-1], where if dgrad_t else None)
         elif img0:
             raise RuntimeError("conv_block: pt_skip is for layers with a data gradient")
         return (dx, dw, db, dgamma, dbeta, (dy if ctx.needs_input_grad[5] else None)) + (None,) * 9
@@ -1430,7 +969,7 @@ class FusedAdam:
         """One launch for all tensors (T2V_ADAM_MULTI=0: one launch per tensor).  Every parameter keeps its own step
         count; a parameter without gradient is skipped, moments included."""
         import math
-        if os.environ.get("T2V_ADAM_MULTI", "1") == "0" or not self.params:
+        if not switch("T2V_ADAM_MULTI") or not self.params:
             for i, (p, m, v) in enumerate(zip(self.params, self.m, self.v)):
                 if p.grad is not None:
                     self.steps[i] += 1
@@ -1464,261 +1003,6 @@ class FusedAdam:
         # the pinned staging tables are reused by the next step: make sure this step's copies have been issued from them
         self._pending = (grads, torch.cuda.current_stream().record_event())
         prefetch_packs(self.params)
-
-
-def _acc(dst, src, overwrite):
-    """dst (+)= src on flat views: HIP kernel on device tensors; host tensors only occur in the gloo CPU tests of the
-    bucket bookkeeping (the trainer itself cannot exist without the GPU)"""
-    if dst.is_cuda:
-        ops.accumulate_(dst, src.contiguous().view(-1), overwrite=overwrite)
-    elif overwrite:
-        dst.view(-1).copy_(src.reshape(-1))
-    else:
-        dst.view(-1).add_(src.reshape(-1))
-
-
-def _zero(x):
-    ops.zero_(x) if x.is_cuda else x.zero_()
-
-
-def _scale(x, f):
-    ops.scale_(x, f) if x.is_cuda else x.mul_(f)
-
-
-class GradBuckets:
-    """Persistent flat gradient buckets of one optimiser's parameters + their data-parallel exchange.
-
-    Layout (static, identical on every rank): the parameters in REVERSE order -- backward reaches the last layers
-    first -- packed into buckets of <= bucket_mb; every parameter's gradient lives at a fixed slice of its bucket
-    (`GradSlot.view`, handed to Adam as p.grad).  During a train step the backward nodes deliver into the slots
-    (`deliver` / the accumulate flags of the weight-gradient kernels); when the last expected node of the last
-    parameter of a bucket has delivered, the bucket's collective is launched from inside the backward pass --
-    asynchronously on the process group's stream (RCCL over xGMI; gloo in the single-GPU tests), buckets strictly in
-    index order so that every rank issues the same sequence.  Replaces DataParallel's gradient reduce onto GPU 0 through
-    10 MiB coalesced copies + re-broadcast of the weights ($SP/torch/cuda/comm.py:24,76-86; nn/parallel/_functions.py)
-    and round 2's cat -> all_reduce -> divide -> copy-back (three extra passes over 1.1-1.5 GB per step): the bytes
-    on the wire are the gradients themselves, in place.
-
-    T2V_GRAD_RS_AG=1: reduce-scatter + all-gather per bucket instead of one all-reduce (what a ring all-reduce does
-    internally; lets a sharded optimiser step sit between the two halves later).  T2V_GRAD_BUCKET_MB overrides 64."""
-
-    def __init__(self, params, bucket_mb=None, name="", register=True):
-        """register=False: the parameters keep the gradient slots they have (a temporary set of buckets over parameters a
-        trainer owns must not take the trainer's slots away: ADVICE r3)"""
-        import torch.distributed as dist
-        self.params = list(params)
-        self.name = name
-        self.collecting = False
-        self.world = dist.get_world_size() if (dist.is_available() and dist.is_initialized()) else 1
-        # (T2V_TRAIN_FORCE_DIST=1 runs the collectives on a 1-rank group too: the RCCL path on a single GPU)
-        self.exchange = self.world > 1 or (os.environ.get("T2V_TRAIN_FORCE_DIST") == "1" and dist.is_available()
-                                            and dist.is_initialized())
-        self.rs_ag = os.environ.get("T2V_GRAD_RS_AG", "0") == "1"
-        if bucket_mb is None:
-            bucket_mb = float(os.environ.get("T2V_GRAD_BUCKET_MB", "64"))
-        limit = max(1, int(bucket_mb * (1 << 20) // 4))
-        pad = 256 * max(1, self.world)     # bucket sizes divisible by the world size (reduce-scatter shards) and 1 KiB
-        order = list(range(len(self.params)))[::-1]
-        bounds, members, off, cur, cur_n = [], [], 0, [], 0
-        for i in order:
-            n = self.params[i].numel()
-            if cur and cur_n + n > limit:
-                size = (cur_n + pad - 1) // pad * pad
-                bounds.append((off, off + size))
-                members.append(cur)
-                off += size
-                cur, cur_n = [], 0
-            cur.append((i, cur_n))
-            cur_n += n
-        if cur:
-            size = (cur_n + pad - 1) // pad * pad
-            bounds.append((off, off + size))
-            members.append(cur)
-            off += size
-        dev = self.params[0].device if self.params else "cpu"
-        self.flat = torch.zeros(off, dtype=torch.float32, device=dev)
-        self.bounds = bounds
-        self.slots = [None] * len(self.params)
-        self.bucket_of = [None] * len(self.params)
-        for bi, mem in enumerate(members):
-            for i, rel in mem:
-                p = self.params[i]
-                view = self.flat[bounds[bi][0] + rel: bounds[bi][0] + rel + p.numel()].view(p.shape)
-                self.slots[i] = GradSlot(self, bi, i, view)
-                if register:
-                    p._t2v_gslot = self.slots[i]
-                self.bucket_of[i] = bi
-        self.members = [[i for i, _ in mem] for mem in members]
-        self.nbytes = 0
-        self._works, self._open, self._launched = [], [], 0
-
-    # -- one train step -----------------------------------------------------------------------------
-    def begin_step(self):
-        for sl in self.slots:
-            sl.expect = sl.got = 0
-            sl.filled = False
-        self._main = torch.cuda.current_stream() if (self.params and self.params[0].is_cuda) else None
-        self._open = [len(m) for m in self.members]      # parameters of each bucket still waiting for nodes
-        self._done = [False] * len(self.params)
-        self._works, self._launched, self.nbytes = [], 0, 0
-        # T2V_GRAD_DIRECT=0: the backward nodes hand their gradients to autograd as before and absorb() copies the sums
-        # into the slots afterwards (one extra pass, no launch from inside the backward pass): the A/B baseline
-        self.collecting = os.environ.get("T2V_GRAD_DIRECT", "1") != "0"
-
-    def seal(self):
-        """The forward pass is over: parameters no node will deliver to (unused in this step) no longer hold their
-        bucket back."""
-        if not self.collecting:
-            return
-        for sl in self.slots:
-            if sl.expect == 0 and not self._done[sl.idx]:
-                self._done[sl.idx] = True
-                self._open[sl.bucket] -= 1
-        # (nothing is launched here: a launch from the first delivering node keeps the bucket order intact)
-
-    def node_done(self, sl):
-        sl.got += 1
-        if sl.got == sl.expect and not self._done[sl.idx]:
-            self._done[sl.idx] = True
-            self._open[sl.bucket] -= 1
-            self._launch_ready()
-
-    def _launch_ready(self):
-        """launch, in bucket order, every bucket whose parameters have all received their last expected gradient"""
-        while self._launched < len(self.bounds) and self._open[self._launched] == 0:
-            self._launch(self._launched)
-            self._launched += 1
-
-    def _launch(self, b):
-        # parameters no backward node reached contribute exact zeros (and get no optimiser step: see finish)
-        for i in self.members[b]:
-            if not self.slots[i].filled and not self.slots[i].zero_valid:
-                _zero(self.slots[i].view)
-        if not self.exchange:
-            return
-        import torch.distributed as dist
-        # The collective is ordered behind the stream it is issued on, and it needs the weight-gradient stream's kernels AND the
-        # current stream's (and the step's main stream's, when this node runs on another).  With weight gradients in flight it
-        # is issued FROM the weight-gradient stream, which first takes in what the other streams hold so far: the backward
-        # pass itself does not stop.  (Until round 6 the current stream joined the weight-gradient stream here, 36 times per
-        # step: the data-gradient chain waited for every layer's weight gradient, and the two queues of DESIGN 6b ran one
-        # after the other again whenever the exchange was on.)  T2V_EXCHANGE_FROM_SIDE=0: the join.
-        cur = torch.cuda.current_stream() if self.flat.is_cuda else None
-        side = _WG_SIDE["stream"] if (cur is not None and _WG_SIDE["pending"]
-                                      and os.environ.get("T2V_EXCHANGE_FROM_SIDE", "1") != "0") else None
-        if side is not None and side != cur:
-            side.wait_stream(cur)
-            if self._main is not None and cur != self._main:
-                side.wait_stream(self._main)
-            with torch.cuda.stream(side):
-                self._issue(b)
-            return
-        wgrad_join()
-        if self._main is not None and torch.cuda.current_stream() != self._main:
-            torch.cuda.current_stream().wait_stream(self._main)
-        self._issue(b)
-
-    def _issue(self, b):
-        import torch.distributed as dist
-        lo, hi = self.bounds[b]
-        buf = self.flat[lo:hi]
-        avg = dist.get_backend() == "nccl"       # RCCL averages in the collective; gloo sums (scaled in finish)
-        op = dist.ReduceOp.AVG if avg else dist.ReduceOp.SUM
-        if self.rs_ag:      # (also on a forced 1-rank group: the RCCL entry points run on device tensors)
-            shard = (hi - lo) // self.world
-            r = dist.get_rank()
-            mine = buf[r * shard:(r + 1) * shard]
-            if avg:     # RCCL: in-place reduce-scatter (output = this rank's shard of the input), then the all-gather,
-                w1 = dist.reduce_scatter_tensor(mine, buf, op=op, async_op=True)      # both stream-ordered
-                self._works.append((w1, None, None, None))
-                w2 = dist.all_gather_into_tensor(buf, mine, async_op=True)
-                self._works.append((w2, buf, avg, None))
-            else:       # gloo (tests): works are not ordered among themselves -- the all-gather is issued in finish()
-                out = torch.empty_like(mine)
-                w1 = dist.reduce_scatter_tensor(out, buf, op=op, async_op=True)
-                self._works.append((w1, buf, avg, (mine, out)))
-        else:
-            self._works.append((dist.all_reduce(buf, op=op, async_op=True), buf, avg, None))
-        self.nbytes += 4 * sum(self.params[i].numel() for i in self.members[b])     # payload (the padding travels too)
-
-    def absorb(self, grads):
-        """After autograd.grad: gradients that came back as tensors (parameters reached through torch-native plumbing,
-        e.g. the cat of the two flow-head convs; a flushed Winograd reduction) are added into their slots; then every
-        bucket not yet launched goes out, in order."""
-        wgrad_join()
-        for i, g in enumerate(grads):
-            if g is not None:
-                sl = self.slots[i]
-                _acc(sl.view, g, not sl.filled)
-                sl.filled = True
-        for b in range(self._launched, len(self.bounds)):
-            self._launch(b)
-        self._launched = len(self.bounds)
-        self.collecting = False
-
-    def finish(self):
-        """Wait for the collectives; p.grad = the slot (None where no rank-local node delivered: Adam then skips the
-        parameter, as torch 0.4.1's does).  Returns the bytes exchanged."""
-        import torch.distributed as dist
-        wgrad_join()
-        for work, buf, avg, shard in self._works:
-            work.wait()
-            if shard is not None:
-                shard[0].copy_(shard[1])
-                dist.all_gather_into_tensor(buf, shard[0].clone())
-            if buf is not None and not avg and self.world > 1:
-                _scale(buf, 1.0 / self.world)
-        self._works = []
-        for p, sl in zip(self.params, self.slots):
-            p.grad = sl.view if sl.filled else None
-        return self.nbytes
-
-    def presence(self):
-        """a checksum of WHICH parameters received gradients on this rank: must agree across ranks, or the replicas'
-        optimiser steps differ (Adam skips parameters without gradient)"""
-        return float(sum((k + 1) * (k + 7) for k, sl in enumerate(self.slots) if sl.filled) % 1000003)
-
-
-def check_presence_across_ranks(buckets, device):
-    """Every rank must have delivered gradients to the same parameters.  One tiny MAX / MIN all-reduce per step."""
-    import torch.distributed as dist
-    if not (dist.is_available() and dist.is_initialized()) or dist.get_world_size() == 1:
-        return
-    v = [b.presence() for b in buckets]
-    dev = device if dist.get_backend() == "nccl" else "cpu"
-    t = torch.tensor(v + [-x for x in v], dtype=torch.float64, device=dev)
-    dist.all_reduce(t, op=dist.ReduceOp.MAX)
-    t = t.cpu().tolist()
-    n = len(v)
-    if any(t[k] != -t[n + k] for k in range(n)):
-        raise RuntimeError("data-parallel ranks disagree on which parameters received gradients this step (checksums "
-                           "max %s / min %s): their optimiser steps would diverge" % (t[:n], [-x for x in t[n:]]))
-
-
-class GradientExchange:
-    """Stand-alone form for gradients that already sit in p.grad (tests, callers outside the trainer): the gradients
-    are moved into a temporary GradBuckets (one pass), exchanged bucket by bucket, and p.grad ends as the averaged slot."""
-
-    def __init__(self, params, bucket_mb=64):
-        ps = [p for p in params if p.grad is not None]
-        self.b = GradBuckets(ps, bucket_mb, register=False) if ps else None
-        if self.b is not None:
-            self.b.begin_step()
-            self.b.absorb([p.grad for p in ps])
-
-    def finish(self):
-        return self.b.finish() if self.b is not None else 0
-
-
-def allreduce_gradients_begin(params, bucket_mb=64):
-    return GradientExchange(params, bucket_mb)
-
-
-def allreduce_gradients(params, bucket_mb=64):
-    """Data-parallel gradient exchange of gradients already in p.grad: bucketed, averaged over ranks; returns the bytes
-    exchanged.  Replaces DataParallel's reduce-to-GPU-0 + re-broadcast: replicas are persistent, so
-    one collective per bucket is all the communication a step needs."""
-    return GradientExchange(params, bucket_mb).finish()
 
 
 # ------------------------------------------------------------------------------------------------
@@ -2001,9 +1285,9 @@ class Vid2VidTrainer:
         # stream they would stand in front of every bucket the generator's pass sends off (GradBuckets._launch orders a
         # collective behind that stream) -- the filler would hold the exchange up (measured with the join of that time:
         # 90.5 ms with the exchange against 82.1 without).  Two streams carry GEMMs from here on: one block per CU
-        if os.environ.get("T2V_TRAIN_SK_HINT", "1") != "0" and wgrad_stream_on(outputs[0]):
-            _WG_SIDE["gemm"] = True
-        _WG_SIDE["inline"] = True
+        if switch("T2V_TRAIN_SK_HINT") and wgrad_stream_on(outputs[0]):
+            STEP.gemm = True
+        STEP.inline = True
         try:
             with torch.cuda.stream(side), input_gradients_off():
                 for y, g in zip(outputs, seeds):
@@ -2014,7 +1298,7 @@ class Vid2VidTrainer:
                             raise RuntimeError("discriminator backward by hand: a node returned a gradient it should have delivered")
                         g, node = res[0], node.next_functions[0][0]
         finally:
-            _WG_SIDE["inline"] = False
+            STEP.inline = False
         side_gemm_hint()
         return side
 
@@ -2155,10 +1439,10 @@ class Vid2VidTrainer:
         # loss reaches D's parameters through it, G's loss reaches the frames through it with D's parameter gradients
         # switched off for that backward pass (param_gradients_off) -- the same values either way, a D forward less per
         # fake input.  The running statistics still move twice (upstream's two forwards).
-        shared = os.environ.get("T2V_D_SHARED_FWD", "1") != "0"
+        shared = switch("T2V_D_SHARED_FWD")
         # T2V_D_BATCHED=0: one launch per pass and per loss term, the scalar graph on autograd (the form this path replaced;
         # kept as its test twin)
-        batched = shared and os.environ.get("T2V_D_BATCHED", "1") != "0"
+        batched = shared and switch("T2V_D_BATCHED")
         self._shared_d = shared
         if batched:
             return self._train_step_batched(pose, real, face_boxes, prev, real_prev, flow_ref, conf_ref, first, fakes, raws, fws,
@@ -2300,13 +1584,14 @@ class Vid2VidTrainer:
                         print("continue_train: %s has no %s, keeping its initial value" % (path, k), flush=True)
                         continue
                     p.copy_(sd[k].to(p.device, torch.float32))
-                    p._t2v_packs = p._t2v_repack = p._t2v_pack_event = None
+                    st = param_state(p)
+                    st.packs = st.repack = None
                     if k.endswith(".weight") and p.dim() == 1 and k[:-len("weight")] + "running_mean" in sd:
                         base = k[:-len("weight")]
                         nbt = sd.get(base + "num_batches_tracked")
-                        p._t2v_running = [sd[base + "running_mean"].to(p.device, torch.float32).clone(),
-                                          sd[base + "running_var"].to(p.device, torch.float32).clone(),
-                                          int(nbt) if nbt is not None else 0]
+                        st.running = [sd[base + "running_mean"].to(p.device, torch.float32).clone(),
+                                      sd[base + "running_var"].to(p.device, torch.float32).clone(),
+                                      int(nbt) if nbt is not None else 0]
 
     def save(self, epoch_label, progress=None):
         """progress = (epoch, samples done in it): written to iter.txt beside the nets every time `latest` is saved, so
