@@ -53,6 +53,7 @@ void options_reload() {
     o.wgrad_combine = env_int("T2V_WGRAD_COMBINE", 1);
     o.wgrad_combine_max = env_int("T2V_WGRAD_COMBINE_MAX", 4);
     o.chain_lazy = env_int("T2V_CHAIN_LAZY", 1);
+    o.finalize_direct = env_int("T2V_FINALIZE_DIRECT", 1);
     o.streams = env_int("T2V_STREAMS", 0);
     o.conv_tile = env_int("T2V_CONV_TILE", 0);
     o.xcd_slices = env_int("T2V_XCD_SLICES", 1);

@@ -56,14 +56,87 @@ __device__ __forceinline__ void running_update(const RunningUpdate& ru, int c, f
     ru.var[c] = rv;
 }
 
+// The closing arithmetic of a finalize: pooled power sums -> (mean, rstd) of channel c, and the running statistics
+__device__ __forceinline__ void finalize_close(double s0, double s1, double s2, double sm2, float ref, int c, float eps,
+                                               float2* __restrict__ mean_rstd, const RunningUpdate& ru) {
+    const double mean_d = s1 / s0;
+    double m2 = sm2 + s2 - s1 * mean_d;
+    m2 = m2 > 0.0 ? m2 : 0.0;
+    const float var = (float)(m2 / s0);
+    const float2 mr = make_float2(ref + (float)mean_d, 1.0f / sqrtf(var + eps));
+    mean_rstd[c] = mr;
+    running_update(ru, c, mr, eps);
+}
+
+// The direct form, for nparts <= kFinSlices (the 64x64 maps of the bottleneck: 32 partials): one thread per channel, no
+// LDS, no barrier.  With at most kFinSlices partials, slice sl of the pooled form below holds partial sl alone (or
+// nothing), and its thread sl == 0 adds the slices in index order onto its own: that IS the sequential fp64 sum over the
+// partials in index order, an empty slice adding +0.0 (exact).  So this loop leaves the same bits, provided every term is
+// rounded as the pooled form rounds it -- n*d and (n*d)*d as products on their own, never contracted into an fma with the
+// running sum.  Pixel counts: lane l of every wave works out partial l's once (kFinSlices == the wave size) and the
+// unrolled loops read them as scalars.  The loads of a chunk are all issued before its sums (an empty partial's is
+// pointed at partial 0 and not used): one memory round trip for the 32 partials of a 64x64 map.
+constexpr int kFinDirectChunk = 32;
+constexpr int kFinDirectBlock = 64;                                       // channels (threads) per block of the direct form
+constexpr size_t kFinPoolLds = sizeof(double) * 4 * kFinSlices * 17;      // LDS of the pooled form
+static_assert(kFinSlices == 64, "the direct form keeps one partial's pixel count per lane of a 64-wide wave");
+struct FinSums { double s0, s1, s2, sm2; };
+// partials base .. base + kFinDirectChunk - 1 of channel c; the first chunk also delivers ref = stats[c].x (its v[0])
+template <bool kFirst>
+__device__ __forceinline__ void finalize_direct_chunk(const float2* __restrict__ stats, int base, int C, int c, int nb_lane,
+                                                      float& ref, FinSums& a) {
+    float2 v[kFinDirectChunk];
+#pragma unroll
+    for (int i = 0; i < kFinDirectChunk; ++i) {
+        const int nb = __builtin_amdgcn_readlane(nb_lane, base + i);
+        const float2* row = stats + (size_t)(nb != 0 ? base + i : 0) * (unsigned)C;   // a scalar address + one lane offset
+        v[i] = row[(unsigned)c];
+    }
+    if (kFirst) ref = v[0].x;   // partial 0 is never empty
+#pragma unroll
+    for (int i = 0; i < kFinDirectChunk; ++i) {
+#pragma clang fp contract(off)
+        const int nb = __builtin_amdgcn_readlane(nb_lane, base + i);
+        if (nb == 0) continue;
+        const double d = (double)(v[i].x - ref), n = (double)nb;
+        const double nd = n * d;
+        const double ndd = nd * d;
+        a.s0 = a.s0 + n;
+        a.s1 = a.s1 + nd;
+        a.s2 = a.s2 + ndd;
+        a.sm2 = a.sm2 + (double)v[i].y;
+    }
+}
+__device__ __forceinline__ void finalize_direct(const float2* __restrict__ stats, int nparts, int mtiles, int BM, int M, int C,
+                                                float eps, float2* __restrict__ mean_rstd, int wm, int H, int W,
+                                                const RunningUpdate& ru) {
+    const int lane = threadIdx.x & 63;
+    const bool uniform = wm == 0 && M % BM == 0;   // every partial covers BM pixels
+    const int nb_lane = lane >= nparts ? 0 : uniform ? BM : partial_pixels(lane, mtiles, BM, M, wm, H, W);
+    const int c = blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= C) return;
+    float ref;
+    FinSums a{0.0, 0.0, 0.0, 0.0};
+    finalize_direct_chunk<true>(stats, 0, C, c, nb_lane, ref, a);
+    if (nparts > kFinDirectChunk) finalize_direct_chunk<false>(stats, kFinDirectChunk, C, c, nb_lane, ref, a);
+    finalize_close(a.s0, a.s1, a.s2, a.sm2, ref, c, eps, mean_rstd, ru);
+}
+
+// blockDim.x == 16 * kFinSlices: the pooled form (its LDS is dynamic: 4 * kFinSlices * 17 doubles); any smaller block:
+// the direct form, blockDim.x channels per block
 __global__ __launch_bounds__(16 * kFinSlices) void inorm_finalize_kernel(const float2* __restrict__ stats, int nparts, int mtiles,
                                                              int BM, int M, int C, float eps,
                                                              float2* __restrict__ mean_rstd, int wm, int H, int W,
                                                              double* __restrict__ scratch, RunningUpdate ru) {
+    if (__builtin_expect(blockDim.x != 16 * kFinSlices, 0)) {   // (laid out behind the pooled form, which keeps its place)
+        finalize_direct(stats, nparts, mtiles, BM, M, C, eps, mean_rstd, wm, H, W, ru);
+        return;
+    }
     // gridDim.y > 1 (scratch given): block y pools every gridDim.y-th group of partials and leaves its four sums
     // in scratch[y][c][4]; inorm_finalize_merge_kernel adds the groups up.  One block per 16 channels cannot pull
     // a 1024x1024 layer's 16384 x 64 partials (8 MB) through a single CU in less than ~1 ms.
-    __shared__ double sh[4][kFinSlices][17];
+    extern __shared__ double fin_lds[];
+    double (*sh)[kFinSlices][17] = reinterpret_cast<double (*)[kFinSlices][17]>(fin_lds);
     const int cc = threadIdx.x & 15, sl = threadIdx.x >> 4;
     const int c = blockIdx.x * 16 + cc;
     double s0 = 0.0, s1 = 0.0, s2 = 0.0, sm2 = 0.0;
@@ -100,13 +173,7 @@ __global__ __launch_bounds__(16 * kFinSlices) void inorm_finalize_kernel(const f
             o[0] = s0; o[1] = s1; o[2] = s2; o[3] = sm2;
             return;
         }
-        const double mean_d = s1 / s0;
-        double m2 = sm2 + s2 - s1 * mean_d;
-        m2 = m2 > 0.0 ? m2 : 0.0;
-        const float var = (float)(m2 / s0);
-        const float2 mr = make_float2(ref + (float)mean_d, 1.0f / sqrtf(var + eps));
-        mean_rstd[c] = mr;
-        running_update(ru, c, mr, eps);
+        finalize_close(s0, s1, s2, sm2, ref, c, eps, mean_rstd, ru);
     }
 }
 
@@ -138,10 +205,26 @@ static int finalize_groups(int nparts, int C, const double* scratch) {
 }
 static int run_finalize(hipStream_t s, const float* stats, int nparts, int mtiles, int BM, int M, int C, float eps,
                         float* mean_rstd, int wm, int H, int W, double* scratch, const RunningUpdate* ru) {
-    const int groups = finalize_groups(nparts, C, scratch);
     const RunningUpdate none{nullptr, nullptr, 0.f, 0.f, 0};
     const RunningUpdate upd = ru ? *ru : none;
-    hipLaunchKernelGGL(inorm_finalize_kernel, dim3((C + 15) / 16, groups), dim3(16 * kFinSlices), 0, s,
+    const int direct = options().finalize_direct;
+    if (direct != 0 && nparts <= kFinSlices) {
+        // the direct form (inorm_finalize_kernel): one thread per channel, kFinDirectBlock channels per block
+        const int block = direct >= 64 && direct <= 256 ? direct / 64 * 64 : kFinDirectBlock;
+        if (wm > 0 && H % wm == 0 && W % wm == 0) {
+            // whole tiles only; with no padding tile either, every partial covers the same 128 pixels: the conv-kernel
+            // form with BM = that count has no per-partial arithmetic (partial_pixels gives the same number)
+            const int tpb = 128 / (wm * wm);
+            if ((H / wm) * (W / wm) == mtiles * tpb) { BM = tpb * wm * wm; M = H * W; wm = 0; }
+        }
+        hipLaunchKernelGGL(inorm_finalize_kernel, dim3((C + block - 1) / block), dim3(block), 0, s,
+                           reinterpret_cast<const float2*>(stats), nparts, mtiles, BM, M, C, eps,
+                           reinterpret_cast<float2*>(mean_rstd), wm, H, W, nullptr, upd);
+        T2V_HIP_CHECK(hipGetLastError());
+        return T2V_OK;
+    }
+    const int groups = finalize_groups(nparts, C, scratch);
+    hipLaunchKernelGGL(inorm_finalize_kernel, dim3((C + 15) / 16, groups), dim3(16 * kFinSlices), kFinPoolLds, s,
                        reinterpret_cast<const float2*>(stats), nparts, mtiles, BM, M, C, eps,
                        reinterpret_cast<float2*>(mean_rstd), wm, H, W, groups > 1 ? scratch : nullptr, groups > 1 ? none : upd);
     T2V_HIP_CHECK(hipGetLastError());
