@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define T2V_ABI_VERSION 21
+#define T2V_ABI_VERSION 22
 
 typedef enum {
     T2V_OK = 0,
@@ -60,8 +60,20 @@ enum { T2V_ACT_NONE = 0, T2V_ACT_TANH = 1, T2V_ACT_FLOW_W = 2 /* ch0,1: x*20 ; c
  * 144 multiply-adds per channel pair: 0.5625x the MFMA FLOPs of SpatialConvolutionMM / SpatialFullDilatedConvolution
  * (THCUNN.h:664,794), points {0, +-3/4, 3/2, inf}.  Only where t2v_conv_polyphase_supported() says so; it goes through
  * the *_winograd entry points (pack_weight, workspace_floats, forward_winograd), its statistics partials through the
- * finalize entries like any producer's. */
-enum { T2V_ALGO_DIRECT = 0, T2V_ALGO_WINOGRAD = 1, T2V_ALGO_WINOGRAD_F4 = 2, T2V_ALGO_POLYPHASE = 3 };
+ * finalize entries like any producer's.
+ * WINOGRAD_F4_BF16X2 (ABI 22) = WINOGRAD_F4 with its 36 GEMMs on the bf16 matrix cores, the one form that is NOT fp32
+ * throughout: every fp32 operand v of the GEMM stage is split into hi = bf16(v) and lo = bf16(v - hi) (round to nearest
+ * even) and the contraction is sum_k (ah*bh + ah*bl + al*bh), accumulated in fp32; al*bl is dropped.  About 16 mantissa
+ * bits per product -- of the Winograd-domain operands V and U, which are an order larger than the output they cancel to,
+ * so the split error is amplified: measured (profiles/split_bf16_accuracy.txt) 2.2e-5 of the output's
+ * rms per 64 -> 128 conv against 1.8e-7 for WINOGRAD_F4 (about 120x), and max |frame - float64| 1.8e-4 against 2.7e-5 (6.9x)
+ * on a 160 x 160 two-block generator, below the 1e-3 parity bar.  (The reduced-precision trade
+ * upstream's --fp16 offered; SpatialConvolutionMM_updateOutput, THCUNN.h:664, as THCUNN's half instantiation ran it.)  The
+ * transforms, bias and statistics are WINOGRAD_F4's fp32 arithmetic.  V and U hold two bf16 planes in the bytes of the fp32
+ * tensors: every size is WINOGRAD_F4's.  Forward only, where t2v_conv_winograd_bf16x2_supported() says so; never chosen by
+ * t2v_conv_best_algo -- a caller opts in (t2v_gen_desc.conv_algo 3). */
+enum { T2V_ALGO_DIRECT = 0, T2V_ALGO_WINOGRAD = 1, T2V_ALGO_WINOGRAD_F4 = 2, T2V_ALGO_POLYPHASE = 3,
+       T2V_ALGO_WINOGRAD_F4_BF16X2 = 4 };
 
 typedef struct t2v_ctx t2v_ctx;
 
@@ -160,6 +172,11 @@ int t2v_conv2d_forward_head_norm(t2v_ctx* ctx, void* stream, const t2v_conv_desc
  * the ceil(H/m) x ceil(W/m) tile grid (m = 2 | 4) is ragged at the bottom / right edge and padded with
  * empty tiles to a multiple of 128 (extra GEMM rows, masked in the output transform). */
 int t2v_conv_winograd_supported(const t2v_conv_desc* d, int x_cs);
+/* 1 where `d` (algo ignored) can run as T2V_ALGO_WINOGRAD_F4_BF16X2 (ABI 22): the conditions of F(4x4,3x3) above plus
+ * Cin % 32 == 0 and Cout % 128 == 0 (the split GEMM's K stage and tile width).  (THCUNN's counterpart is the type
+ * dispatch that picked SpatialConvolutionMM's half instantiation, THCUNN.h:664 under THC_GENERIC_FILE.)  Every backward,
+ * weight-gradient and data-gradient entry and query refuses a descriptor whose algo is T2V_ALGO_WINOGRAD_F4_BF16X2. */
+int t2v_conv_winograd_bf16x2_supported(const t2v_conv_desc* d, int x_cs);
 /* bit 0: T2V_ALGO_POLYPHASE applies to `d` (d->algo ignored); bit 1: ... and is the form the library itself selects (both
  * channel counts >= 256, >= 128 tiles: where it measured faster than the implicit-GEMM kernel).  Applies to: 3x3, stride 2; a conv with zero padding 1 and even H, W, or a
  * transposed conv with pad 1 / output_padding 1; x_cs == Cin, Cin % 32 == 0, Cout % 128 == 0, no activation.  The tile grid
@@ -182,13 +199,17 @@ int t2v_conv_winograd_tile_rows(const t2v_conv_desc* d);
 /* Which form the batched GEMM stage of an F(4x4,3x3) conv over `nimg` images takes under the current switches (reporting
  * only: bench.py's roofline label): one block per tile, or a fixed grid of resident blocks that hand accumulators over where
  * a tile is cut -- on 128x128 tiles, 192x64 tiles, 160x128 tiles with one block per CU (129..160 tile rows: the reference's
- * 512x320 frames), or ragged M tiles of 4,..,4,r 32-row fragments.  -1: not an F(4x4,3x3) conv. */
+ * 512x320 frames), or ragged M tiles of 4,..,4,r 32-row fragments; T2V_ALGO_WINOGRAD_F4_BF16X2 has the one split-bf16 form.
+ * -1: not an F(4x4,3x3) conv. */
 enum { T2V_GEMM_TILE_PER_BLOCK_64x64 = 0, T2V_GEMM_TILE_PER_BLOCK_128x128 = 1, T2V_GEMM_FIXED_GRID_128x128 = 2,
        T2V_GEMM_FIXED_GRID_192x64 = 3, T2V_GEMM_FIXED_GRID_160x128 = 4, T2V_GEMM_FIXED_GRID_RAGGED = 5,
        T2V_GEMM_FIXED_GRID_256x128 = 6 /* one block per CU, like 160x128 */,
-       T2V_GEMM_FIXED_GRID_RAGGED_TALL = 7 /* ragged, balanced tiles of 3..6 fragments, one block per CU */ };
+       T2V_GEMM_FIXED_GRID_RAGGED_TALL = 7 /* ragged, balanced tiles of 3..6 fragments, one block per CU */,
+       T2V_GEMM_SPLIT_BF16_128x128 = 8 /* T2V_ALGO_WINOGRAD_F4_BF16X2: one block per tile on the bf16 matrix cores (ABI 22;
+                                        * SpatialConvolutionMM's GEMM, THCUNN.h:664, in split-bf16 arithmetic) */ };
 int t2v_conv_winograd_gemm_form(const t2v_conv_desc* d, int nimg);
-/* forward with d->algo == T2V_ALGO_WINOGRAD | T2V_ALGO_WINOGRAD_F4; same contract as t2v_conv2d_forward plus the workspace */
+/* forward with d->algo == T2V_ALGO_WINOGRAD | T2V_ALGO_WINOGRAD_F4 | T2V_ALGO_WINOGRAD_F4_BF16X2; same contract as
+ * t2v_conv2d_forward plus the workspace */
 int t2v_conv2d_forward_winograd(t2v_ctx* ctx, void* stream, const t2v_conv_desc* d, const float* x, int x_cs,
                                 const float* w_packed, const float* bias, float* y, int y_cs, float* stats_partial,
                                 float* workspace);
@@ -486,7 +507,9 @@ typedef struct {
     float flow_multiplier; /* 20 * 2^scale */
     float eps;          /* 1e-5 */
     int conv_algo;      /* ResnetBlock convs: 0 = best supported of F(4x4,3x3) > F(2x2,3x3) > direct;
-                         * 1 = direct only; 2 = F(2x2,3x3) or direct */
+                         * 1 = direct only; 2 = F(2x2,3x3) or direct; 3 (ABI 22) = as 0, with every ResnetBlock conv that 0
+                         * runs as F(4x4,3x3) and t2v_conv_winograd_bf16x2_supported() accepts as
+                         * T2V_ALGO_WINOGRAD_F4_BF16X2 (the reduced-precision mode; workspace sizes are those of 0) */
 } t2v_gen_desc;
 
 typedef struct {

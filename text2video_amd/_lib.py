@@ -15,9 +15,11 @@ LIB_PATH = os.environ.get("T2V_LIBRARY") or os.path.join(_HERE, "lib", "libt2v_h
 T2V_OK = 0
 PAD_ZERO, PAD_REFLECT = 0, 1
 ACT_NONE, ACT_TANH, ACT_FLOW_W, ACT_LRELU = 0, 1, 2, 3
-ABI_VERSION = 21
+ABI_VERSION = 22
 MAX_BATCH = 8     # T2V_MAX_BATCH
 ALGO_DIRECT, ALGO_WINOGRAD, ALGO_WINOGRAD_F4, ALGO_POLYPHASE = 0, 1, 2, 3
+ALGO_WINOGRAD_F4_BF16X2 = 4     # F(4x4,3x3) with split-bf16 GEMMs: forward only, opt-in (t2v_gen_desc.conv_algo 3)
+CONV_ALGO_BF16X2 = 3            # t2v_gen_desc.conv_algo: the selection of 0 with its F(4x4,3x3) trunk in split-bf16 arithmetic
 
 
 class ConvDesc(Structure):
@@ -70,6 +72,7 @@ SIGNATURES = {
     "t2v_conv2d_forward_head_norm": (c_int, [c_void_p, c_void_p, POINTER(ConvDesc), c_void_p, c_int, c_void_p, c_void_p,
                                              c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int]),
     "t2v_conv_winograd_supported": (c_int, [POINTER(ConvDesc), c_int]),
+    "t2v_conv_winograd_bf16x2_supported": (c_int, [POINTER(ConvDesc), c_int]),
     "t2v_conv_polyphase_supported": (c_int, [POINTER(ConvDesc), c_int]),
     "t2v_conv_best_algo": (c_int, [POINTER(ConvDesc), c_int, c_int]),
     "t2v_conv_winograd_workspace_floats": (c_size_t, [POINTER(ConvDesc), c_int]),

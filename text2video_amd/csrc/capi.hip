@@ -290,9 +290,22 @@ bool winograd_supported(const t2v_conv_desc* d, int x_cs, int algo) {
     if (wino_out_h(d) < 1 || wino_out_w(d) < 1) return false;
     // any H, W >= 2 (reflection needs 2): ragged tiles are masked, the tile count is padded to 128
     if (d->Cin % 32 != 0 || x_cs != d->Cin || d->Cout % 4 != 0 || d->H < 2 || d->W < 2) return false;
+    // the split-bf16 GEMM works on whole 128-wide N tiles (Cin % 32 == 0, its K stage, is asked of every form above)
+    if (is_split(algo) && d->Cout % 128 != 0) return false;
     // the F(4x4) output transform can apply a (Leaky)ReLU (convs without a norm: the VGG19 loss network)
-    return d->act == T2V_ACT_NONE || (algo == T2V_ALGO_WINOGRAD_F4 && d->act == T2V_ACT_LRELU);
+    return d->act == T2V_ACT_NONE || (is_f4(algo) && d->act == T2V_ACT_LRELU);
 }
+// Training is fp32: every backward, weight-gradient and data-gradient entry turns a split-bf16 descriptor away by name
+static bool refuses_split(const t2v_conv_desc* d, const char* entry) {
+    if (!d || !is_split(d->algo)) return false;
+    set_error("%s: T2V_ALGO_WINOGRAD_F4_BF16X2 (algo 4) is a forward-only form; gradients run in fp32 (algo %d)", entry,
+              T2V_ALGO_WINOGRAD_F4);
+    return true;
+}
+#define T2V_REFUSE_SPLIT(d, entry)                       \
+    do {                                                 \
+        if (refuses_split(d, entry)) return T2V_ERR_INVALID; \
+    } while (0)
 
 // F(4x4) unless the zero tiles that pad its coarser grid to 128 make F(2x2) the smaller GEMM (tiny maps); direct
 // when neither beats 9 rows per output pixel
@@ -479,12 +492,12 @@ int winograd_forward(t2v_ctx* ctx, hipStream_t s, const t2v_conv_desc* d, const 
     const WinoBatch one;
     const WinoBatch& wb = batch ? *batch : one;
     const int nimg = wb.nimg;
-    const bool f4 = d->algo == T2V_ALGO_WINOGRAD_F4;
+    const bool f4 = is_f4(d->algo), split = is_split(d->algo);
     if (f4) T2V_TRY(check_async_errors());
     T2V_REQUIRE(nimg >= 1 && (f4 || nimg == 1), "winograd: batches are F(4x4,3x3) only");
     const size_t T = (size_t)wino_rows_batch(d, d->algo, nimg);
     const bool keep = wb.keep_v != nullptr;
-    T2V_REQUIRE(!keep || (f4 && nimg == 1 && wb.keep_slot >= 0 && wb.keep_slot < wb.keep_total),
+    T2V_REQUIRE(!keep || (f4 && !split && nimg == 1 && wb.keep_slot >= 0 && wb.keep_slot < wb.keep_total),
                 "winograd: V is kept for the weight gradient of single F(4x4,3x3) images only");
     T2V_REQUIRE(!wb.v_in || (f4 && !keep && !(stages & 1)), "winograd: a borrowed V replaces the input transform (F(4x4,3x3))");
     float* V = keep ? wb.keep_v + (size_t)wb.keep_slot * T * d->Cin : workspace;
@@ -493,10 +506,12 @@ int winograd_forward(t2v_ctx* ctx, hipStream_t s, const t2v_conv_desc* d, const 
         const int reflect = d->pad_mode == T2V_PAD_REFLECT;
         if (keep) T2V_TRY(launch_winograd4_input(s, x, wb.keep_v, d->H, d->W, d->Cin, d->pad, reflect, wb.keep_total, wb.keep_slot));
         else
-        T2V_TRY(f4 ? launch_winograd4_input(s, x, V, d->H, d->W, d->Cin, d->pad, reflect, nimg, 0, nimg, wb.img_stride_x)
+        T2V_TRY(f4 ? launch_winograd4_input(s, x, V, d->H, d->W, d->Cin, d->pad, reflect, nimg, 0, nimg, wb.img_stride_x, nullptr, split)
                    : launch_winograd_input(s, x, V, d->H, d->W, d->Cin, d->pad, reflect));
     }
-    if (stages & 2) {
+    if ((stages & 2) && split) {   // V and w_packed hold bf16 plane pairs: one form, one block per tile (winograd_split.hip)
+        T2V_TRY(launch_wino_split_gemm(s, wb.v_in ? wb.v_in : V, w_packed, Mm, (int)T, d->Cin, d->Cout));
+    } else if (stages & 2) {
         PositionGemm g;
         g.has_scratch = f4;      // (F(2x2)'s workspace has none: winograd_workspace_floats)
         g.groups = wino_pos(d->algo);
@@ -652,6 +667,9 @@ int t2v_conv_polyphase_supported(const t2v_conv_desc* d, int x_cs) {
 int t2v_conv_winograd_supported(const t2v_conv_desc* d, int x_cs) {
     return (winograd_supported(d, x_cs, T2V_ALGO_WINOGRAD) ? 1 : 0) | (winograd_supported(d, x_cs, T2V_ALGO_WINOGRAD_F4) ? 2 : 0);
 }
+int t2v_conv_winograd_bf16x2_supported(const t2v_conv_desc* d, int x_cs) {
+    return winograd_supported(d, x_cs, T2V_ALGO_WINOGRAD_F4_BF16X2) ? 1 : 0;
+}
 
 int t2v_conv_best_algo(const t2v_conv_desc* d, int x_cs, int cap) { return d ? best_conv_algo(d, x_cs, cap) : T2V_ALGO_DIRECT; }
 
@@ -664,7 +682,7 @@ size_t t2v_conv_winograd_workspace_floats(const t2v_conv_desc* d, int x_cs) {
 size_t t2v_conv_winograd_batch_workspace_floats(const t2v_conv_desc* d, int x_cs, int nimg) {
     if (!d || nimg < 1) return 0;
     if (d->algo == T2V_ALGO_POLYPHASE) return nimg == 1 && polyphase_supported(d, x_cs) ? polyphase_workspace_floats(d) : 0;
-    if (!winograd_supported(d, x_cs, d->algo) || (nimg > 1 && d->algo != T2V_ALGO_WINOGRAD_F4)) return 0;
+    if (!winograd_supported(d, x_cs, d->algo) || (nimg > 1 && !is_f4(d->algo))) return 0;
     return winograd_workspace_floats(d, nimg);
 }
 
@@ -708,13 +726,13 @@ int t2v_conv2d_forward_winograd_batch_stages(t2v_ctx* ctx, void* stream, const t
     }
     T2V_REQUIRE(winograd_supported(d, x_cs, d->algo), "winograd forward: shape/algo not supported (t2v_conv_winograd_supported)");
     T2V_REQUIRE(y_cs == d->Cout, "winograd forward: output channel storage must equal Cout");
-    T2V_REQUIRE(d->algo == T2V_ALGO_WINOGRAD_F4 || (nimg == 1 && !mean_rstd),
+    T2V_REQUIRE(is_f4(d->algo) || (nimg == 1 && !mean_rstd),
                 "winograd batch forward: batches and the lazy norm are F(4x4,3x3) only");
     if (mean_rstd && (stages & 1)) {
         T2V_REQUIRE(relu == 0 || relu == 1, "winograd batch forward: relu %d", relu);
         const LazyNorm ln{mean_rstd, gamma, beta, relu, res, xout};
         T2V_TRY(launch_winograd4_input(s, x, workspace, d->H, d->W, d->Cin, d->pad, d->pad_mode == T2V_PAD_REFLECT, nimg, 0, nimg,
-                                       img_stride, &ln));
+                                       img_stride, &ln, is_split(d->algo)));
         stages &= ~1;
     }
     WinoBatch wb;
@@ -728,6 +746,7 @@ int t2v_conv2d_forward_winograd_keep_v(t2v_ctx* ctx, void* stream, const t2v_con
                                        const float* w_packed, const float* bias, float* y, int y_cs, float* stats_partial,
                                        float* workspace, float* wgrad_workspace, int batch, int slot) {
     T2V_REQUIRE(ctx && d && x && w_packed && y && workspace && wgrad_workspace, "winograd forward (V kept): null pointer");
+    T2V_REFUSE_SPLIT(d, "conv2d_forward_winograd_keep_v");
     T2V_REQUIRE(d->algo == T2V_ALGO_WINOGRAD_F4 && winograd_supported(d, x_cs, d->algo) && x_cs == d->Cin &&
                     wgrad_winograd_ok(d, x_cs, d->Cout),
                 "winograd forward (V kept): F(4x4,3x3) layers with a Winograd-domain weight gradient only "
@@ -761,6 +780,10 @@ static int pack_weight(t2v_ctx* ctx, void* stream, const t2v_conv_desc* d, int x
     }
     if (is_winograd(d->algo)) {
         T2V_REQUIRE(winograd_supported(d, x_cs, d->algo), "pack_weight: Winograd not supported for this shape");
+        if (is_split(d->algo)) {   // (Cout % 128 == 0: no padding rows)
+            T2V_REFUSE_SPLIT(adjoint ? d : nullptr, "conv_pack_weight_adjoint");
+            return launch_winograd4_weight_split(s, w_torch_dev, packed_dev, d->Cout, d->Cin, pl.Cout_p, x_cs);
+        }
         return (d->algo == T2V_ALGO_WINOGRAD_F4 ? launch_winograd4_weight : launch_winograd_weight)(
             s, w_torch_dev, packed_dev, d->Cout, d->Cin, pl.Cout_p, x_cs, adjoint);
     }
@@ -931,7 +954,7 @@ static bool wgrad_combine_on() { return options().wgrad_combine != 0; }
 
 size_t t2v_conv_backward_weight_workspace_floats(const t2v_conv_desc* d, int x_cs, int batch) {
     ConvPlan pl;
-    if (!d || build_conv_plan(d, x_cs, true, &pl) != T2V_OK) return 0;
+    if (!d || is_split(d->algo) || build_conv_plan(d, x_cs, true, &pl) != T2V_OK) return 0;
     const int dy_cs = round_up(d->Cout, 4);
     if (wgrad_fold_n(d, x_cs, dy_cs)) {   // padded input copy + the partials of its own split rule
         const long nk = ((long)batch * (d->H + 2 * d->pad) * (d->W + 2 * d->pad) + 31) / 32;
@@ -949,6 +972,7 @@ static int backward_weight_impl(t2v_ctx* ctx, void* stream, const t2v_conv_desc*
                                 int x_cs, long x_stride, const float* dy, int dy_cs, long dy_stride, float* dw_packed,
                                 int accumulate, float* workspace) {
     T2V_REQUIRE(ctx && x && dy && dw_packed && batch >= 1, "backward_weight: bad arguments");
+    T2V_REFUSE_SPLIT(d, "conv2d_backward_weight");
     ConvPlan pl;
     T2V_TRY(build_conv_plan(d, x_cs, true, &pl));   // 128-row weight granule, plain 128x128 bookkeeping
     T2V_REQUIRE(dy_cs >= d->Cout && dy_cs % 4 == 0, "backward_weight: dy channel storage %d", dy_cs);
@@ -1048,7 +1072,7 @@ int t2v_conv2d_backward_weight(t2v_ctx* ctx, void* stream, const t2v_conv_desc* 
 }
 int t2v_conv_backward_weight_strided_supported(const t2v_conv_desc* d, int x_cs, int dy_cs) {
     ConvPlan pl;
-    if (!d || build_conv_plan(d, x_cs, true, &pl) != T2V_OK) return 0;
+    if (!d || is_split(d->algo) || build_conv_plan(d, x_cs, true, &pl) != T2V_OK) return 0;
     if ((wgrad_fold_n(d, x_cs, dy_cs) && dy_cs == round_up(d->Cout, 4)) || wgrad_fold(d, x_cs)) return 0;
     WgradParams w;
     memset(&w, 0, sizeof(w));
@@ -1067,13 +1091,13 @@ int t2v_conv2d_backward_weight_strided(t2v_ctx* ctx, void* stream, const t2v_con
 
 // ---- weight gradient in the Winograd domain (F(4x4,3x3)) -------------------------------------------------
 static bool wgrad_winograd_ok(const t2v_conv_desc* d, int x_cs, int dy_cs) {
-    return winograd_supported(d, x_cs, T2V_ALGO_WINOGRAD_F4) && dy_cs == d->Cout && d->Cout % 4 == 0;
+    return !is_split(d->algo) && winograd_supported(d, x_cs, T2V_ALGO_WINOGRAD_F4) && dy_cs == d->Cout && d->Cout % 4 == 0;
 }
 int t2v_conv_backward_weight_winograd_supported(const t2v_conv_desc* d, int x_cs, int dy_cs) {
     return d && wgrad_winograd_ok(d, x_cs, dy_cs) ? 1 : 0;
 }
 size_t t2v_conv_backward_weight_winograd_workspace_floats(const t2v_conv_desc* d, int x_cs, int batch) {
-    if (!d || batch < 1 || !winograd_supported(d, x_cs, T2V_ALGO_WINOGRAD_F4)) return 0;
+    if (!d || batch < 1 || is_split(d->algo) || !winograd_supported(d, x_cs, T2V_ALGO_WINOGRAD_F4)) return 0;
     const size_t Tp = (size_t)wino_tiles_padded(d, T2V_ALGO_WINOGRAD_F4);
     const size_t Cout_p = (size_t)round_up(d->Cout, 128), Kp = (size_t)round_up(x_cs, kBK);
     // V, M_dy, dU, then the hand-over area of the fixed-grid reduction (conv_wgrad.hip: wino_wgrad_sk_kernel)
@@ -1083,7 +1107,8 @@ int t2v_conv_winograd_tile_rows(const t2v_conv_desc* d) {
     return d ? wino_tiles_padded(d, T2V_ALGO_WINOGRAD_F4) : 0;
 }
 int t2v_conv_winograd_gemm_form(const t2v_conv_desc* d, int nimg) {
-    if (!d || d->algo != T2V_ALGO_WINOGRAD_F4 || nimg < 1) return -1;
+    if (!d || !is_f4(d->algo) || nimg < 1) return -1;
+    if (is_split(d->algo)) return wino_split_gemm_ok(wino_rows_batch(d, d->algo, nimg), d->Cin, d->Cout) ? T2V_GEMM_SPLIT_BF16_128x128 : -1;
     PositionGemm g;      // as winograd_forward fills it
     g.groups = 36; g.rows = nimg * wino_tiles_real(d, d->algo); g.T = wino_rows_batch(d, d->algo, nimg);
     g.K = d->Cin; g.N = d->Cout;
@@ -1094,6 +1119,7 @@ int t2v_conv2d_backward_weight_winograd_stages(t2v_ctx* ctx, void* stream, const
                                                float* dw_torch, int accumulate, float* workspace, int stages) {
     T2V_REQUIRE(ctx && d && workspace && batch >= 1 && b0 >= 0 && nb >= 0 && b0 + nb <= batch,
                 "backward_weight_winograd: bad arguments");
+    T2V_REFUSE_SPLIT(d, "conv2d_backward_weight_winograd");
     T2V_REQUIRE(wgrad_winograd_ok(d, x_cs, dy_cs), "backward_weight_winograd: shape not supported "
                                                   "(t2v_conv_backward_weight_winograd_supported)");
     hipStream_t s = (hipStream_t)stream;
@@ -1152,6 +1178,7 @@ int t2v_conv2d_backward_weight_winograd_dy_norm(t2v_ctx* ctx, void* stream, cons
                                                 float* workspace) {
     T2V_REQUIRE(ctx && d && conv_out && dy && mean_rstd && sums && workspace && batch >= 1 && slot >= 0 && slot < batch,
                 "backward_weight_winograd_dy_norm: bad arguments");
+    T2V_REFUSE_SPLIT(d, "conv2d_backward_weight_winograd_dy_norm");
     T2V_REQUIRE(wgrad_winograd_ok(d, x_cs, d->Cout), "backward_weight_winograd_dy_norm: shape not supported "
                                                      "(t2v_conv_backward_weight_winograd_supported)");
     const int Tp = wino_tiles_padded(d, T2V_ALGO_WINOGRAD_F4), Tt = batch * Tp;
@@ -1174,7 +1201,7 @@ static bool dgrad_winograd_ok(const t2v_conv_desc* d, int x_cs, int dy_cs) {
     return wgrad_winograd_ok(d, x_cs, dy_cs) && d->pad_mode == T2V_PAD_REFLECT && d->pad == 1 && d->H % 4 == 0 && d->W % 4 == 0 &&
            d->Cout % kBK == 0;
 }
-int t2v_conv_backward_data_winograd_supported(const t2v_conv_desc* d, int x_cs, int dy_cs) {
+int t2v_conv_backward_data_winograd_supported(const t2v_conv_desc* d, int x_cs, int dy_cs) {   // (0 for a split-bf16 desc)
     return d && dgrad_winograd_ok(d, x_cs, dy_cs) ? 1 : 0;
 }
 size_t t2v_conv_backward_data_winograd_weight_floats(const t2v_conv_desc* d, int x_cs) {
@@ -1189,6 +1216,7 @@ size_t t2v_conv_backward_data_winograd_scratch_floats(const t2v_conv_desc* d, in
 int t2v_conv_pack_weight_transposed(t2v_ctx* ctx, void* stream, const t2v_conv_desc* d, int x_cs, const float* w_forward_dev,
                                     float* packed_dev) {
     T2V_REQUIRE(ctx && d && w_forward_dev && packed_dev, "pack_weight_transposed: null pointer");
+    T2V_REFUSE_SPLIT(d, "conv_pack_weight_transposed");
     T2V_REQUIRE(dgrad_winograd_ok(d, x_cs, d->Cout), "pack_weight_transposed: shape not supported "
                                                      "(t2v_conv_backward_data_winograd_supported)");
     // U^T[xi][c][n]: the rows are the forward layer's INPUT channels, K runs over its OUTPUT channels
@@ -1219,6 +1247,7 @@ int t2v_conv2d_backward_data_winograd(t2v_ctx* ctx, void* stream, const t2v_conv
 int t2v_conv2d_backward_data_winograd_fw(t2v_ctx* ctx, void* stream, const t2v_conv_desc* d, int batch, int slot,
                                          const float* wgrad_workspace, int x_cs, const float* u_forward_packed, float* scratch,
                                          float* dx) {
+    T2V_REFUSE_SPLIT(d, "conv2d_backward_data_winograd_fw");
     T2V_REQUIRE(d && dgrad_winograd_forward_weights_ok(d, x_cs, d->Cout),
                 "backward_data_winograd_fw: shape not supported (t2v_conv_backward_data_winograd_takes_forward_weights)");
     return backward_data_winograd(ctx, stream, d, batch, slot, wgrad_workspace, x_cs, u_forward_packed, true, scratch, dx);
@@ -1228,6 +1257,7 @@ static int backward_data_winograd(t2v_ctx* ctx, void* stream, const t2v_conv_des
                                   float* scratch, float* dx) {
     T2V_REQUIRE(ctx && d && wgrad_workspace && ut_packed && scratch && dx && batch >= 1 && slot >= 0 && slot < batch,
                 "backward_data_winograd: bad arguments");
+    T2V_REFUSE_SPLIT(d, "conv2d_backward_data_winograd");
     T2V_REQUIRE(dgrad_winograd_ok(d, x_cs, d->Cout), "backward_data_winograd: shape not supported");
     T2V_TRY(check_async_errors());
     hipStream_t s = (hipStream_t)stream;
@@ -1251,6 +1281,7 @@ static int backward_data_winograd(t2v_ctx* ctx, void* stream, const t2v_conv_des
 int t2v_conv_unpack_weight_into(t2v_ctx* ctx, void* stream, const t2v_conv_desc* d, int x_cs, const float* packed_dev,
                                 float* w_torch_dev, int accumulate) {
     T2V_REQUIRE(ctx && packed_dev && w_torch_dev, "unpack_weight: null pointer");
+    T2V_REFUSE_SPLIT(d, "conv_unpack_weight");
     ConvPlan pl;
     T2V_TRY(build_conv_plan(d, x_cs, false, &pl));
     if (!d->transposed)

@@ -16,8 +16,11 @@ struct ConvPlan {
 };
 
 int build_conv_plan(const t2v_conv_desc* d, int x_cs, bool need_stats, ConvPlan* out);
-inline bool is_winograd(int algo) { return algo == T2V_ALGO_WINOGRAD || algo == T2V_ALGO_WINOGRAD_F4; }
-inline int wino_m(int algo) { return algo == T2V_ALGO_WINOGRAD_F4 ? 4 : 2; }          // output tile edge
+// F(4x4,3x3) in either arithmetic: the split-bf16 form shares every geometry, layout size and the output transform
+inline bool is_split(int algo) { return algo == T2V_ALGO_WINOGRAD_F4_BF16X2; }
+inline bool is_f4(int algo) { return algo == T2V_ALGO_WINOGRAD_F4 || is_split(algo); }
+inline bool is_winograd(int algo) { return algo == T2V_ALGO_WINOGRAD || is_f4(algo); }
+inline int wino_m(int algo) { return is_f4(algo) ? 4 : 2; }          // output tile edge
 inline int wino_pos(int algo) { return (wino_m(algo) + 2) * (wino_m(algo) + 2); }    // transform positions: 16 | 36
 inline int wino_out_h(const t2v_conv_desc* d) { return d->H + 2 * d->pad - 2; }   // 3x3, stride 1
 inline int wino_out_w(const t2v_conv_desc* d) { return d->W + 2 * d->pad - 2; }
@@ -27,14 +30,15 @@ inline int wino_tiles_padded(const t2v_conv_desc* d, int algo) { return wino_til
 inline int wino_tiles_real(const t2v_conv_desc* d, int algo) { return wino_tile_grid(d, algo).T; }
 // GEMM rows per transform position for a batch of nimg images: F(4x4) packs the images' tiles and pads the total
 inline int wino_rows_batch(const t2v_conv_desc* d, int algo, int nimg) {
-    return (nimg > 1 && algo == T2V_ALGO_WINOGRAD_F4) ? wino_pad_tiles(nimg * wino_tiles_real(d, algo)) : wino_tiles_padded(d, algo);
+    return (nimg > 1 && is_f4(algo)) ? wino_pad_tiles(nimg * wino_tiles_real(d, algo)) : wino_tiles_padded(d, algo);
 }
 inline size_t winograd_vm_floats(const t2v_conv_desc* d, int nimg = 1) {             // V + M of `nimg` images
     return (size_t)wino_pos(d->algo) * wino_rows_batch(d, d->algo, nimg) * ((size_t)d->Cin + d->Cout);
 }
-// ... followed, for F(4x4,3x3), by the hand-over scratch of the fixed-grid GEMM (conv_igemm.hip: wino_gemm_sk_kernel)
+// ... followed, for F(4x4,3x3), by the hand-over scratch of the fixed-grid GEMM (conv_igemm.hip: wino_gemm_sk_kernel; the
+// split-bf16 form keeps the size and leaves the scratch alone)
 inline size_t winograd_workspace_floats(const t2v_conv_desc* d, int nimg = 1) {
-    return winograd_vm_floats(d, nimg) + (d->algo == T2V_ALGO_WINOGRAD_F4 ? wino_gemm_sk_scratch_floats() : 0);
+    return winograd_vm_floats(d, nimg) + (is_f4(d->algo) ? wino_gemm_sk_scratch_floats() : 0);
 }
 // GEMM rows of the whole conv (all positions): what the algorithm choice compares
 inline long wino_gemm_rows(const t2v_conv_desc* d, int algo) { return (long)wino_pos(algo) * wino_tiles_padded(d, algo); }

@@ -52,7 +52,7 @@ void enumerate_layers(const t2v_gen_desc& g, std::vector<LayerSpec>& out) {
         for (int i = 0; i < n; ++i) {
             t2v_conv_desc cd = mk_conv(H >> i, W >> i, G << i, G << (i + 1), 3, 2, 1, T2V_PAD_ZERO, 0);
             // the deep stride-2 layers as polyphase Winograd F(4,2) (polyphase.hip) where that is the faster form
-            if (g.conv_algo == 0 && polyphase_pays(&cd, G << i)) cd.algo = T2V_ALGO_POLYPHASE;
+            if ((g.conv_algo == 0 || g.conv_algo == 3) && polyphase_pays(&cd, G << i)) cd.algo = T2V_ALGO_POLYPHASE;
             out.push_back({cd, G << i, true});
         }
     };
@@ -60,14 +60,17 @@ void enumerate_layers(const t2v_gen_desc& g, std::vector<LayerSpec>& out) {
         const int C = G << n;
         t2v_conv_desc cd = mk_conv(H >> n, W >> n, C, C, 3, 1, 1, T2V_PAD_REFLECT, 0);
         // the ResnetBlock convs (84 % of the FLOPs) run as Winograd F(2x2,3x3) wherever the geometry allows
-        cd.algo = best_conv_algo(&cd, C, g.conv_algo);
+        // conv_algo 3: the selection of 0, its F(4x4,3x3) layers in split-bf16 arithmetic where that form takes them
+        cd.algo = best_conv_algo(&cd, C, g.conv_algo == 3 ? 0 : g.conv_algo);
+        if (g.conv_algo == 3 && cd.algo == T2V_ALGO_WINOGRAD_F4 && winograd_supported(&cd, C, T2V_ALGO_WINOGRAD_F4_BF16X2))
+            cd.algo = T2V_ALGO_WINOGRAD_F4_BF16X2;
         for (int i = 0; i < 2 * count; ++i) out.push_back({cd, C, true});
     };
     auto ups = [&]() {
         for (int i = 0; i < n; ++i) {
             const int l = n - i;
             t2v_conv_desc cd = mk_conv(H >> l, W >> l, G << l, G << (l - 1), 3, 2, 1, T2V_PAD_ZERO, 1);
-            if (g.conv_algo == 0 && polyphase_pays(&cd, G << l)) cd.algo = T2V_ALGO_POLYPHASE;
+            if ((g.conv_algo == 0 || g.conv_algo == 3) && polyphase_pays(&cd, G << l)) cd.algo = T2V_ALGO_POLYPHASE;
             out.push_back({cd, G << l, true});
         }
     };
@@ -141,7 +144,7 @@ void plan_buffers(const t2v_gen_desc& g, const std::vector<LayerSpec>& layers, i
         b.vshare = nullptr;
         if (flow_global) {
             const LayerSpec& L = layers[2 * (1 + n + 2 * (g.n_blocks - g.n_blocks / 2))];      // the branches' first conv
-            if (L.cd.algo == T2V_ALGO_WINOGRAD_F4)
+            if (is_f4(L.cd.algo))
                 b.vshare = a.alloc((size_t)wino_pos(L.cd.algo) * wino_rows_batch(&L.cd, L.cd.algo, nimg) * L.cd.Cin);
         }
     }
@@ -181,7 +184,7 @@ void plan_buffers(const t2v_gen_desc& g, const std::vector<LayerSpec>& layers, i
     size_t max_wino = 0;
     for (const LayerSpec& L : layers)
         if (is_winograd(L.cd.algo)) {
-            const size_t w = winograd_workspace_floats(&L.cd, L.cd.algo == T2V_ALGO_WINOGRAD_F4 ? nimg : 1);
+            const size_t w = winograd_workspace_floats(&L.cd, is_f4(L.cd.algo) ? nimg : 1);
             if (w > max_wino) max_wino = w;
         } else if (L.cd.algo == T2V_ALGO_POLYPHASE) {
             const size_t w = polyphase_workspace_floats(&L.cd);
@@ -356,7 +359,7 @@ struct Runner {
             const LazyNorm ln{b.mean_rstd[sc], g.norm_affine ? lz->norm->gamma : nullptr, g.norm_affine ? lz->norm->beta : nullptr,
                               lz->relu, lz->res, lz->xout};
             T2V_TRY(launch_winograd4_input(s, x, b.wino[sc], cd.H, cd.W, cd.Cin, cd.pad, cd.pad_mode == T2V_PAD_REFLECT, nimg, 0,
-                                           nimg, (long)b.bott, &ln));
+                                           nimg, (long)b.bott, &ln, is_split(cd.algo)));
         }
         WinoBatch wb;
         wb.nimg = nimg;
@@ -414,13 +417,13 @@ struct Runner {
     // pointer in *out.  tmp: 4 distinct buffers != x.
     // a chain of `count` blocks starting at layer l takes the lazy form
     bool chain_is_lazy(int l, int count) const {
-        return options().chain_lazy && count > 0 && specs[l].cd.algo == T2V_ALGO_WINOGRAD_F4 && b.mr_stride == (size_t)2 * specs[l].cd.Cout;
+        return options().chain_lazy && count > 0 && is_f4(specs[l].cd.algo) && b.mr_stride == (size_t)2 * specs[l].cd.Cout;
     }
     // V of the map the chain at layer l starts from (the batch back to back), into the shared slot
     int share_v(int l, const float* x) {
         const t2v_conv_desc& cd = specs[l].cd;
         return launch_winograd4_input(s, x, b.vshare, cd.H, cd.W, cd.Cin, cd.pad, cd.pad_mode == T2V_PAD_REFLECT, nimg, 0, nimg,
-                                      (long)b.bott);
+                                      (long)b.bott, nullptr, is_split(cd.algo));
     }
     int res_chain(const float* x, int count, float* tmp[4], const float** out, PendingNorm* pend_out = nullptr,
                   const float* v0 = nullptr) {

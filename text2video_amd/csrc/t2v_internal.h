@@ -222,8 +222,17 @@ int launch_winograd_output(hipStream_t s, const float* Mm, const float* bias, fl
 int launch_winograd4_weight(hipStream_t s, const float* w, float* U, int Cout, int Cin, int Cout_p, int Cin_s, int adjoint = 0);
 // nimg == 0: slot layout (image -> slot `image` of `batch` slots of Tp rows); nimg > 0: packed batch of nimg images.
 // lazy (packed only): x still has to go through its norm layer (winograd4_input_kernel<1|2>)
+// split (packed only): V receives the two bf16 planes of T2V_ALGO_WINOGRAD_F4_BF16X2 (winograd_split.hip) instead of fp32
 int launch_winograd4_input(hipStream_t s, const float* x, float* V, int H, int W, int C, int pad, int reflect, int batch = 1,
-                           int image = 0, int nimg = 0, long img_stride = 0, const LazyNorm* lazy = nullptr);
+                           int image = 0, int nimg = 0, long img_stride = 0, const LazyNorm* lazy = nullptr, bool split = false);
+// winograd_split.hip: the split-bf16 form of the F(4x4,3x3) stages 1 and 2 and of its weight packing.  mode 0 | 1 | 2 as
+// winograd4_input_kernel; the geometry is the one launch_winograd4_input worked out (packed layout)
+int launch_winograd4_input_split(hipStream_t s, int mode, const float* x, float* V, int H, int W, int C, const TileGrid& tg,
+                                 int pad, int reflect, int Tt, int nimg, long img_stride, int last_tiles, const LazyNorm& ln,
+                                 unsigned xcd_grid);
+int launch_winograd4_weight_split(hipStream_t s, const float* w, float* U, int Cout, int Cin, int Cout_p, int Cin_s);
+bool wino_split_gemm_ok(int Tt, int K, int N);
+int launch_wino_split_gemm(hipStream_t s, const float* V, const float* U, float* M, int Tt, int K, int N);
 int launch_winograd4_dgrad_output(hipStream_t s, const float* dV, float* dxp, int H, int W, int C);
 // polyphase.hip
 int launch_polyphase_weight(hipStream_t s, const float* w, float* U, int Cout, int Cin, int Cout_p, int Cin_s, int up);

@@ -4,6 +4,7 @@
 // bit by construction (the build uses -ffp-contract=off: inlining into different kernels cannot change a result).
 #pragma once
 #include <hip/hip_runtime.h>
+#include "winograd_f4_consts.h"
 
 namespace t2v {
 
@@ -151,6 +152,117 @@ __device__ __forceinline__ void output_transform_4x4(const double (&AT)[4][P], c
             }
     }
     block_stats_128(out, mask, sh, tl, cl, ok, stats, N, n);
+}
+
+// ---- F(4x4,3x3) input and weight transforms with a store policy: the fp32 kernels of winograd.hip and the split-bf16 ones
+// of winograd_split.hip run the same arithmetic and differ only in what `store` does with a finished value.
+// U[pos] = (G g G^T)[pos] of one (n, c) filter: transformed in fp64, rounded once; store(pos, u)
+template <class Store>
+__device__ __forceinline__ void winograd4_weight_transform(const double (&g)[3][3], Store store) {
+    double t[6][3];
+#pragma unroll
+    for (int a = 0; a < 6; ++a)
+#pragma unroll
+        for (int b = 0; b < 3; ++b) t[a][b] = f4::kG[a][0] * g[0][b] + f4::kG[a][1] * g[1][b] + f4::kG[a][2] * g[2][b];
+#pragma unroll
+    for (int a = 0; a < 6; ++a)
+#pragma unroll
+        for (int b = 0; b < 6; ++b) {
+            const double u = t[a][0] * f4::kG[b][0] + t[a][1] * f4::kG[b][1] + t[a][2] * f4::kG[b][2];
+            store(a * 6 + b, (float)u);
+        }
+}
+
+// One image's view of an F(4x4) input transform launch (the per-image pointers already advanced)
+struct Wino4Input {
+    const float2* x;
+    int H, W, C2, TW, T, pad, reflect;
+    const float2* mean_rstd;   // MODE 1 | 2
+    const float2* gamma;       // both or neither
+    const float2* beta;
+    const float2* res;         // MODE 2
+    float2* xout;              // MODE 2
+};
+// V[a*6+b] = (B^T d B)[a][b] of tile `tile` (row-major in the TW-wide tile grid; tile >= T: a padding tile, zeros) for the
+// channel pair c2; store(pos, v) receives the 36 values.  MODE as winograd4_input_kernel: 0 plain, 1 lazy norm + ReLU,
+// 2 lazy norm + residual with the tile's own 4x4 pixels written to xout.
+template <int MODE, class Store>
+__device__ __forceinline__ void winograd4_input_item(const Wino4Input& p, const long tile, const int c2, Store store) {
+    const int H = p.H, W = p.W, C2 = p.C2, pad = p.pad;
+    if (tile >= p.T) {   // padding tiles: zeros
+#pragma unroll
+        for (int xi = 0; xi < 36; ++xi) store(xi, make_float2(0.f, 0.f));
+        return;
+    }
+    const int ty = (int)(tile / p.TW), tx = (int)(tile - (long)ty * p.TW);
+    int ry[6], rx[6];
+    bool oky[6], okx[6];
+#pragma unroll
+    for (int k = 0; k < 6; ++k) {
+        int yy = 4 * ty - pad + k, xx = 4 * tx - pad + k;
+        oky[k] = p.reflect || ((unsigned)yy < (unsigned)H);
+        okx[k] = p.reflect || ((unsigned)xx < (unsigned)W);
+        yy = yy < 0 ? -yy : yy;
+        xx = xx < 0 ? -xx : xx;
+        ry[k] = max(min(yy, 2 * H - 2 - yy), 0);   // past the reflected border: ragged tile, outputs masked
+        rx[k] = max(min(xx, 2 * W - 2 - xx), 0);
+    }
+    float2 mr0, mr1, gm = make_float2(1.f, 1.f), bt = make_float2(0.f, 0.f);
+    if (MODE) {
+        mr0 = p.mean_rstd[2 * c2];
+        mr1 = p.mean_rstd[2 * c2 + 1];
+        if (p.gamma) {
+            gm = p.gamma[c2];
+            bt = p.beta[c2];
+        }
+    }
+    // rows first: r[a][j] = sum_b B^T[j][b] d[a][b]
+    float rxv[6][6], ryv[6][6];
+#pragma unroll
+    for (int a = 0; a < 6; ++a) {
+        float2 d[6], r[6];
+#pragma unroll
+        for (int b = 0; b < 6; ++b) {
+            const long at = ((long)ry[a] * W + rx[b]) * C2 + c2;
+            d[b] = (oky[a] && okx[b]) ? p.x[at] : make_float2(0.f, 0.f);
+            if (MODE == 2) r[b] = (oky[a] && okx[b]) ? p.res[at] : make_float2(0.f, 0.f);
+        }
+        float dx[6], dy[6];
+#pragma unroll
+        for (int b = 0; b < 6; ++b) {
+            float2 v = d[b];
+            if (MODE && oky[a] && okx[b]) {
+                v.x = norm_apply(v.x, mr0.x, mr0.y, p.gamma != nullptr, gm.x, bt.x, MODE == 1);
+                v.y = norm_apply(v.y, mr1.x, mr1.y, p.gamma != nullptr, gm.y, bt.y, MODE == 1);
+                if (MODE == 2) {
+                    v.x += r[b].x;
+                    v.y += r[b].y;
+                    // the tile's own pixels: rows / columns pad .. pad+3 of the patch, inside the map
+                    if (a >= pad && a < pad + 4 && b >= pad && b < pad + 4 && 4 * ty - pad + a < H && 4 * tx - pad + b < W)
+                        p.xout[((long)ry[a] * W + rx[b]) * C2 + c2] = v;
+                }
+            }
+            dx[b] = v.x;
+            dy[b] = v.y;
+        }
+#pragma unroll
+        for (int j = 0; j < 6; ++j) {
+            rxv[a][j] = cdot<6>(f4::kBT[j], dx);
+            ryv[a][j] = cdot<6>(f4::kBT[j], dy);
+        }
+    }
+    // columns: v[a2][j] = sum_a B^T[a2][a] r[a][j]
+#pragma unroll
+    for (int j = 0; j < 6; ++j) {
+        float cx[6], cy[6];
+#pragma unroll
+        for (int a = 0; a < 6; ++a) {
+            cx[a] = rxv[a][j];
+            cy[a] = ryv[a][j];
+        }
+#pragma unroll
+        for (int a2 = 0; a2 < 6; ++a2) store(a2 * 6 + j, make_float2(cdot<6>(f4::kBT[a2], cx), cdot<6>(f4::kBT[a2], cy)));
+    }
 }
 
 }  // namespace t2v

@@ -196,18 +196,7 @@ int launch_winograd_output(hipStream_t s, const float* Mm, const float* bias, fl
 // M [36][Tp][N], T = ceil(H/4) * ceil(W/4) tiles padded to Tp (multiple of 128).
 __device__ __forceinline__ void winograd4_weight_store(const double (&g)[3][3], float* __restrict__ U, size_t at,
                                                         size_t pos_stride) {
-    double t[6][3];
-#pragma unroll
-    for (int a = 0; a < 6; ++a)
-#pragma unroll
-        for (int b = 0; b < 3; ++b) t[a][b] = f4::kG[a][0] * g[0][b] + f4::kG[a][1] * g[1][b] + f4::kG[a][2] * g[2][b];
-#pragma unroll
-    for (int a = 0; a < 6; ++a)
-#pragma unroll
-        for (int b = 0; b < 6; ++b) {
-            const double u = t[a][0] * f4::kG[b][0] + t[a][1] * f4::kG[b][1] + t[a][2] * f4::kG[b][2];
-            U[(size_t)(a * 6 + b) * pos_stride + at] = (float)u;   // transformed in fp64, rounded once
-        }
+    winograd4_weight_transform(g, [&](int pos, float u) { U[(size_t)pos * pos_stride + at] = u; });
 }
 __global__ void winograd4_weight_kernel(const float* __restrict__ w, float* __restrict__ U, int Cout, int Cin, int Cout_p,
                                         int Cin_s) {
@@ -299,82 +288,10 @@ __global__ __launch_bounds__(256) void winograd4_input_kernel(const float2* __re
         }
     }
     const int ntiles = blockIdx.y == gridDim.y - 1 ? last_tiles : img_tiles;
+    const Wino4Input in{x, H, W, C2, TW, T, pad, reflect, mean_rstd, gamma, beta, res, xout};
+    // the arithmetic of one (tile, channel pair): winograd4_input_item (transform_common.h), stored as fp32
     auto item = [&](const long tile, const int c2) {
-        if (tile >= T) {   // padding tiles: zeros
-#pragma unroll
-            for (int xi = 0; xi < 36; ++xi) V[((long)xi * Tt + t0 + tile) * C2 + c2] = make_float2(0.f, 0.f);
-            return;
-        }
-        const int ty = (int)(tile / TW), tx = (int)(tile - (long)ty * TW);
-        int ry[6], rx[6];
-        bool oky[6], okx[6];
-#pragma unroll
-        for (int k = 0; k < 6; ++k) {
-            int yy = 4 * ty - pad + k, xx = 4 * tx - pad + k;
-            oky[k] = reflect || ((unsigned)yy < (unsigned)H);
-            okx[k] = reflect || ((unsigned)xx < (unsigned)W);
-            yy = yy < 0 ? -yy : yy;
-            xx = xx < 0 ? -xx : xx;
-            ry[k] = max(min(yy, 2 * H - 2 - yy), 0);   // past the reflected border: ragged tile, outputs masked
-            rx[k] = max(min(xx, 2 * W - 2 - xx), 0);
-        }
-        float2 mr0, mr1, gm = make_float2(1.f, 1.f), bt = make_float2(0.f, 0.f);
-        if (MODE) {
-            mr0 = mean_rstd[2 * c2];
-            mr1 = mean_rstd[2 * c2 + 1];
-            if (gamma) {
-                gm = gamma[c2];
-                bt = beta[c2];
-            }
-        }
-        // rows first: r[a][j] = sum_b B^T[j][b] d[a][b]
-        float rxv[6][6], ryv[6][6];
-#pragma unroll
-        for (int a = 0; a < 6; ++a) {
-            float2 d[6], r[6];
-#pragma unroll
-            for (int b = 0; b < 6; ++b) {
-                const long at = ((long)ry[a] * W + rx[b]) * C2 + c2;
-                d[b] = (oky[a] && okx[b]) ? x[at] : make_float2(0.f, 0.f);
-                if (MODE == 2) r[b] = (oky[a] && okx[b]) ? res[at] : make_float2(0.f, 0.f);
-            }
-            float dx[6], dy[6];
-#pragma unroll
-            for (int b = 0; b < 6; ++b) {
-                float2 v = d[b];
-                if (MODE && oky[a] && okx[b]) {
-                    v.x = norm_apply(v.x, mr0.x, mr0.y, gamma != nullptr, gm.x, bt.x, MODE == 1);
-                    v.y = norm_apply(v.y, mr1.x, mr1.y, gamma != nullptr, gm.y, bt.y, MODE == 1);
-                    if (MODE == 2) {
-                        v.x += r[b].x;
-                        v.y += r[b].y;
-                        // the tile's own pixels: rows / columns pad .. pad+3 of the patch, inside the map
-                        if (a >= pad && a < pad + 4 && b >= pad && b < pad + 4 && 4 * ty - pad + a < H && 4 * tx - pad + b < W)
-                            xout[((long)ry[a] * W + rx[b]) * C2 + c2] = v;
-                    }
-                }
-                dx[b] = v.x;
-                dy[b] = v.y;
-            }
-#pragma unroll
-            for (int j = 0; j < 6; ++j) {
-                rxv[a][j] = cdot<6>(f4::kBT[j], dx);
-                ryv[a][j] = cdot<6>(f4::kBT[j], dy);
-            }
-        }
-        // columns: v[a2][j] = sum_a B^T[a2][a] r[a][j]
-#pragma unroll
-        for (int j = 0; j < 6; ++j) {
-            float cx[6], cy[6];
-#pragma unroll
-            for (int a = 0; a < 6; ++a) {
-                cx[a] = rxv[a][j];
-                cy[a] = ryv[a][j];
-            }
-#pragma unroll
-            for (int a2 = 0; a2 < 6; ++a2)
-                V[((long)(a2 * 6 + j) * Tt + t0 + tile) * C2 + c2] = make_float2(cdot<6>(f4::kBT[a2], cx), cdot<6>(f4::kBT[a2], cy));
-        }
+        winograd4_input_item<MODE>(in, tile, c2, [&](int xi, float2 v) { V[((long)xi * Tt + t0 + tile) * C2 + c2] = v; });
     };
     if constexpr (XCD) {
         // XCD x owns the channel slices {x, x + 8, ..} of 64 pairs for ALL tiles (C2 % 512 == 0): the up to four tiles whose
@@ -406,7 +323,7 @@ static inline unsigned xcd_slice_grid(long tiles, int C2) {
 // lazy (packed layout only): x still has to go through its norm layer -- relu 1 = [ReLU](norm(x)); relu 0 = norm(x) + res
 // with the result also written to xout (both required)
 int launch_winograd4_input(hipStream_t s, const float* x, float* V, int H, int W, int C, int pad, int reflect, int batch,
-                           int image, int nimg, long img_stride, const LazyNorm* lazy) {
+                           int image, int nimg, long img_stride, const LazyNorm* lazy, bool split) {
     const LazyNorm none{};
     const LazyNorm& ln = lazy ? *lazy : none;
     const int mode = !lazy ? 0 : ln.relu ? 1 : 2;
@@ -425,6 +342,10 @@ int launch_winograd4_input(hipStream_t s, const float* x, float* V, int H, int W
     const int img_tiles = packed ? T : Tp, last_tiles = packed ? Tt - (n - 1) * T : Tp, t0 = packed ? 0 : image * Tp;
     const long most = last_tiles > img_tiles ? last_tiles : img_tiles;   // (packed: the image with the padding rows walks the most)
     const unsigned xg = xcd_slice_grid(most, C / 2);
+    if (split) {
+        T2V_REQUIRE(packed, "winograd4_input: the split-bf16 planes are written in the packed layout only");
+        return launch_winograd4_input_split(s, mode, x, V, H, W, C, tg, pad, reflect, Tt, n, img_stride, last_tiles, ln, xg);
+    }
     auto kern = xg ? (mode == 0 ? winograd4_input_kernel<0, true> : mode == 1 ? winograd4_input_kernel<1, true> : winograd4_input_kernel<2, true>)
                    : (mode == 0 ? winograd4_input_kernel<0, false> : mode == 1 ? winograd4_input_kernel<1, false> : winograd4_input_kernel<2, false>);
     hipLaunchKernelGGL(kern, dim3(xg ? xg : wg_grid(most * (C / 2), 256), n), dim3(256), 0, s,

@@ -170,14 +170,35 @@ def upload_tensors(tensors, device):
     return {k: v.detach().to(dev, torch.float32).contiguous() for k, v in tensors.items()}
 
 
+ARITHS = ("fp32", "bf16x2")
+
+
 class HipGenerator:
     """One generator scale resident on the GPU: packed weights + workspace + forward().
 
     Weights are packed lazily per frame geometry: the ResnetBlock convs use Winograd-transformed
     weights wherever the geometry supports it (t2v_generator_layer_desc reports the algorithm)."""
 
-    def __init__(self, spec, device="cuda", conv_algo=None):
+    def __init__(self, spec, device="cuda", conv_algo=None, arith="fp32"):
+        """arith: "fp32" (default: every kernel in exact fp32) | "bf16x2": the ResnetBlock trunk's F(4x4,3x3) GEMMs in
+        split-bf16 arithmetic (t2v_gen_desc.conv_algo 3; inference only).  Measured (DESIGN.md section 0,
+        profiles/split_bf16_accuracy.txt): 2.2e-5 of the output's rms per conv against 1.8e-7 for the fp32 pipeline -- the
+        Winograd-domain operands are an order larger than the output they cancel to, which amplifies the split error -- and
+        max |frame - float64| 1.8e-4 against 2.7e-5 (6.9x) on the 160 x 160 test generator, below the 1e-3 parity bar.
+        The mode is chosen by this argument only: conv_algo=3 without it, or T2V_CONV_ALGO=3, is refused."""
         import os
+        if arith not in ARITHS:
+            raise ValueError("arith=%r: one of %s" % (arith, ", ".join(ARITHS)))
+        if arith == "bf16x2":
+            if conv_algo not in (None, 0, _lib.CONV_ALGO_BF16X2):
+                raise ValueError("arith='bf16x2' selects the ResnetBlock algorithm itself (conv_algo=%r given)" % (conv_algo,))
+            conv_algo = _lib.CONV_ALGO_BF16X2
+        elif conv_algo == _lib.CONV_ALGO_BF16X2:
+            raise ValueError("conv_algo=3 is the split-bf16 trunk: select it with arith='bf16x2'")
+        elif conv_algo is None and int(os.environ.get("T2V_CONV_ALGO", "0")) == _lib.CONV_ALGO_BF16X2:
+            raise ValueError("T2V_CONV_ALGO=3: the split-bf16 trunk is selected with arith='bf16x2' (--arith bf16x2), not by the "
+                             "environment; T2V_CONV_ALGO takes 0, 1 or 2")
+        self.arith = arith
         self.spec = spec
         self.device = torch.device(device)
         self.ctx = ops.context(self.device)

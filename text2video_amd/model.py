@@ -77,7 +77,8 @@ def load_checkpoint(path):
 def create_model(opt, device="cuda:0", marks=None):
     marks = marks if marks is not None else {}
     if opt.fp16:
-        print("warning: --fp16 ignored, the MI355X path computes in exact fp32", file=sys.stderr)
+        print("warning: --fp16 ignored: the reduced-precision mode of the MI355X path is --arith bf16x2 "
+              "(without it every kernel computes in exact fp32)", file=sys.stderr)
     nets = []
     for s, spec in enumerate(generator_specs(opt)):
         path = os.path.join(opt.checkpoints_dir, opt.name, "%s_net_G%d.pth" % (opt.which_epoch, s))
@@ -99,7 +100,7 @@ def create_model(opt, device="cuda:0", marks=None):
         else:
             raise FileNotFoundError("%s not found (pass --synthetic_weights SEED to run without a checkpoint)" % path)
         t0 = time.perf_counter()
-        nets.append(HipGenerator(spec, device).load_state_dict(sd))
+        nets.append(HipGenerator(spec, device, arith=getattr(opt, "arith", "fp32")).load_state_dict(sd))
         torch.cuda.synchronize(device)
         marks["weights_to_device_s"] = marks.get("weights_to_device_s", 0.0) + time.perf_counter() - t0
         if getattr(torch, "LAST_UPLOAD", None):

@@ -12,7 +12,7 @@ from ._xp import torch     # the real torch, or leantorch under vid2vid/test.py'
 
 from . import _lib
 from ._lib import (ACT_FLOW_W, ACT_LRELU, ACT_NONE, ACT_TANH, ALGO_DIRECT, ALGO_WINOGRAD,  # noqa: F401
-                   ALGO_POLYPHASE, ALGO_WINOGRAD_F4, PAD_REFLECT, PAD_ZERO, ConvDesc, check)
+                   ALGO_POLYPHASE, ALGO_WINOGRAD_F4, ALGO_WINOGRAD_F4_BF16X2, PAD_REFLECT, PAD_ZERO, ConvDesc, check)
 
 _contexts = {}
 
@@ -84,6 +84,8 @@ def winograd_supported(desc, x_cs=None, algo=None):
     """True when `desc` can run as the Winograd variant `algo` (default: desc.algo, or F(2x2,3x3) for a direct desc)."""
     x_cs = round_up(desc.Cin, 4) if x_cs is None else x_cs
     algo = (desc.algo or ALGO_WINOGRAD) if algo is None else algo
+    if algo == ALGO_WINOGRAD_F4_BF16X2:
+        return bool(_lib.load().t2v_conv_winograd_bf16x2_supported(ctypes.byref(desc), x_cs))
     mask = _lib.load().t2v_conv_winograd_supported(ctypes.byref(desc), x_cs)
     return bool(mask & (2 if algo == ALGO_WINOGRAD_F4 else 1))
 
@@ -108,7 +110,7 @@ def best_conv_algo(desc, x_cs=None, cap=0):
 
 def conv2d_auto(x, packed_w, bias, desc, y_cs=None, stats=None, out=None):
     """conv2d or conv2d_winograd, whichever desc.algo (and the weight packing that goes with it) says."""
-    if desc.algo in (ALGO_WINOGRAD, ALGO_WINOGRAD_F4, ALGO_POLYPHASE):
+    if desc.algo in (ALGO_WINOGRAD, ALGO_WINOGRAD_F4, ALGO_WINOGRAD_F4_BF16X2, ALGO_POLYPHASE):
         assert y_cs is None or y_cs == desc.Cout
         return conv2d_winograd(x, packed_w, bias, desc, stats=stats, out=out)
     return conv2d(x, packed_w, bias, desc, y_cs=y_cs, stats=stats, out=out)
@@ -126,7 +128,8 @@ GEMM_FORMS = {0: "conv_igemm_kernel<64x64 tiles, one block per tile>", 1: "conv_
               4: "wino_gemm_sk_kernel<160x128 tiles on a fixed grid of 1 block per CU>",
               5: "wino_gemm_skr_kernel<ragged 128/96/64/32 x 128 tiles on a fixed grid of 2 blocks per CU>",
               6: "wino_gemm_sk_kernel<256x128 tiles on a fixed grid of 1 block per CU>",
-              7: "wino_gemm_skt_kernel<ragged 96..192 x 128 tiles on a fixed grid of 1 block per CU>"}
+              7: "wino_gemm_skt_kernel<ragged 96..192 x 128 tiles on a fixed grid of 1 block per CU>",
+              8: "wino_split_gemm_kernel<128x128 tiles, one block per tile, split-bf16 on the bf16 matrix cores>"}
 
 
 def winograd_gemm_form(desc, nimg=1):
@@ -147,7 +150,8 @@ def winograd_workspace(desc, x_cs, device):
 
 
 def conv2d_winograd(x, packed_u, bias, desc, stats=None, out=None, workspace=None, stages=7, keep_v=None):
-    """3x3 stride-1 reflect-pad-1 conv through Winograd (desc.algo: ALGO_WINOGRAD F(2x2,3x3) | ALGO_WINOGRAD_F4 F(4x4,3x3)).
+    """3x3 stride-1 reflect-pad-1 conv through Winograd (desc.algo: ALGO_WINOGRAD F(2x2,3x3) | ALGO_WINOGRAD_F4 F(4x4,3x3) |
+    ALGO_WINOGRAD_F4_BF16X2, F(4x4,3x3) with split-bf16 GEMMs: V and the packed weight then hold two bf16 planes).
     stages: bit mask 1 = input transform, 2 = batched GEMM, 4 = output transform (all by default).
     keep_v = (wgrad_ws, batch, slot): the input transform lands in that slot of the Winograd-domain weight gradient's workspace
     (backward_weight_winograd_workspace) and stays there for the backward pass (conv2d_backward_weight_winograd_dy)."""

@@ -1070,7 +1070,9 @@ class Vid2VidTrainer:
                                ("max_frames_backpropagate", getattr(opt, "max_frames_backpropagate", 1) > 1,
                                 "generated previous frames are always detached (the recipe's default, 1)"),
                                ("use_single_G", bool(getattr(opt, "use_single_G", False)), "no first-frame generator"),
-                               ("fg", bool(getattr(opt, "fg", False)), "no foreground / background generators")):
+                               ("fg", bool(getattr(opt, "fg", False)), "no foreground / background generators"),
+                               ("arith", getattr(opt, "arith", "fp32") != "fp32",
+                                "the split-bf16 trunk is a forward-only form; training computes in fp32")):
             if bad:
                 raise NotImplementedError("--%s: %s" % (flag, why))
         for flag, on in (("pool_size", getattr(opt, "pool_size", 1) > 1), ("niter_fix_global", getattr(opt, "niter_fix_global", 0) > 0)):
