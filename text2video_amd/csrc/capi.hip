@@ -500,13 +500,14 @@ int winograd_forward(t2v_ctx* ctx, hipStream_t s, const t2v_conv_desc* d, const 
     T2V_REQUIRE(!keep || (f4 && !split && nimg == 1 && wb.keep_slot >= 0 && wb.keep_slot < wb.keep_total),
                 "winograd: V is kept for the weight gradient of single F(4x4,3x3) images only");
     T2V_REQUIRE(!wb.v_in || (f4 && !keep && !(stages & 1)), "winograd: a borrowed V replaces the input transform (F(4x4,3x3))");
+    T2V_REQUIRE(!wb.lazy || (f4 && !keep), "winograd: the input transform applies a pending norm for F(4x4,3x3) into the call's own V");
     float* V = keep ? wb.keep_v + (size_t)wb.keep_slot * T * d->Cin : workspace;
     float* Mm = workspace + wino_pos(d->algo) * T * d->Cin;
     if (stages & 1) {
         const int reflect = d->pad_mode == T2V_PAD_REFLECT;
         if (keep) T2V_TRY(launch_winograd4_input(s, x, wb.keep_v, d->H, d->W, d->Cin, d->pad, reflect, wb.keep_total, wb.keep_slot));
         else
-        T2V_TRY(f4 ? launch_winograd4_input(s, x, V, d->H, d->W, d->Cin, d->pad, reflect, nimg, 0, nimg, wb.img_stride_x, nullptr, split)
+        T2V_TRY(f4 ? launch_winograd4_input(s, x, V, d->H, d->W, d->Cin, d->pad, reflect, nimg, 0, nimg, wb.img_stride_x, wb.lazy, split)
                    : launch_winograd_input(s, x, V, d->H, d->W, d->Cin, d->pad, reflect));
     }
     if ((stages & 2) && split) {   // V and w_packed hold bf16 plane pairs: one form, one block per tile (winograd_split.hip)
@@ -567,6 +568,37 @@ int polyphase_forward(t2v_ctx* ctx, hipStream_t s, const t2v_conv_desc* d, const
     if (stages & 4)
         T2V_TRY(launch_polyphase_output(s, Mm, bias, y, stats_partial, poly_out_h(d), poly_out_w(d), d->Cout, up, T));
     return T2V_OK;
+}
+
+size_t norm_partial_floats(const t2v_conv_desc* d, int x_cs) {
+    if (!d) return 0;
+    if (is_winograd(d->algo))   // one partial per 128 output-pixel slots of the padded tile grid
+        return (size_t)(wino_tiles_padded(d, d->algo) * wino_m(d->algo) * wino_m(d->algo) / 128) * d->Cout * 2;
+    if (d->algo == T2V_ALGO_POLYPHASE) return (size_t)(poly_tiles_padded(d) * poly_m(d) * poly_m(d) / 128) * d->Cout * 2;
+    ConvPlan pl;
+    if (build_conv_plan(d, x_cs, true, &pl) != T2V_OK) return 0;
+    return (size_t)pl.nparts * d->Cout * 2;
+}
+
+int finalize_norm(hipStream_t s, const t2v_conv_desc* producer, int x_cs, const float* stats, int pooled_images, float eps,
+                  float* mean_rstd, double* scratch, const RunningUpdate* ru, const ConvPlan* plan) {
+    if (producer && is_winograd(producer->algo))   // the output transform emits one partial per 128 pixels
+        return launch_inorm_finalize_winograd(s, stats, wino_m(producer->algo), wino_out_h(producer), wino_out_w(producer),
+                                              producer->Cout, eps, mean_rstd, pooled_images, scratch, ru);
+    if (producer && producer->algo == T2V_ALGO_POLYPHASE)
+        return launch_inorm_finalize_winograd(s, stats, poly_m(producer), poly_out_h(producer), poly_out_w(producer),
+                                              producer->Cout, eps, mean_rstd, pooled_images, scratch, ru);
+    ConvPlan own;
+    if (!plan) {
+        T2V_TRY(build_conv_plan(producer, x_cs, true, &own));
+        plan = &own;
+    }
+    if (plan->tile == kTileStem)
+        return launch_inorm_finalize_tiles(s, stats, 16, producer->H, producer->W, producer->Cout, eps, mean_rstd, pooled_images,
+                                           scratch, ru);
+    // the per-image partial blocks are contiguous: a batch is just `pooled_images` times more partial rows
+    return launch_inorm_finalize(s, stats, pooled_images * plan->nparts, plan->kp.mtiles, plan->BM, plan->kp.M, producer->Cout,
+                                 eps, mean_rstd, scratch, ru);
 }
 
 }  // namespace t2v
@@ -686,24 +718,37 @@ size_t t2v_conv_winograd_batch_workspace_floats(const t2v_conv_desc* d, int x_cs
     return winograd_workspace_floats(d, nimg);
 }
 
+// The generator's forms of a Winograd / polyphase conv (generator.hip: wino4_conv_stats, conv_norm_one) with the same launchers
+// and nothing of its own: nimg packed images (F(4x4) only) and, with `lazy`, the previous layer's norm applied inside the input
+// transform.  Both stage entries end here.
+static int winograd_stages(t2v_ctx* ctx, hipStream_t s, const t2v_conv_desc* d, int nimg, const float* x, int x_cs, long img_stride,
+                           const float* w_packed, const float* bias, float* y, int y_cs, float* stats_partial, float* workspace,
+                           int stages, const LazyNorm* lazy) {
+    if (d->algo == T2V_ALGO_POLYPHASE) {
+        T2V_REQUIRE(polyphase_supported(d, x_cs), "polyphase forward: shape not supported (t2v_conv_polyphase_supported)");
+        T2V_REQUIRE(y_cs == d->Cout, "polyphase forward: output channel storage must equal Cout");
+        T2V_REQUIRE(nimg == 1 && !(lazy && (lazy->res || lazy->xout)), "polyphase batch forward: one image, no residual");
+        return polyphase_forward(ctx, s, d, x, w_packed, bias, y, stats_partial, workspace, stages, lazy);
+    }
+    T2V_REQUIRE(winograd_supported(d, x_cs, d->algo), "winograd forward: shape/algo not supported (t2v_conv_winograd_supported)");
+    T2V_REQUIRE(y_cs == d->Cout, "winograd forward: output channel storage must equal Cout");
+    T2V_REQUIRE(is_f4(d->algo) || (nimg == 1 && !lazy), "winograd batch forward: batches and the lazy norm are F(4x4,3x3) only");
+    if (lazy && (stages & 1)) T2V_REQUIRE(lazy->relu == 0 || lazy->relu == 1, "winograd batch forward: relu %d", lazy->relu);
+    WinoBatch wb;
+    wb.nimg = nimg;
+    wb.img_stride_x = img_stride;
+    wb.lazy = lazy;
+    return winograd_forward(ctx, s, d, x, w_packed, bias, y, stats_partial, workspace, stages, &wb);
+}
+
 int t2v_conv2d_forward_winograd_stages(t2v_ctx* ctx, void* stream, const t2v_conv_desc* d, const float* x, int x_cs,
                                        const float* w_packed, const float* bias, float* y, int y_cs,
                                        float* stats_partial, float* workspace, int stages) {
     T2V_REQUIRE(ctx && d && x && w_packed && y && workspace, "winograd forward: null pointer");
-    if (d->algo == T2V_ALGO_POLYPHASE) {
-        T2V_REQUIRE(polyphase_supported(d, x_cs), "polyphase forward: shape not supported (t2v_conv_polyphase_supported)");
-        T2V_REQUIRE(y_cs == d->Cout, "polyphase forward: output channel storage must equal Cout");
-        return polyphase_forward(ctx, (hipStream_t)stream, d, x, w_packed, bias, y, stats_partial, workspace, stages);
-    }
-    T2V_REQUIRE(winograd_supported(d, x_cs, d->algo),
-                "winograd forward: shape/algo not supported (t2v_conv_winograd_supported)");
-    T2V_REQUIRE(y_cs == d->Cout, "winograd forward: output channel storage must equal Cout");
-    return winograd_forward(ctx, (hipStream_t)stream, d, x, w_packed, bias, y, stats_partial, workspace, stages);
+    return winograd_stages(ctx, (hipStream_t)stream, d, 1, x, x_cs, 0, w_packed, bias, y, y_cs, stats_partial, workspace, stages,
+                           nullptr);
 }
 
-// The generator's forms of a Winograd conv (generator.hip: wino4_conv_stats, conv_norm_one) with the same launchers and
-// nothing of its own: nimg packed images (F(4x4) only) and, with mean_rstd, the previous layer's norm applied inside the
-// input transform -- the LazyNorm of launch_winograd4_input for F(4x4) and of polyphase_forward.
 int t2v_conv2d_forward_winograd_batch_stages(t2v_ctx* ctx, void* stream, const t2v_conv_desc* d, int nimg, const float* x,
                                              int x_cs, long img_stride, const float* w_packed, const float* bias, float* y,
                                              int y_cs, float* stats_partial, float* workspace, int stages,
@@ -716,29 +761,9 @@ int t2v_conv2d_forward_winograd_batch_stages(t2v_ctx* ctx, void* stream, const t
                 img_stride);
     T2V_REQUIRE(mean_rstd || (!gamma && !beta && !res && !xout && relu == 0),
                 "winograd batch forward: gamma, beta, relu, res and xout need mean_rstd");
-    hipStream_t s = (hipStream_t)stream;
-    if (d->algo == T2V_ALGO_POLYPHASE) {
-        T2V_REQUIRE(polyphase_supported(d, x_cs), "polyphase forward: shape not supported (t2v_conv_polyphase_supported)");
-        T2V_REQUIRE(y_cs == d->Cout, "polyphase forward: output channel storage must equal Cout");
-        T2V_REQUIRE(nimg == 1 && !res && !xout, "polyphase batch forward: one image, no residual");
-        const LazyNorm ln{mean_rstd, gamma, beta, relu};
-        return polyphase_forward(ctx, s, d, x, w_packed, bias, y, stats_partial, workspace, stages, mean_rstd ? &ln : nullptr);
-    }
-    T2V_REQUIRE(winograd_supported(d, x_cs, d->algo), "winograd forward: shape/algo not supported (t2v_conv_winograd_supported)");
-    T2V_REQUIRE(y_cs == d->Cout, "winograd forward: output channel storage must equal Cout");
-    T2V_REQUIRE(is_f4(d->algo) || (nimg == 1 && !mean_rstd),
-                "winograd batch forward: batches and the lazy norm are F(4x4,3x3) only");
-    if (mean_rstd && (stages & 1)) {
-        T2V_REQUIRE(relu == 0 || relu == 1, "winograd batch forward: relu %d", relu);
-        const LazyNorm ln{mean_rstd, gamma, beta, relu, res, xout};
-        T2V_TRY(launch_winograd4_input(s, x, workspace, d->H, d->W, d->Cin, d->pad, d->pad_mode == T2V_PAD_REFLECT, nimg, 0, nimg,
-                                       img_stride, &ln, is_split(d->algo)));
-        stages &= ~1;
-    }
-    WinoBatch wb;
-    wb.nimg = nimg;
-    wb.img_stride_x = img_stride;
-    return winograd_forward(ctx, s, d, x, w_packed, bias, y, stats_partial, workspace, stages, &wb);
+    const LazyNorm ln{mean_rstd, gamma, beta, relu, res, xout};
+    return winograd_stages(ctx, (hipStream_t)stream, d, nimg, x, x_cs, img_stride, w_packed, bias, y, y_cs, stats_partial,
+                           workspace, stages, mean_rstd ? &ln : nullptr);
 }
 
 static bool wgrad_winograd_ok(const t2v_conv_desc* d, int x_cs, int dy_cs);
@@ -803,14 +828,7 @@ int t2v_conv_pack_weight_adjoint(t2v_ctx* ctx, void* stream, const t2v_conv_desc
     return pack_weight(ctx, stream, d, x_cs, w_forward_dev, packed_dev, 1);
 }
 
-size_t t2v_conv_stats_floats(const t2v_conv_desc* d) {
-    if (d && is_winograd(d->algo))   // one partial per 128 output-pixel slots of the padded tile grid
-        return (size_t)(wino_tiles_padded(d, d->algo) * wino_m(d->algo) * wino_m(d->algo) / 128) * d->Cout * 2;
-    if (d && d->algo == T2V_ALGO_POLYPHASE) return (size_t)(poly_tiles_padded(d) * poly_m(d) * poly_m(d) / 128) * d->Cout * 2;
-    ConvPlan pl;
-    if (!d || build_conv_plan(d, round_up(d->Cin, 4), true, &pl) != T2V_OK) return 0;
-    return (size_t)pl.nparts * d->Cout * 2;
-}
+size_t t2v_conv_stats_floats(const t2v_conv_desc* d) { return d ? norm_partial_floats(d, round_up(d->Cin, 4)) : 0; }
 
 int t2v_conv2d_forward(t2v_ctx* ctx, void* stream, const t2v_conv_desc* d, const float* x, int x_cs,
                        const float* w_packed, const float* bias, float* y, int y_cs, float* stats_partial) {
@@ -842,49 +860,19 @@ int t2v_conv2d_forward_batch(t2v_ctx* ctx, void* stream, const t2v_conv_desc* d,
     ConvPlan pl;
     T2V_TRY(build_conv_plan(d, x_cs, stats_partial != nullptr, &pl));
     return run_conv_batch(ctx, (hipStream_t)stream, pl, batch, x, (long)d->H * d->W * x_cs, w_packed, bias, y, y_cs,
-                          (long)pl.Hout * pl.Wout * y_cs, stats_partial, (long)t2v_conv_stats_floats(d));
+                          (long)pl.Hout * pl.Wout * y_cs, stats_partial, (long)norm_partial_floats(d, round_up(d->Cin, 4)));
 }
 
 int t2v_instance_norm_finalize(t2v_ctx* ctx, void* stream, const t2v_conv_desc* producer, const float* stats_partial,
                                float eps, float* mean_rstd) {
     T2V_REQUIRE(ctx && stats_partial && mean_rstd, "inorm_finalize: null pointer");
-    if (producer && is_winograd(producer->algo)) {   // the output transform emits one partial per 128 pixels
-        return launch_inorm_finalize_winograd((hipStream_t)stream, stats_partial, wino_m(producer->algo),
-                                              wino_out_h(producer), wino_out_w(producer), producer->Cout, eps, mean_rstd, 1);
-    }
-    if (producer && producer->algo == T2V_ALGO_POLYPHASE)
-        return launch_inorm_finalize_winograd((hipStream_t)stream, stats_partial, poly_m(producer), poly_out_h(producer),
-                                              poly_out_w(producer), producer->Cout, eps, mean_rstd, 1);
-    ConvPlan pl;
-    T2V_TRY(build_conv_plan(producer, round_up(producer ? producer->Cin : 0, 4), true, &pl));
-    if (pl.tile == kTileStem)
-        return launch_inorm_finalize_tiles((hipStream_t)stream, stats_partial, 16, producer->H, producer->W, producer->Cout, eps,
-                                           mean_rstd, 1);
-    return launch_inorm_finalize((hipStream_t)stream, stats_partial, pl.nparts, pl.kp.mtiles, pl.BM, pl.kp.M,
-                                 producer->Cout, eps, mean_rstd);
+    return finalize_norm((hipStream_t)stream, producer, round_up(producer ? producer->Cin : 0, 4), stats_partial, 1, eps, mean_rstd);
 }
 
-static int batch_norm_finalize(hipStream_t s, const t2v_conv_desc* producer, int batch, const float* stats_partial, float eps,
-                               float* mean_rstd, const RunningUpdate* ru) {
-    if (producer && is_winograd(producer->algo))
-        return launch_inorm_finalize_winograd(s, stats_partial, wino_m(producer->algo), wino_out_h(producer),
-                                              wino_out_w(producer), producer->Cout, eps, mean_rstd, batch, nullptr, ru);
-    if (producer && producer->algo == T2V_ALGO_POLYPHASE)
-        return launch_inorm_finalize_winograd(s, stats_partial, poly_m(producer), poly_out_h(producer), poly_out_w(producer),
-                                              producer->Cout, eps, mean_rstd, batch, nullptr, ru);
-    ConvPlan pl;
-    T2V_TRY(build_conv_plan(producer, round_up(producer ? producer->Cin : 0, 4), true, &pl));
-    if (pl.tile == kTileStem)
-        return launch_inorm_finalize_tiles(s, stats_partial, 16, producer->H, producer->W, producer->Cout, eps, mean_rstd, batch,
-                                           nullptr, ru);
-    // the per-image partial blocks are contiguous: a batch is just `batch` times more partial rows
-    return launch_inorm_finalize(s, stats_partial, batch * pl.nparts, pl.kp.mtiles, pl.BM, pl.kp.M, producer->Cout, eps,
-                                 mean_rstd, nullptr, ru);
-}
 int t2v_batch_norm_finalize(t2v_ctx* ctx, void* stream, const t2v_conv_desc* producer, int batch,
                             const float* stats_partial, float eps, float* mean_rstd) {
     T2V_REQUIRE(ctx && stats_partial && mean_rstd && batch >= 1, "batch_norm_finalize: bad arguments");
-    return batch_norm_finalize((hipStream_t)stream, producer, batch, stats_partial, eps, mean_rstd, nullptr);
+    return finalize_norm((hipStream_t)stream, producer, round_up(producer ? producer->Cin : 0, 4), stats_partial, batch, eps, mean_rstd);
 }
 int t2v_batch_norm_finalize_running(t2v_ctx* ctx, void* stream, const t2v_conv_desc* producer, int batch,
                                     const float* stats_partial, float eps, float* mean_rstd, float* running_mean,
@@ -896,7 +884,7 @@ int t2v_batch_norm_finalize_running(t2v_ctx* ctx, void* stream, const t2v_conv_d
     const long n = (long)batch * ho * wo;
     T2V_REQUIRE(n >= 2, "batch_norm_finalize_running: the unbiased variance needs at least two values per channel");
     const RunningUpdate ru{running_mean, running_var, (float)n, momentum, times};
-    return batch_norm_finalize((hipStream_t)stream, producer, batch, stats_partial, eps, mean_rstd, &ru);
+    return finalize_norm((hipStream_t)stream, producer, round_up(producer->Cin, 4), stats_partial, batch, eps, mean_rstd, nullptr, &ru);
 }
 
 // narrow-input regular convs (7x7 stems: 12 / 8 channels; the discriminators' 4x4 first layers: 8): fold the taps

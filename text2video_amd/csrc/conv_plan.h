@@ -76,10 +76,18 @@ struct WinoBatch {
     // v_in != null: the GEMM reads a V that another call made of the same input (same geometry and batch) instead of the
     // workspace's own; `stages` then leaves the input transform out
     const float* v_in = nullptr;
+    // lazy != null (F(4x4,3x3), own V): x is a raw conv output whose norm the input transform applies (stage bit 1)
+    const LazyNorm* lazy = nullptr;
 };
 int winograd_forward(t2v_ctx* ctx, hipStream_t s, const t2v_conv_desc* d, const float* x, const float* w_packed,
                      const float* bias, float* y, float* stats_partial, float* workspace, int stages,
                      const WinoBatch* batch = nullptr);
+// statistics partials one image of `d`'s output leaves for its norm (floats); 0 where the layer has no plan
+size_t norm_partial_floats(const t2v_conv_desc* d, int x_cs);
+// partials -> (mean, rstd) with the launcher that matches the producer's partial geometry; `pooled_images` images' partials
+// (back to back) pool into one table.  plan: the producer's direct-conv plan where the caller has built it already
+int finalize_norm(hipStream_t s, const t2v_conv_desc* producer, int x_cs, const float* stats, int pooled_images, float eps,
+                  float* mean_rstd, double* scratch = nullptr, const RunningUpdate* ru = nullptr, const ConvPlan* plan = nullptr);
 int run_conv(t2v_ctx* ctx, hipStream_t s, const ConvPlan& pl, const float* x, const float* w, const float* bias,
              float* y, int y_cs, float* stats);
 // the plan is one the dedicated 7x7 head kernel takes (conv_head.hip) ...

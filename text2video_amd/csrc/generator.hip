@@ -4,6 +4,12 @@
 // section 8a rows a4, a13).  Pure launch sequencing: every tensor lives in the caller's
 // workspace (bump-allocated here, identically by t2v_generator_workspace_bytes), nothing
 // synchronises, so a frame is ~150 back-to-back launches on the caller's stream.
+//
+// Norms applied by their consumers: a producer that next_takes_raw() allows (and a lazy ResnetBlock chain) leaves its conv
+// output raw and returns a Pending value -- the layer whose gamma / beta apply, the scratch set holding its (mean, rstd), relu,
+// a residual.  The next conv_norm / head / export_feat / the encoder join takes that value; lazy_norm() and join_side() turn it
+// into what the kernels read, discharge() runs the apply pass where no consumer does.
+#include <algorithm>
 #include <vector>
 
 #include "conv_plan.h"
@@ -41,6 +47,10 @@ struct LayerSpec {
     t2v_conv_desc cd;
     int x_cs;
     bool has_norm;
+    long out_px() const {      // pixels of the output map (the transposed layers: k3, s2, p1, output_padding 1)
+        if (cd.transposed) return 4L * cd.H * cd.W;
+        return (long)((cd.H + 2 * cd.pad - cd.kH) / cd.stride + 1) * ((cd.W + 2 * cd.pad - cd.kW) / cd.stride + 1);
+    }
 };
 
 // canonical layer list (the order documented in t2v.h)
@@ -159,18 +169,7 @@ void plan_buffers(const t2v_gen_desc& g, const std::vector<LayerSpec>& layers, i
     size_t max_stats = 0;
     int max_c = 4;
     for (const LayerSpec& L : layers) {
-        ConvPlan pl;
-        if (L.has_norm && is_winograd(L.cd.algo)) {
-            const int m = wino_m(L.cd.algo);
-            const size_t s = (size_t)(wino_tiles_padded(&L.cd, L.cd.algo) * m * m / 128) * L.cd.Cout * 2;
-            if (s > max_stats) max_stats = s;
-        } else if (L.has_norm && L.cd.algo == T2V_ALGO_POLYPHASE) {
-            const size_t s = (size_t)(poly_tiles_padded(&L.cd) * poly_m(&L.cd) * poly_m(&L.cd) / 128) * L.cd.Cout * 2;
-            if (s > max_stats) max_stats = s;
-        } else if (L.has_norm && build_conv_plan(&L.cd, L.x_cs, true, &pl) == T2V_OK) {
-            const size_t s = (size_t)pl.nparts * L.cd.Cout * 2;
-            if (s > max_stats) max_stats = s;
-        }
+        if (L.has_norm) max_stats = std::max(max_stats, norm_partial_floats(&L.cd, L.x_cs));
         if (L.cd.Cout > max_c) max_c = L.cd.Cout;
     }
     b.stats_stride = (max_stats + 63) / 64 * 64;
@@ -206,6 +205,19 @@ struct MutPtrs {
     }
 };
 
+// A raw conv output whose norm is still owed: the consumer (or discharge()) applies y = [relu](norm(x)) + res.  Nothing is
+// owed while layer < 0.  One value per batch: the images' (mean, rstd) tables sit mr_stride apart in scratch set `sc` until
+// that set's next finalize replaces them, a residual is the batch's bottleneck maps back to back.
+struct Pending {
+    int layer = -1;              // the layer whose statistics and gamma / beta apply
+    int sc = 0;                  // scratch set of the (mean, rstd) tables
+    int relu = 0;
+    const float* res = nullptr;
+    explicit operator bool() const { return layer >= 0; }
+};
+// what applies a pending norm: the forms that may carry one, and the rest
+enum class Takes { Applied, Polyphase, Head7x7, ChainF4 };
+
 struct Runner {
     t2v_ctx* ctx;
     hipStream_t s;
@@ -230,59 +242,75 @@ struct Runner {
     float* stats_of(int im) const { return b.stats[sc] + (size_t)im * b.stats_stride; }
     float* mr_of(int im) const { return b.mean_rstd[sc] + (size_t)im * b.mr_stride; }
     double* fin_of(int im) const { return b.fin[sc] + (size_t)im * b.fin_stride; }
-    // conv (+ fused stats) -> finalize -> apply of layer `l` for ONE image.  y receives the conv output and is
-    // normalised in place: y = [relu](norm(conv(x))) + res1 + res2
-    // lazy_in: x is layer l-1's raw conv output, whose (mean, rstd) still sit in mr_of(im) -- this (polyphase) layer's input
-    // transform normalises it; lazy_out: leave y raw for the next layer to do the same (no apply pass: a read and a write of
-    // the map less).  Same arithmetic in the same order: the frames are bit-identical to the apply form (T2V_CHAIN_LAZY=0).
-    int conv_norm_one(int l, int im, const float* x, float* y, int relu, const float* res1, const float* res2,
-                      bool lazy_in = false, bool lazy_out = false) {
-        const LayerSpec& L = specs[l];
-        const t2v_layer& w = layers[l];
-        ConvPlan pl;
-        const int Cout = L.cd.Cout;
-        float* stats = stats_of(im);
-        float* mr = mr_of(im);
-        const float* gam = g.norm_affine ? w.gamma : nullptr;
-        const float* bet = g.norm_affine ? w.beta : nullptr;
-        if (g.norm_affine) T2V_REQUIRE(gam && bet, "layer %d: norm_affine=1 but gamma/beta missing", l);
-        if (is_winograd(L.cd.algo)) {
-            const int M = L.cd.H * L.cd.W;
-            const int wm = wino_m(L.cd.algo);
-            WinoBatch wb;
-            T2V_TRY(winograd_forward(ctx, s, &L.cd, x, w.w, w.bias, y, stats, b.wino[sc], 7, &wb));
-            T2V_REQUIRE(!lazy_in && !lazy_out, "internal: a Winograd layer outside a chain takes and leaves applied norms");
-            T2V_TRY(launch_inorm_finalize_winograd(s, stats, wm, L.cd.H, L.cd.W, Cout, g.eps, mr, 1, fin_of(im)));
-            return launch_inorm_apply(s, y, mr, gam, bet, res1, res2, y, (long)M, Cout, relu);
-        }
-        T2V_REQUIRE(!lazy_out || (relu == 1 && !res1 && !res2), "internal: a lazy output carries a plain norm + ReLU");
-        if (L.cd.algo == T2V_ALGO_POLYPHASE) {
-            const int Ho = poly_out_h(&L.cd), Wo = poly_out_w(&L.cd);
-            const LazyNorm ln{mr, g.norm_affine ? layers[l - 1].gamma : nullptr, g.norm_affine ? layers[l - 1].beta : nullptr, 1};
-            T2V_TRY(polyphase_forward(ctx, s, &L.cd, x, w.w, w.bias, y, stats, b.wino[sc], 7, lazy_in ? &ln : nullptr));
-            T2V_TRY(launch_inorm_finalize_winograd(s, stats, poly_m(&L.cd), Ho, Wo, Cout, g.eps, mr, 1, fin_of(im)));
-            if (lazy_out) return T2V_OK;
-            return launch_inorm_apply(s, y, mr, gam, bet, res1, res2, y, (long)Ho * Wo, Cout, relu);
-        }
-        T2V_REQUIRE(!lazy_in, "internal: only the polyphase input transform applies a pending norm");
-        T2V_TRY(build_conv_plan(&L.cd, L.x_cs, true, &pl));
-        T2V_TRY(run_conv(ctx, s, pl, x, w.w, w.bias, y, Cout, stats));
-        if (pl.tile == kTileStem)
-            T2V_TRY(launch_inorm_finalize_tiles(s, stats, 16, L.cd.H, L.cd.W, Cout, g.eps, mr, 1, fin_of(im)));
-        else
-            T2V_TRY(launch_inorm_finalize(s, stats, pl.nparts, pl.kp.mtiles, pl.BM, pl.kp.M, Cout, g.eps, mr, fin_of(im)));
-        if (lazy_out) return T2V_OK;
-        return launch_inorm_apply(s, y, mr, gam, bet, res1, res2, y, (long)pl.Hout * pl.Wout, Cout, relu);
+
+    // the norm `p` owes the maps y, from image `im` on, as the join kernel takes it
+    NormJoinSide join_side(const Pending& p, int im, const float* y) const {
+        const t2v_layer& w = layers[p.layer];
+        return {y, b.mean_rstd[p.sc] + (size_t)im * b.mr_stride, g.norm_affine ? w.gamma : nullptr,
+                g.norm_affine ? w.beta : nullptr, p.res ? p.res + (size_t)im * b.bott : nullptr};
     }
-    // the next layer for every image of the batch (one launch sequence per image).  (The images of a lock-step batch as
+    // ... and as the input side of a consumer of form `by` takes it (xout: LazyNorm's side output, the chain only)
+    int lazy_norm(const Pending& p, int im, Takes by, float* xout, LazyNorm* out) const {
+        T2V_REQUIRE(by != Takes::Applied,
+                    "internal: only the polyphase input transform, the halo-tile head and a chain's F(4x4) input transform apply a pending norm");
+        if (by == Takes::ChainF4) {
+            T2V_REQUIRE(b.mr_stride == (size_t)2 * specs[p.layer].cd.Cout, "internal: chain scratch layout");
+            T2V_REQUIRE((p.relu == 0 || p.relu == 1) && (p.res != nullptr) == (xout != nullptr) && !(p.res && p.relu),
+                        "internal: a chain's pending norm is norm + ReLU, or norm + residual with the sum written on the side");
+        } else {
+            T2V_REQUIRE(p.relu == 1 && !p.res && !xout, "internal: a lazy output carries a plain norm + ReLU");
+        }
+        const NormJoinSide n = join_side(p, im, nullptr);
+        *out = LazyNorm{n.mean_rstd, n.gamma, n.beta, p.relu, n.res, xout};
+        return T2V_OK;
+    }
+    // the apply pass that nobody took over: dst = [relu](norm(src)) + res for `count` images from image `im` on
+    int discharge(const Pending& p, int im, int count, const float* src, float* dst) const {
+        const LayerSpec& L = specs[p.layer];
+        T2V_REQUIRE(count == 1 || b.mr_stride == (size_t)2 * L.cd.Cout, "internal: chain scratch layout");
+        const NormJoinSide n = join_side(p, im, src);
+        return launch_inorm_apply(s, n.y, n.mean_rstd, n.gamma, n.beta, n.res, nullptr, dst, L.out_px(), L.cd.Cout, p.relu, count);
+    }
+
+    // conv (+ fused stats) -> finalize of layer `own.layer` for ONE image; y receives the conv output.  `in`: the norm x still
+    // owes -- this (polyphase) layer's input transform applies it.  defer: leave y raw and `own` to the next layer (no apply
+    // pass: a read and a write of the map less), else y is normalised in place.  Same arithmetic in the same order: the frames
+    // are bit-identical to the apply form (T2V_CHAIN_LAZY=0).
+    int conv_norm_one(int im, const float* x, const Pending& in, float* y, const Pending& own, bool defer) {
+        const LayerSpec& L = specs[own.layer];
+        const t2v_layer& w = layers[own.layer];
+        float* stats = stats_of(im);
+        if (g.norm_affine) T2V_REQUIRE(w.gamma && w.beta, "layer %d: norm_affine=1 but gamma/beta missing", own.layer);
+        const bool poly = L.cd.algo == T2V_ALGO_POLYPHASE;
+        LazyNorm ln;
+        if (in) T2V_TRY(lazy_norm(in, im, poly ? Takes::Polyphase : Takes::Applied, nullptr, &ln));
+        ConvPlan pl;
+        const ConvPlan* plan = nullptr;
+        if (is_winograd(L.cd.algo)) {
+            T2V_REQUIRE(!defer, "internal: a Winograd layer outside a chain leaves an applied norm");
+            T2V_TRY(winograd_forward(ctx, s, &L.cd, x, w.w, w.bias, y, stats, b.wino[sc], 7));
+        } else if (poly) {
+            T2V_TRY(polyphase_forward(ctx, s, &L.cd, x, w.w, w.bias, y, stats, b.wino[sc], 7, in ? &ln : nullptr));
+        } else {
+            T2V_TRY(build_conv_plan(&L.cd, L.x_cs, true, &pl));
+            T2V_TRY(run_conv(ctx, s, pl, x, w.w, w.bias, y, L.cd.Cout, stats));
+            plan = &pl;
+        }
+        T2V_TRY(finalize_norm(s, &L.cd, L.x_cs, stats, 1, g.eps, mr_of(im), fin_of(im), nullptr, plan));
+        return defer ? T2V_OK : discharge(own, im, 1, y, y);
+    }
+    // the next layer for every image of the batch (one launch sequence per image): y = [relu](norm(conv(x))) + res, or with
+    // `defer` the raw conv output and that norm in *owed.  (The images of a lock-step batch as
     // blockIdx.y of ONE launch of the stride-2 / transposed convs -- run_conv_batch, what the train step's discriminators
     // use -- was measured here and dropped: 142.1 / 141.9 vs 142.1 / 141.7 fps for two 512x320 sequences, 67.0 / 66.7 vs
     // 66.8 / 66.7 at 512x680, 92.0 / 92.0 vs 91.8 / 91.7 at 512x512, alternating runs: inside two-stream frames the other
     // stream already fills what a 2.5-blocks-per-CU launch leaves idle.)
-    int conv_norm(const Ptrs& x, const MutPtrs& y, int relu, const Ptrs& res1, bool lazy_in = false, bool lazy_out = false) {
-        for (int im = 0; im < nimg; ++im)
-            T2V_TRY(conv_norm_one(li, im, x.p[im], y.p[im], relu, res1.p[im], nullptr, lazy_in, lazy_out));
+    int conv_norm(const Ptrs& x, Pending in, const MutPtrs& y, int relu, const float* res, bool defer = false,
+                  Pending* owed = nullptr) {
+        const Pending own{li, sc, relu, res};
+        for (int im = 0; im < nimg; ++im) T2V_TRY(conv_norm_one(im, x.p[im], in, y.p[im], own, defer));
         ++li;
+        if (owed) *owed = defer ? own : Pending{};
         return T2V_OK;
     }
     // the layer after the current one consumes this one's output, nothing else does, and it applies a pending norm itself:
@@ -295,17 +323,17 @@ struct Runner {
         return !nx.has_norm && build_conv_plan(&nx.cd, nx.x_cs, false, &pl) == T2V_OK && conv_plan_is_head7x7(pl);
     }
 
-    // x_raw: x is the last decoder layer's raw conv output, its (mean, rstd) still in mr_of(im): the head normalises it
-    int head(const Ptrs& x, const MutPtrs& y, bool x_raw) {
+    // in: the norm the last decoder layer left to the head
+    int head(const Ptrs& x, const Pending& in, const MutPtrs& y) {
         const LayerSpec& L = specs[li];
         const t2v_layer& w = layers[li];
-        const t2v_layer& prev = layers[li - 1];
         ++li;
         ConvPlan pl;
         T2V_TRY(build_conv_plan(&L.cd, L.x_cs, false, &pl));
         for (int im = 0; im < nimg; ++im) {
-            if (x_raw) {
-                const LazyNorm ln{mr_of(im), g.norm_affine ? prev.gamma : nullptr, g.norm_affine ? prev.beta : nullptr, 1};
+            if (in) {
+                LazyNorm ln;
+                T2V_TRY(lazy_norm(in, im, Takes::Head7x7, nullptr, &ln));
                 T2V_TRY(run_head7x7(s, pl, x.p[im], w.w, w.bias, y.p[im], 4, &ln));
             } else {
                 T2V_TRY(run_conv(ctx, s, pl, x.p[im], w.w, w.bias, y.p[im], 4, nullptr));
@@ -313,64 +341,51 @@ struct Runner {
         }
         return T2V_OK;
     }
-    // The feature map a caller asked for (the two-scale path's img_feat / flow_feat): a copy of the decoder output, or, where
-    // the decoder left it raw for the head, the apply pass the decoder skipped, written into the caller's buffer (the same
-    // traffic as the copy).  The layer whose norm is pending is the one before the head just run.
-    int export_feat(const float* feat, size_t stride, float* const* dst, bool raw) {
-        const LayerSpec& L = specs[li - 2];
-        const t2v_layer& w = layers[li - 2];
-        const size_t floats = (size_t)g.H * g.W * L.cd.Cout;
+    // The feature map a caller asked for (the two-scale path's img_feat / flow_feat; `stride` floats each): a copy of the
+    // decoder output, or, where the decoder left its norm to the head, the apply pass the decoder skipped, written into the
+    // caller's buffer (the same traffic as the copy).
+    int export_feat(const float* feat, size_t stride, const Pending& in, float* const* dst) {
         for (int im = 0; im < nimg; ++im) {
             if (!dst[im]) continue;
-            if (raw)
-                T2V_TRY(launch_inorm_apply(s, feat + im * stride, mr_of(im), g.norm_affine ? w.gamma : nullptr,
-                                           g.norm_affine ? w.beta : nullptr, nullptr, nullptr, dst[im], (long)g.H * g.W, L.cd.Cout, 1));
+            if (in)
+                T2V_TRY(discharge(in, im, 1, feat + im * stride, dst[im]));
             else
-                T2V_HIP_CHECK(hipMemcpyAsync(dst[im], feat + im * stride, floats * sizeof(float), hipMemcpyDeviceToDevice, s));
+                T2V_HIP_CHECK(hipMemcpyAsync(dst[im], feat + im * stride, stride * sizeof(float), hipMemcpyDeviceToDevice, s));
         }
         return T2V_OK;
     }
 
     // x + [pad1,conv3,N,ReLU,pad1,conv3,N](x), image by image
-    int resblock(const Ptrs& x, const MutPtrs& t, const MutPtrs& y) {
-        T2V_TRY(conv_norm(x, t, 1, Ptrs{}));
-        return conv_norm(t, y, 0, x);
+    int resblock(const float* x, float* t, float* y) {
+        T2V_TRY(conv_norm(at(x, b.bott), Pending{}, at(t, b.bott), 1, nullptr));
+        return conv_norm(at(t, b.bott), Pending{}, at(y, b.bott), 0, x);
     }
 
     // One F(4x4) Winograd conv of a chain over the whole batch (maps `bott` floats apart), up to and including the
-    // finalize of its norm statistics; the norm itself is left to the consumer.  `lz` (or null for a plain input map)
-    // describes the norm layer the INPUT still has to go through: the previous conv's, whose (mean, rstd) tables are in
-    // mean_rstd[sc] until this conv's finalize replaces them.
-    struct LazyIn {
-        const t2v_layer* norm;
-        int relu;
-        const float* res;
-        float* xout;
-    };
-    // v_in (lz == null only): the V of x that share_v() made; the input transform is left out
-    int wino4_conv_stats(const float* x, const LazyIn* lz, float* y_raw, const float* v_in = nullptr) {
+    // finalize of its norm statistics; the norm itself, [relu](norm(y_raw)) + res, is left to the consumer as *owed.
+    // `in` is the norm the INPUT still owes: the previous conv's, whose (mean, rstd) tables are in mean_rstd[sc] until this
+    // conv's finalize replaces them; xout as in LazyNorm.
+    // v_in (nothing owed only): the V of x that share_v() made; the input transform is left out
+    int wino4_conv_stats(const float* x, const Pending& in, float* xout, float* y_raw, int relu, const float* res, Pending* owed,
+                         const float* v_in = nullptr) {
         const LayerSpec& L = specs[li];
         const t2v_layer& w = layers[li];
+        *owed = Pending{li, sc, relu, res};
         ++li;
         const t2v_conv_desc& cd = L.cd;
-        if (g.norm_affine) T2V_REQUIRE(w.gamma && w.beta, "layer %d: norm_affine=1 but gamma/beta missing", li - 1);
-        T2V_REQUIRE(b.mr_stride == (size_t)2 * cd.Cout, "internal: chain scratch layout");
-        if (lz) {
-            const LazyNorm ln{b.mean_rstd[sc], g.norm_affine ? lz->norm->gamma : nullptr, g.norm_affine ? lz->norm->beta : nullptr,
-                              lz->relu, lz->res, lz->xout};
-            T2V_TRY(launch_winograd4_input(s, x, b.wino[sc], cd.H, cd.W, cd.Cin, cd.pad, cd.pad_mode == T2V_PAD_REFLECT, nimg, 0,
-                                           nimg, (long)b.bott, &ln, is_split(cd.algo)));
-        }
+        if (g.norm_affine) T2V_REQUIRE(w.gamma && w.beta, "layer %d: norm_affine=1 but gamma/beta missing", owed->layer);
+        LazyNorm ln;
+        if (in) T2V_TRY(lazy_norm(in, 0, Takes::ChainF4, xout, &ln));
         WinoBatch wb;
         wb.nimg = nimg;
         wb.img_stride_x = (long)b.bott;
-        wb.v_in = lz ? nullptr : v_in;
-        // the images' partials are packed back to back by the batched output transform: nparts*Cout*2 floats each
-        T2V_TRY(winograd_forward(ctx, s, &cd, x, w.w, w.bias, y_raw, b.stats[sc], b.wino[sc], (lz || v_in) ? 6 : 7, &wb));
-        const size_t per_img = (size_t)(wino_tiles_padded(&cd, cd.algo) / 8) * cd.Cout * 2;
+        wb.lazy = in ? &ln : nullptr;
+        wb.v_in = in ? nullptr : v_in;
+        // the images' partials are packed back to back by the batched output transform
+        T2V_TRY(winograd_forward(ctx, s, &cd, x, w.w, w.bias, y_raw, b.stats[sc], b.wino[sc], wb.v_in ? 6 : 7, &wb));
+        const size_t per_img = norm_partial_floats(&cd, L.x_cs);
         for (int im = 0; im < nimg; ++im)
-            T2V_TRY(launch_inorm_finalize_winograd(s, b.stats[sc] + im * per_img, 4, cd.H, cd.W, cd.Cout, g.eps, mr_of(im), 1,
-                                                   fin_of(im)));
+            T2V_TRY(finalize_norm(s, &cd, L.x_cs, b.stats[sc] + im * per_img, 1, g.eps, mr_of(im), fin_of(im)));
         return T2V_OK;
     }
 
@@ -378,43 +393,23 @@ struct Runner {
     // the residual) on the fly, and writes the block output the following block needs as ITS residual on the side.
     // Only the last norm of the chain runs as an apply pass.  Per block: 8 launches instead of 10 for the WHOLE batch, and one read + one write of the map less
     // per conv.  tmp: raw conv1 / conv2 outputs, block outputs (alternating); all hold the batch back to back.
-    // pend_out != null: the last norm is left to the caller as well (the encoder join applies both encoders' in one pass);
+    // defer: the last norm is left to the caller as well (the encoder join applies both encoders' in one pass);
     // v0: V of x, made by share_v()
-    struct PendingNorm {
-        const float* y;          // raw conv output
-        const float* res;        // the block input that is added to its norm
-        const t2v_layer* norm;
-    };
-    int res_chain_lazy(const float* x, int count, float* tmp[4], const float** out, PendingNorm* pend_out, const float* v0) {
+    int res_chain_lazy(const float* x, int count, float* tmp[4], const float** out, bool defer, Pending* owed, const float* v0) {
         const float* cur = x;
-        const t2v_layer* pend = nullptr;   // norm layer of the conv output waiting in tmp[1]
+        Pending end;      // what the conv output waiting in tmp[1] owes: its norm + the block input `cur`
         for (int i = 0; i < count; ++i) {
-            if (i == 0) {
-                T2V_TRY(wino4_conv_stats(x, nullptr, tmp[0], v0));
-            } else {
-                float* xi = tmp[2 + (i & 1)];
-                const LazyIn in{pend, 0, cur, xi};
-                T2V_TRY(wino4_conv_stats(tmp[1], &in, tmp[0]));
-                cur = xi;
-            }
-            const LazyIn mid{&layers[li - 1], 1, nullptr, nullptr};
-            T2V_TRY(wino4_conv_stats(tmp[0], &mid, tmp[1]));
-            pend = &layers[li - 1];
+            float* xi = i ? tmp[2 + (i & 1)] : nullptr;      // block i's input, written on the side by its first transform
+            Pending mid;
+            T2V_TRY(wino4_conv_stats(i ? tmp[1] : x, end, xi, tmp[0], 1, nullptr, &mid, i ? nullptr : v0));
+            if (i) cur = xi;
+            T2V_TRY(wino4_conv_stats(tmp[0], mid, nullptr, tmp[1], 0, cur, &end));
         }
         *out = tmp[1];
-        if (pend_out) {
-            *pend_out = {tmp[1], cur, pend};
-            return T2V_OK;
-        }
-        const LayerSpec& L = specs[li - 1];
-        T2V_TRY(launch_inorm_apply(s, tmp[1], b.mean_rstd[sc], g.norm_affine ? pend->gamma : nullptr,
-                                   g.norm_affine ? pend->beta : nullptr, cur, nullptr, tmp[1], (long)L.cd.H * L.cd.W,
-                                   L.cd.Cout, 0, nimg));
-        return T2V_OK;
+        *owed = defer ? end : Pending{};
+        return defer ? T2V_OK : discharge(end, 0, nimg, tmp[1], tmp[1]);
     }
 
-    // chain of `count` resblocks starting from x (never written; the batch back to back, `bott` floats apart); result
-    // pointer in *out.  tmp: 4 distinct buffers != x.
     // a chain of `count` blocks starting at layer l takes the lazy form
     bool chain_is_lazy(int l, int count) const {
         return options().chain_lazy && count > 0 && is_f4(specs[l].cd.algo) && b.mr_stride == (size_t)2 * specs[l].cd.Cout;
@@ -425,58 +420,54 @@ struct Runner {
         return launch_winograd4_input(s, x, b.vshare, cd.H, cd.W, cd.Cin, cd.pad, cd.pad_mode == T2V_PAD_REFLECT, nimg, 0, nimg,
                                       (long)b.bott, nullptr, is_split(cd.algo));
     }
-    int res_chain(const float* x, int count, float* tmp[4], const float** out, PendingNorm* pend_out = nullptr,
-                  const float* v0 = nullptr) {
-        if (chain_is_lazy(li, count)) return res_chain_lazy(x, count, tmp, out, pend_out, v0);
-        T2V_REQUIRE(!pend_out && !v0, "internal: only the lazy chain leaves its last norm pending / borrows a V");
+    // chain of `count` resblocks starting from x (never written; the batch back to back, `bott` floats apart); result
+    // pointer in *out, the norm it still owes (with `defer`, the lazy chain only) in *owed.  tmp: 4 distinct buffers != x.
+    int res_chain(const float* x, int count, float* tmp[4], const float** out, bool defer, Pending* owed, const float* v0 = nullptr) {
+        if (chain_is_lazy(li, count)) return res_chain_lazy(x, count, tmp, out, defer, owed, v0);
+        T2V_REQUIRE(!defer && !v0, "internal: only the lazy chain leaves its last norm pending / borrows a V");
         const float* cur = x;
         for (int i = 0; i < count; ++i) {
-            float* t = tmp[0];
             float* y = (cur == tmp[1]) ? tmp[2] : tmp[1];
-            T2V_TRY(resblock(at(cur, b.bott), at(t, b.bott), at(y, b.bott)));
+            T2V_TRY(resblock(cur, tmp[0], y));
             cur = y;
         }
         *out = cur;
+        *owed = Pending{};
         return T2V_OK;
     }
 
-    // c7,N,R, (d,N,R) x n, RB x nb
-    int encoder(const Ptrs& x, float** act, int nb, float* tmp[4], const float** out, PendingNorm* pend_out) {
+    // c7,N,R, (d,N,R) x n, RB x nb; defer: as res_chain
+    int encoder(const Ptrs& x, float** act, int nb, float* tmp[4], const float** out, bool defer, Pending* owed) {
         const int n = g.is_local ? 1 : g.n_downsample;
-        bool raw = n > 0 && next_takes_raw();      // (the stem's output feeds the first stride-2 layer only)
-        T2V_TRY(conv_norm(x, at(act[0], b.lvl[0]), 1, Ptrs{}, false, raw));
-        for (int i = 0; i < n; ++i) {
-            const bool raw_out = i + 1 < n && next_takes_raw();
-            T2V_TRY(conv_norm(at(act[i], b.lvl[i]), at(act[i + 1], b.lvl[i + 1]), 1, Ptrs{}, raw, raw_out));
-            raw = raw_out;
-        }
+        // (the stem's output feeds the first stride-2 layer only)
+        T2V_TRY(conv_norm(x, Pending{}, at(act[0], b.lvl[0]), 1, nullptr, n > 0 && next_takes_raw(), owed));
+        for (int i = 0; i < n; ++i)
+            T2V_TRY(conv_norm(at(act[i], b.lvl[i]), *owed, at(act[i + 1], b.lvl[i + 1]), 1, nullptr,
+                              i + 1 < n && next_takes_raw(), owed));
         if (nb == 0) {
-            T2V_REQUIRE(!pend_out, "internal: an encoder without blocks ends in an applied norm");
+            T2V_REQUIRE(!defer, "internal: an encoder without blocks ends in an applied norm");
             *out = act[n];
             return T2V_OK;
         }
-        return res_chain(act[n], nb, tmp, out, pend_out);
+        return res_chain(act[n], nb, tmp, out, defer, owed);
     }
 
-    // *out_raw: the last layer's output was left raw for the head (its (mean, rstd) in mr_of(im))
-    int decoder(const float* x, float** dec, const float** out, bool* out_raw) {
+    // *owed: the norm the last layer left to the head
+    int decoder(const float* x, float** dec, const float** out, Pending* owed) {
         const int n = g.is_local ? 1 : g.n_downsample;
         const float* cur = x;
         size_t cur_stride = b.bott;
-        bool raw = false;
+        *owed = Pending{};
         for (int i = 0; i < n; ++i) {
             const int l = n - 1 - i;
             float* y = dec[l];
             // (the direct 128 <-> 256 layers load by LDS-DMA with hardware zero padding and take no pending norm: has_norm
             // layers other than polyphase never answer next_takes_raw)
-            const bool raw_out = next_takes_raw();
-            T2V_TRY(conv_norm(at(cur, cur_stride), at(y, b.lvl[l]), 1, Ptrs{}, raw, raw_out));
-            raw = raw_out;
+            T2V_TRY(conv_norm(at(cur, cur_stride), *owed, at(y, b.lvl[l]), 1, nullptr, next_takes_raw(), owed));
             cur = y;
             cur_stride = b.lvl[l];
         }
         *out = cur;
-        *out_raw = raw;
         return T2V_OK;
     }
 };
@@ -593,16 +584,14 @@ int t2v_generator_forward_batch(t2v_ctx* ctx, void* stream, const t2v_gen_desc* 
     // Both chains lazy (they have the same layers): their closing norms + residuals and the sum of the two run as ONE pass
     // after the join instead of two apply passes and an add
     const bool fused_join = r.chain_is_lazy(1 + n, nb_enc);
-    Runner::PendingNorm pendA{}, pendB{};
-    T2V_TRY(r2.encoder(prevp, b.encB, nb_enc, tmpB, &imgout, fused_join ? &pendB : nullptr));
-    T2V_TRY(r.encoder(pose, b.encA, nb_enc, tmpA, &segout, fused_join ? &pendA : nullptr));
+    Pending owedA, owedB;
+    T2V_TRY(r2.encoder(prevp, b.encB, nb_enc, tmpB, &imgout, fused_join, &owedB));
+    T2V_TRY(r.encoder(pose, b.encA, nb_enc, tmpA, &segout, fused_join, &owedA));
     T2V_TRY(join());
     // (norm + x) + seg: the order the fused form summed in
     if (fused_join) {
-        const bool aff = d->norm_affine != 0;
-        const NormJoinSide sb{pendB.y, b.mean_rstd[r2.sc], aff ? pendB.norm->gamma : nullptr, aff ? pendB.norm->beta : nullptr, pendB.res};
-        const NormJoinSide sa{pendA.y, b.mean_rstd[r.sc], aff ? pendA.norm->gamma : nullptr, aff ? pendA.norm->beta : nullptr, pendA.res};
-        T2V_TRY(launch_inorm_join(s, sb, sa, b.d, (long)(d->H >> n) * (d->W >> n), G << n, batch));
+        T2V_TRY(launch_inorm_join(s, r2.join_side(owedB, 0, imgout), r.join_side(owedA, 0, segout), b.d,
+                                  (long)(d->H >> n) * (d->W >> n), G << n, batch));
     } else {
         T2V_TRY(launch_add(s, imgout, segout, b.d, (long)(batch * bott)));
     }
@@ -640,22 +629,22 @@ int t2v_generator_forward_batch(t2v_ctx* ctx, void* stream, const t2v_gen_desc* 
         T2V_TRY(r.share_v(2 * enc_layers, dsum));
         v0 = b.vshare;
     }
-    bool feat_raw = false;
+    Pending owed_img, owed_flow;      // one per branch: the branches run on two streams and share nothing
     if (!d->no_flow) {
         // flow branch on the side stream (temporaries bt2: the encoders are done with them)
         T2V_TRY(fork());
         r2.li = 2 * enc_layers + branch_layers;
         const float *res_flow, *flow_feat;
-        T2V_TRY(r2.res_chain(flow_in, nb_res, tmpB, &res_flow, nullptr, v0));
-        T2V_TRY(r2.decoder(res_flow, b.decF, &flow_feat, &feat_raw));
-        T2V_TRY(r2.head(r2.at(flow_feat, feat), fw, feat_raw));
-        T2V_TRY(r2.export_feat(flow_feat, feat, want_flow_feat, feat_raw));
+        T2V_TRY(r2.res_chain(flow_in, nb_res, tmpB, &res_flow, false, &owed_flow, v0));
+        T2V_TRY(r2.decoder(res_flow, b.decF, &flow_feat, &owed_flow));
+        T2V_TRY(r2.head(r2.at(flow_feat, feat), owed_flow, fw));
+        T2V_TRY(r2.export_feat(flow_feat, feat, owed_flow, want_flow_feat));
     }
     const float *res_img, *img_feat;
-    T2V_TRY(r.res_chain(img_in, nb_res, tmpA, &res_img, nullptr, v0));
-    T2V_TRY(r.decoder(res_img, b.decI, &img_feat, &feat_raw));
-    T2V_TRY(r.head(r.at(img_feat, feat), raw, feat_raw));
-    T2V_TRY(r.export_feat(img_feat, feat, want_img_feat, feat_raw));
+    T2V_TRY(r.res_chain(img_in, nb_res, tmpA, &res_img, false, &owed_img, v0));
+    T2V_TRY(r.decoder(res_img, b.decI, &img_feat, &owed_img));
+    T2V_TRY(r.head(r.at(img_feat, feat), owed_img, raw));
+    T2V_TRY(r.export_feat(img_feat, feat, owed_img, want_img_feat));
     if (!d->no_flow) {
         T2V_TRY(join());
         r.li += branch_layers;
