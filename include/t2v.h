@@ -31,6 +31,8 @@
 extern "C" {
 #endif
 
+/* (T2V_ALGO_POLYPHASE_BF16X2, t2v_conv_polyphase_bf16x2_supported and t2v_gen_desc.conv_algo 4 came after 22 and left it
+ * alone: they add a symbol and values, no existing entry, struct or value changed.) */
 #define T2V_ABI_VERSION 22
 
 typedef enum {
@@ -71,9 +73,15 @@ enum { T2V_ACT_NONE = 0, T2V_ACT_TANH = 1, T2V_ACT_FLOW_W = 2 /* ch0,1: x*20 ; c
  * upstream's --fp16 offered; SpatialConvolutionMM_updateOutput, THCUNN.h:664, as THCUNN's half instantiation ran it.)  The
  * transforms, bias and statistics are WINOGRAD_F4's fp32 arithmetic.  V and U hold two bf16 planes in the bytes of the fp32
  * tensors: every size is WINOGRAD_F4's.  Forward only, where t2v_conv_winograd_bf16x2_supported() says so; never chosen by
- * t2v_conv_best_algo -- a caller opts in (t2v_gen_desc.conv_algo 3). */
+ * t2v_conv_best_algo -- a caller opts in (t2v_gen_desc.conv_algo 3).
+ * POLYPHASE_BF16X2 = POLYPHASE with its 81 GEMMs in the same split-bf16 arithmetic on the same kernel (SpatialConvolutionMM /
+ * SpatialFullDilatedConvolution, THCUNN.h:664,794, as THCUNN's half instantiations ran them).  Transforms, bias and statistics
+ * are POLYPHASE's fp32 arithmetic; V and U hold two bf16 planes in the bytes of the fp32 tensors, so every size is POLYPHASE's.
+ * The F(4,2) operands are milder than F(4x4,3x3)'s: the float64 emulation of the form gives 1.7e-5 of the output's rms per
+ * conv.  Forward only, where t2v_conv_polyphase_bf16x2_supported() says so; never chosen by t2v_conv_best_algo -- a caller
+ * opts in (t2v_gen_desc.conv_algo 4). */
 enum { T2V_ALGO_DIRECT = 0, T2V_ALGO_WINOGRAD = 1, T2V_ALGO_WINOGRAD_F4 = 2, T2V_ALGO_POLYPHASE = 3,
-       T2V_ALGO_WINOGRAD_F4_BF16X2 = 4 };
+       T2V_ALGO_WINOGRAD_F4_BF16X2 = 4, T2V_ALGO_POLYPHASE_BF16X2 = 5 };
 
 typedef struct t2v_ctx t2v_ctx;
 
@@ -182,6 +190,11 @@ int t2v_conv_winograd_bf16x2_supported(const t2v_conv_desc* d, int x_cs);
  * transposed conv with pad 1 / output_padding 1; x_cs == Cin, Cin % 32 == 0, Cout % 128 == 0, no activation.  The tile grid
  * (4x4 outputs | 4x4 inputs) is ragged at the bottom / right edge and padded with empty tiles, as for the Winograd forms.  t2v_generator_layer_desc() selects it where it measured faster. */
 int t2v_conv_polyphase_supported(const t2v_conv_desc* d, int x_cs);
+/* 1 where `d` (algo ignored) can run as T2V_ALGO_POLYPHASE_BF16X2: bit 0 of t2v_conv_polyphase_supported (which asks
+ * x_cs == Cin, Cin % 32 == 0 and Cout % 128 == 0, the split GEMM's K stage and tile width) and V and U within the GEMM's
+ * 32-bit byte offsets (81 * rows * Cin * 4 bytes each, rows = the padded tile count | Cout).  Every backward, weight-gradient
+ * and data-gradient entry and query refuses a descriptor whose algo is T2V_ALGO_POLYPHASE_BF16X2. */
+int t2v_conv_polyphase_bf16x2_supported(const t2v_conv_desc* d, int x_cs);
 /* The algorithm the library itself would pick for `d` (d->algo ignored): the one with the fewest GEMM rows among
  * direct (9 per output pixel), F(2x2,3x3) and F(4x4,3x3) (16 | 36 per tile, tile count padded to 128).
  * cap: 0 = any, 1 = direct only, 2 = at most F(2x2,3x3).  Returns a T2V_ALGO_* value. */
@@ -509,7 +522,9 @@ typedef struct {
     int conv_algo;      /* ResnetBlock convs: 0 = best supported of F(4x4,3x3) > F(2x2,3x3) > direct;
                          * 1 = direct only; 2 = F(2x2,3x3) or direct; 3 (ABI 22) = as 0, with every ResnetBlock conv that 0
                          * runs as F(4x4,3x3) and t2v_conv_winograd_bf16x2_supported() accepts as
-                         * T2V_ALGO_WINOGRAD_F4_BF16X2 (the reduced-precision mode; workspace sizes are those of 0) */
+                         * T2V_ALGO_WINOGRAD_F4_BF16X2 (the reduced-precision mode; workspace sizes are those of 0);
+                         * 4 = as 3, and every stride-2 / transposed layer that 0 runs as T2V_ALGO_POLYPHASE and
+                         * t2v_conv_polyphase_bf16x2_supported() accepts as T2V_ALGO_POLYPHASE_BF16X2 (same sizes) */
 } t2v_gen_desc;
 
 typedef struct {

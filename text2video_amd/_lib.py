@@ -20,6 +20,8 @@ MAX_BATCH = 8     # T2V_MAX_BATCH
 ALGO_DIRECT, ALGO_WINOGRAD, ALGO_WINOGRAD_F4, ALGO_POLYPHASE = 0, 1, 2, 3
 ALGO_WINOGRAD_F4_BF16X2 = 4     # F(4x4,3x3) with split-bf16 GEMMs: forward only, opt-in (t2v_gen_desc.conv_algo 3)
 CONV_ALGO_BF16X2 = 3            # t2v_gen_desc.conv_algo: the selection of 0 with its F(4x4,3x3) trunk in split-bf16 arithmetic
+ALGO_POLYPHASE_BF16X2 = 5       # polyphase F(4,2) with split-bf16 GEMMs: forward only, opt-in (t2v_gen_desc.conv_algo 4)
+CONV_ALGO_BF16X2_STRIDE2 = 4    # t2v_gen_desc.conv_algo: 3, and the polyphase stride-2 / transposed layers in split-bf16 as well
 
 
 class ConvDesc(Structure):
@@ -74,6 +76,7 @@ SIGNATURES = {
     "t2v_conv_winograd_supported": (c_int, [POINTER(ConvDesc), c_int]),
     "t2v_conv_winograd_bf16x2_supported": (c_int, [POINTER(ConvDesc), c_int]),
     "t2v_conv_polyphase_supported": (c_int, [POINTER(ConvDesc), c_int]),
+    "t2v_conv_polyphase_bf16x2_supported": (c_int, [POINTER(ConvDesc), c_int]),
     "t2v_conv_best_algo": (c_int, [POINTER(ConvDesc), c_int, c_int]),
     "t2v_conv_winograd_workspace_floats": (c_size_t, [POINTER(ConvDesc), c_int]),
     "t2v_conv_winograd_batch_workspace_floats": (c_size_t, [POINTER(ConvDesc), c_int, c_int]),

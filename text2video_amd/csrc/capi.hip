@@ -297,6 +297,11 @@ bool winograd_supported(const t2v_conv_desc* d, int x_cs, int algo) {
 }
 // Training is fp32: every backward, weight-gradient and data-gradient entry turns a split-bf16 descriptor away by name
 static bool refuses_split(const t2v_conv_desc* d, const char* entry) {
+    if (d && is_poly_split(d->algo)) {
+        set_error("%s: T2V_ALGO_POLYPHASE_BF16X2 (algo 5) is a forward-only form; gradients run in fp32 (algo %d)", entry,
+                  T2V_ALGO_POLYPHASE);
+        return true;
+    }
     if (!d || !is_split(d->algo)) return false;
     set_error("%s: T2V_ALGO_WINOGRAD_F4_BF16X2 (algo 4) is a forward-only form; gradients run in fp32 (algo %d)", entry,
               T2V_ALGO_WINOGRAD_F4);
@@ -511,7 +516,7 @@ int winograd_forward(t2v_ctx* ctx, hipStream_t s, const t2v_conv_desc* d, const 
                    : launch_winograd_input(s, x, V, d->H, d->W, d->Cin, d->pad, reflect));
     }
     if ((stages & 2) && split) {   // V and w_packed hold bf16 plane pairs: one form, one block per tile (winograd_split.hip)
-        T2V_TRY(launch_wino_split_gemm(s, wb.v_in ? wb.v_in : V, w_packed, Mm, (int)T, d->Cin, d->Cout));
+        T2V_TRY(launch_wino_split_gemm(s, 36, wb.v_in ? wb.v_in : V, w_packed, Mm, (int)T, d->Cin, d->Cout));
     } else if (stages & 2) {
         PositionGemm g;
         g.has_scratch = f4;      // (F(2x2)'s workspace has none: winograd_workspace_floats)
@@ -549,6 +554,15 @@ bool polyphase_supported(const t2v_conv_desc* d, int x_cs) {
 bool polyphase_pays(const t2v_conv_desc* d, int x_cs) {
     return polyphase_supported(d, x_cs) && d->Cin >= 256 && d->Cout >= 256 && poly_tiles_real(d) >= 128;
 }
+// the split-bf16 form: the same layers where the 81-position GEMM takes the shape (Cin % 32 and Cout % 128 are asked above)
+bool polyphase_split_supported(const t2v_conv_desc* d, int x_cs) {
+    return polyphase_supported(d, x_cs) && wino_split_gemm_ok(81, poly_tiles_padded(d), d->Cin, d->Cout);
+}
+
+// the form d->algo names (T2V_ALGO_POLYPHASE | T2V_ALGO_POLYPHASE_BF16X2) takes the layer
+static bool poly_form_supported(const t2v_conv_desc* d, int x_cs) {
+    return is_poly_split(d->algo) ? polyphase_split_supported(d, x_cs) : polyphase_supported(d, x_cs);
+}
 
 // stages bit 1 = input transform, 2 = the 81 batched GEMMs, 4 = output transform (bias, statistics partials)
 int polyphase_forward(t2v_ctx* ctx, hipStream_t s, const t2v_conv_desc* d, const float* x, const float* w_packed,
@@ -559,8 +573,11 @@ int polyphase_forward(t2v_ctx* ctx, hipStream_t s, const t2v_conv_desc* d, const
     const int T = poly_tiles_padded(d), rows = poly_tiles_real(d);
     float* V = workspace;
     float* Mm = workspace + (size_t)81 * T * d->Cin;
-    if (stages & 1) T2V_TRY(launch_polyphase_input(s, x, V, d->H, d->W, d->Cin, up, T, lazy));
-    if (stages & 2) {
+    const bool split = is_poly_split(d->algo);
+    if (stages & 1) T2V_TRY(launch_polyphase_input(s, x, V, d->H, d->W, d->Cin, up, T, lazy, split));
+    if ((stages & 2) && split) {   // V and w_packed hold bf16 plane pairs (polyphase_split.hip); the scratch is left alone
+        T2V_TRY(launch_wino_split_gemm(s, 81, V, w_packed, Mm, T, d->Cin, d->Cout));
+    } else if (stages & 2) {
         PositionGemm g;
         g.groups = 81; g.rows = rows; g.T = T; g.K = d->Cin; g.N = d->Cout;
         T2V_TRY(run_position_gemm(ctx, s, g, V, w_packed, Mm, workspace + (size_t)81 * T * ((size_t)d->Cin + d->Cout)));
@@ -574,7 +591,7 @@ size_t norm_partial_floats(const t2v_conv_desc* d, int x_cs) {
     if (!d) return 0;
     if (is_winograd(d->algo))   // one partial per 128 output-pixel slots of the padded tile grid
         return (size_t)(wino_tiles_padded(d, d->algo) * wino_m(d->algo) * wino_m(d->algo) / 128) * d->Cout * 2;
-    if (d->algo == T2V_ALGO_POLYPHASE) return (size_t)(poly_tiles_padded(d) * poly_m(d) * poly_m(d) / 128) * d->Cout * 2;
+    if (is_poly(d->algo)) return (size_t)(poly_tiles_padded(d) * poly_m(d) * poly_m(d) / 128) * d->Cout * 2;
     ConvPlan pl;
     if (build_conv_plan(d, x_cs, true, &pl) != T2V_OK) return 0;
     return (size_t)pl.nparts * d->Cout * 2;
@@ -585,7 +602,7 @@ int finalize_norm(hipStream_t s, const t2v_conv_desc* producer, int x_cs, const 
     if (producer && is_winograd(producer->algo))   // the output transform emits one partial per 128 pixels
         return launch_inorm_finalize_winograd(s, stats, wino_m(producer->algo), wino_out_h(producer), wino_out_w(producer),
                                               producer->Cout, eps, mean_rstd, pooled_images, scratch, ru);
-    if (producer && producer->algo == T2V_ALGO_POLYPHASE)
+    if (producer && is_poly(producer->algo))
         return launch_inorm_finalize_winograd(s, stats, poly_m(producer), poly_out_h(producer), poly_out_w(producer),
                                               producer->Cout, eps, mean_rstd, pooled_images, scratch, ru);
     ConvPlan own;
@@ -689,9 +706,10 @@ size_t t2v_conv_packed_weight_floats(const t2v_conv_desc* d, int x_cs) {
     ConvPlan pl;
     if (build_conv_plan(d, x_cs, false, &pl) != T2V_OK) return 0;
     if (is_winograd(d->algo)) return winograd_supported(d, x_cs, d->algo) ? (size_t)wino_pos(d->algo) * pl.Cout_p * x_cs : 0;
-    if (d->algo == T2V_ALGO_POLYPHASE) return polyphase_supported(d, x_cs) ? (size_t)81 * pl.Cout_p * x_cs : 0;
+    if (is_poly(d->algo)) return poly_form_supported(d, x_cs) ? (size_t)81 * pl.Cout_p * x_cs : 0;
     return pl.wfloats;
 }
+int t2v_conv_polyphase_bf16x2_supported(const t2v_conv_desc* d, int x_cs) { return polyphase_split_supported(d, x_cs) ? 1 : 0; }
 int t2v_conv_polyphase_supported(const t2v_conv_desc* d, int x_cs) {
     return (polyphase_supported(d, x_cs) ? 1 : 0) | (polyphase_pays(d, x_cs) ? 2 : 0);
 }
@@ -706,14 +724,14 @@ int t2v_conv_winograd_bf16x2_supported(const t2v_conv_desc* d, int x_cs) {
 int t2v_conv_best_algo(const t2v_conv_desc* d, int x_cs, int cap) { return d ? best_conv_algo(d, x_cs, cap) : T2V_ALGO_DIRECT; }
 
 size_t t2v_conv_winograd_workspace_floats(const t2v_conv_desc* d, int x_cs) {
-    if (d && d->algo == T2V_ALGO_POLYPHASE) return polyphase_supported(d, x_cs) ? polyphase_workspace_floats(d) : 0;
+    if (d && is_poly(d->algo)) return poly_form_supported(d, x_cs) ? polyphase_workspace_floats(d) : 0;
     if (!d || !winograd_supported(d, x_cs, d->algo)) return 0;
     return winograd_workspace_floats(d);
 }
 
 size_t t2v_conv_winograd_batch_workspace_floats(const t2v_conv_desc* d, int x_cs, int nimg) {
     if (!d || nimg < 1) return 0;
-    if (d->algo == T2V_ALGO_POLYPHASE) return nimg == 1 && polyphase_supported(d, x_cs) ? polyphase_workspace_floats(d) : 0;
+    if (is_poly(d->algo)) return nimg == 1 && poly_form_supported(d, x_cs) ? polyphase_workspace_floats(d) : 0;
     if (!winograd_supported(d, x_cs, d->algo) || (nimg > 1 && !is_f4(d->algo))) return 0;
     return winograd_workspace_floats(d, nimg);
 }
@@ -724,8 +742,9 @@ size_t t2v_conv_winograd_batch_workspace_floats(const t2v_conv_desc* d, int x_cs
 static int winograd_stages(t2v_ctx* ctx, hipStream_t s, const t2v_conv_desc* d, int nimg, const float* x, int x_cs, long img_stride,
                            const float* w_packed, const float* bias, float* y, int y_cs, float* stats_partial, float* workspace,
                            int stages, const LazyNorm* lazy) {
-    if (d->algo == T2V_ALGO_POLYPHASE) {
-        T2V_REQUIRE(polyphase_supported(d, x_cs), "polyphase forward: shape not supported (t2v_conv_polyphase_supported)");
+    if (is_poly(d->algo)) {
+        T2V_REQUIRE(poly_form_supported(d, x_cs), "polyphase forward: shape not supported (t2v_conv_polyphase_supported, "
+                                                  "t2v_conv_polyphase_bf16x2_supported)");
         T2V_REQUIRE(y_cs == d->Cout, "polyphase forward: output channel storage must equal Cout");
         T2V_REQUIRE(nimg == 1 && !(lazy && (lazy->res || lazy->xout)), "polyphase batch forward: one image, no residual");
         return polyphase_forward(ctx, s, d, x, w_packed, bias, y, stats_partial, workspace, stages, lazy);
@@ -799,9 +818,11 @@ static int pack_weight(t2v_ctx* ctx, void* stream, const t2v_conv_desc* d, int x
     ConvPlan pl;
     T2V_TRY(build_conv_plan(d, x_cs, false, &pl));
     hipStream_t s = (hipStream_t)stream;
-    if (d->algo == T2V_ALGO_POLYPHASE) {
-        T2V_REQUIRE(polyphase_supported(d, x_cs) && !adjoint, "pack_weight: polyphase form not supported for this shape");
-        return launch_polyphase_weight(s, w_torch_dev, packed_dev, d->Cout, d->Cin, pl.Cout_p, x_cs, d->transposed ? 1 : 0);
+    if (is_poly(d->algo)) {
+        T2V_REQUIRE(poly_form_supported(d, x_cs) && !adjoint, "pack_weight: polyphase form not supported for this shape");
+        const bool split = is_poly_split(d->algo);
+        T2V_REQUIRE(!split || pl.Cout_p == d->Cout, "pack_weight: the split-bf16 planes have no padding rows");
+        return launch_polyphase_weight(s, w_torch_dev, packed_dev, d->Cout, d->Cin, pl.Cout_p, x_cs, d->transposed ? 1 : 0, split);
     }
     if (is_winograd(d->algo)) {
         T2V_REQUIRE(winograd_supported(d, x_cs, d->algo), "pack_weight: Winograd not supported for this shape");
@@ -824,6 +845,7 @@ int t2v_conv_pack_weight(t2v_ctx* ctx, void* stream, const t2v_conv_desc* d, int
 }
 int t2v_conv_pack_weight_adjoint(t2v_ctx* ctx, void* stream, const t2v_conv_desc* d, int x_cs, const float* w_forward_dev,
                                  float* packed_dev) {
+    T2V_REFUSE_SPLIT(d, "conv_pack_weight_adjoint");      // (before the shape: a forward-only form is refused by name)
     T2V_REQUIRE(d && !d->transposed && d->stride == 1, "pack_weight_adjoint: `d` must be a stride-1 (data-gradient) conv");
     return pack_weight(ctx, stream, d, x_cs, w_forward_dev, packed_dev, 1);
 }
@@ -942,7 +964,7 @@ static bool wgrad_combine_on() { return options().wgrad_combine != 0; }
 
 size_t t2v_conv_backward_weight_workspace_floats(const t2v_conv_desc* d, int x_cs, int batch) {
     ConvPlan pl;
-    if (!d || is_split(d->algo) || build_conv_plan(d, x_cs, true, &pl) != T2V_OK) return 0;
+    if (!d || is_bf16x2(d->algo) || build_conv_plan(d, x_cs, true, &pl) != T2V_OK) return 0;
     const int dy_cs = round_up(d->Cout, 4);
     if (wgrad_fold_n(d, x_cs, dy_cs)) {   // padded input copy + the partials of its own split rule
         const long nk = ((long)batch * (d->H + 2 * d->pad) * (d->W + 2 * d->pad) + 31) / 32;
@@ -1060,7 +1082,7 @@ int t2v_conv2d_backward_weight(t2v_ctx* ctx, void* stream, const t2v_conv_desc* 
 }
 int t2v_conv_backward_weight_strided_supported(const t2v_conv_desc* d, int x_cs, int dy_cs) {
     ConvPlan pl;
-    if (!d || is_split(d->algo) || build_conv_plan(d, x_cs, true, &pl) != T2V_OK) return 0;
+    if (!d || is_bf16x2(d->algo) || build_conv_plan(d, x_cs, true, &pl) != T2V_OK) return 0;
     if ((wgrad_fold_n(d, x_cs, dy_cs) && dy_cs == round_up(d->Cout, 4)) || wgrad_fold(d, x_cs)) return 0;
     WgradParams w;
     memset(&w, 0, sizeof(w));
@@ -1079,13 +1101,13 @@ int t2v_conv2d_backward_weight_strided(t2v_ctx* ctx, void* stream, const t2v_con
 
 // ---- weight gradient in the Winograd domain (F(4x4,3x3)) -------------------------------------------------
 static bool wgrad_winograd_ok(const t2v_conv_desc* d, int x_cs, int dy_cs) {
-    return !is_split(d->algo) && winograd_supported(d, x_cs, T2V_ALGO_WINOGRAD_F4) && dy_cs == d->Cout && d->Cout % 4 == 0;
+    return !is_bf16x2(d->algo) && winograd_supported(d, x_cs, T2V_ALGO_WINOGRAD_F4) && dy_cs == d->Cout && d->Cout % 4 == 0;
 }
 int t2v_conv_backward_weight_winograd_supported(const t2v_conv_desc* d, int x_cs, int dy_cs) {
     return d && wgrad_winograd_ok(d, x_cs, dy_cs) ? 1 : 0;
 }
 size_t t2v_conv_backward_weight_winograd_workspace_floats(const t2v_conv_desc* d, int x_cs, int batch) {
-    if (!d || batch < 1 || is_split(d->algo) || !winograd_supported(d, x_cs, T2V_ALGO_WINOGRAD_F4)) return 0;
+    if (!d || batch < 1 || is_bf16x2(d->algo) || !winograd_supported(d, x_cs, T2V_ALGO_WINOGRAD_F4)) return 0;
     const size_t Tp = (size_t)wino_tiles_padded(d, T2V_ALGO_WINOGRAD_F4);
     const size_t Cout_p = (size_t)round_up(d->Cout, 128), Kp = (size_t)round_up(x_cs, kBK);
     // V, M_dy, dU, then the hand-over area of the fixed-grid reduction (conv_wgrad.hip: wino_wgrad_sk_kernel)
@@ -1096,7 +1118,7 @@ int t2v_conv_winograd_tile_rows(const t2v_conv_desc* d) {
 }
 int t2v_conv_winograd_gemm_form(const t2v_conv_desc* d, int nimg) {
     if (!d || !is_f4(d->algo) || nimg < 1) return -1;
-    if (is_split(d->algo)) return wino_split_gemm_ok(wino_rows_batch(d, d->algo, nimg), d->Cin, d->Cout) ? T2V_GEMM_SPLIT_BF16_128x128 : -1;
+    if (is_split(d->algo)) return wino_split_gemm_ok(36, wino_rows_batch(d, d->algo, nimg), d->Cin, d->Cout) ? T2V_GEMM_SPLIT_BF16_128x128 : -1;
     PositionGemm g;      // as winograd_forward fills it
     g.groups = 36; g.rows = nimg * wino_tiles_real(d, d->algo); g.T = wino_rows_batch(d, d->algo, nimg);
     g.K = d->Cin; g.N = d->Cout;

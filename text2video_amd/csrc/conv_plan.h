@@ -47,6 +47,12 @@ bool winograd_supported(const t2v_conv_desc* d, int x_cs, int algo);
 // (down) | 4x4 inputs = 8x8 outputs (up)
 bool polyphase_supported(const t2v_conv_desc* d, int x_cs);
 bool polyphase_pays(const t2v_conv_desc* d, int x_cs);      // ... and is the faster form (the generator's selection rule)
+// either arithmetic: the split-bf16 form shares every geometry, layout size and the output transforms
+inline bool is_poly_split(int algo) { return algo == T2V_ALGO_POLYPHASE_BF16X2; }
+inline bool is_poly(int algo) { return algo == T2V_ALGO_POLYPHASE || is_poly_split(algo); }
+inline bool is_bf16x2(int algo) { return is_split(algo) || is_poly_split(algo); }      // the forward-only forms
+// ... the split-bf16 form (81 GEMMs on wino_split_gemm_kernel) takes the layer
+bool polyphase_split_supported(const t2v_conv_desc* d, int x_cs);
 inline TileGrid poly_tile_grid(const t2v_conv_desc* d) {
     return d->transposed ? tile_grid(d->H, d->W, 4) : tile_grid(d->H / 2, d->W / 2, 4);
 }
@@ -55,6 +61,7 @@ inline int poly_tiles_padded(const t2v_conv_desc* d) { return poly_tile_grid(d).
 inline int poly_out_h(const t2v_conv_desc* d) { return d->transposed ? 2 * d->H : d->H / 2; }
 inline int poly_out_w(const t2v_conv_desc* d) { return d->transposed ? 2 * d->W : d->W / 2; }
 inline int poly_m(const t2v_conv_desc* d) { return d->transposed ? 8 : 4; }       // output tile edge (statistics partial geometry)
+// (the split-bf16 form keeps the size and leaves the scratch alone)
 inline size_t polyphase_workspace_floats(const t2v_conv_desc* d) {                // V + M + the fixed-grid GEMM's hand-over scratch
     return (size_t)81 * poly_tiles_padded(d) * ((size_t)d->Cin + d->Cout) + wino_gemm_sk_scratch_floats();
 }

@@ -53,6 +53,19 @@ struct LayerSpec {
     }
 };
 
+// conv_algo 3 | 4: the selection of 0 in the opt-in split-bf16 arithmetic, 3 on the trunk, 4 on the stride-2 layers as well
+inline bool split_mode(const t2v_gen_desc& g) { return g.conv_algo == 3 || g.conv_algo == 4; }
+// a stride-2 / transposed 3x3 layer: polyphase F(4,2) where that is the faster form, with conv_algo 4 in split-bf16 arithmetic
+// where that form takes the layer.  Every class polyphase_pays selects measured faster split than fp32 as a whole conv, ranges
+// apart (scripts/measure_split_bf16_stride2.py, MI355X, profiles/split_bf16_stride2_times.txt): 256->512 @256x256 251.6 -> 192.8 us
+// (the shortest ring run, K = 256), 512->1024 @128x128 221.0 -> 136.9, 1024->512 (transposed) @64x64 214.4 -> 133.2, 512->256
+// (transposed) @128x128 250.2 -> 198.1; 512<->1024 at 512x320 148.9 -> 115.2 / 141.3 -> 111.8, at 512x680 290.1 -> 177.1 /
+// 292.3 -> 185.5: no class is excluded
+int stride2_algo(const t2v_gen_desc& g, const t2v_conv_desc& cd, int x_cs) {
+    if (!(g.conv_algo == 0 || split_mode(g)) || !polyphase_pays(&cd, x_cs)) return T2V_ALGO_DIRECT;
+    return g.conv_algo == 4 && polyphase_split_supported(&cd, x_cs) ? T2V_ALGO_POLYPHASE_BF16X2 : T2V_ALGO_POLYPHASE;
+}
+
 // canonical layer list (the order documented in t2v.h)
 void enumerate_layers(const t2v_gen_desc& g, std::vector<LayerSpec>& out) {
     const int G = g.ngf, n = g.is_local ? 1 : g.n_downsample;
@@ -62,7 +75,7 @@ void enumerate_layers(const t2v_gen_desc& g, std::vector<LayerSpec>& out) {
         for (int i = 0; i < n; ++i) {
             t2v_conv_desc cd = mk_conv(H >> i, W >> i, G << i, G << (i + 1), 3, 2, 1, T2V_PAD_ZERO, 0);
             // the deep stride-2 layers as polyphase Winograd F(4,2) (polyphase.hip) where that is the faster form
-            if ((g.conv_algo == 0 || g.conv_algo == 3) && polyphase_pays(&cd, G << i)) cd.algo = T2V_ALGO_POLYPHASE;
+            cd.algo = stride2_algo(g, cd, G << i);
             out.push_back({cd, G << i, true});
         }
     };
@@ -70,9 +83,9 @@ void enumerate_layers(const t2v_gen_desc& g, std::vector<LayerSpec>& out) {
         const int C = G << n;
         t2v_conv_desc cd = mk_conv(H >> n, W >> n, C, C, 3, 1, 1, T2V_PAD_REFLECT, 0);
         // the ResnetBlock convs (84 % of the FLOPs) run as Winograd F(2x2,3x3) wherever the geometry allows
-        // conv_algo 3: the selection of 0, its F(4x4,3x3) layers in split-bf16 arithmetic where that form takes them
-        cd.algo = best_conv_algo(&cd, C, g.conv_algo == 3 ? 0 : g.conv_algo);
-        if (g.conv_algo == 3 && cd.algo == T2V_ALGO_WINOGRAD_F4 && winograd_supported(&cd, C, T2V_ALGO_WINOGRAD_F4_BF16X2))
+        // conv_algo 3 | 4: the selection of 0, its F(4x4,3x3) layers in split-bf16 arithmetic where that form takes them
+        cd.algo = best_conv_algo(&cd, C, split_mode(g) ? 0 : g.conv_algo);
+        if (split_mode(g) && cd.algo == T2V_ALGO_WINOGRAD_F4 && winograd_supported(&cd, C, T2V_ALGO_WINOGRAD_F4_BF16X2))
             cd.algo = T2V_ALGO_WINOGRAD_F4_BF16X2;
         for (int i = 0; i < 2 * count; ++i) out.push_back({cd, C, true});
     };
@@ -80,7 +93,7 @@ void enumerate_layers(const t2v_gen_desc& g, std::vector<LayerSpec>& out) {
         for (int i = 0; i < n; ++i) {
             const int l = n - i;
             t2v_conv_desc cd = mk_conv(H >> l, W >> l, G << l, G << (l - 1), 3, 2, 1, T2V_PAD_ZERO, 1);
-            if ((g.conv_algo == 0 || g.conv_algo == 3) && polyphase_pays(&cd, G << l)) cd.algo = T2V_ALGO_POLYPHASE;
+            cd.algo = stride2_algo(g, cd, G << l);
             out.push_back({cd, G << l, true});
         }
     };
@@ -185,7 +198,7 @@ void plan_buffers(const t2v_gen_desc& g, const std::vector<LayerSpec>& layers, i
         if (is_winograd(L.cd.algo)) {
             const size_t w = winograd_workspace_floats(&L.cd, is_f4(L.cd.algo) ? nimg : 1);
             if (w > max_wino) max_wino = w;
-        } else if (L.cd.algo == T2V_ALGO_POLYPHASE) {
+        } else if (is_poly(L.cd.algo)) {
             const size_t w = polyphase_workspace_floats(&L.cd);
             if (w > max_wino) max_wino = w;
         }
@@ -281,7 +294,7 @@ struct Runner {
         const t2v_layer& w = layers[own.layer];
         float* stats = stats_of(im);
         if (g.norm_affine) T2V_REQUIRE(w.gamma && w.beta, "layer %d: norm_affine=1 but gamma/beta missing", own.layer);
-        const bool poly = L.cd.algo == T2V_ALGO_POLYPHASE;
+        const bool poly = is_poly(L.cd.algo);
         LazyNorm ln;
         if (in) T2V_TRY(lazy_norm(in, im, poly ? Takes::Polyphase : Takes::Applied, nullptr, &ln));
         ConvPlan pl;
@@ -318,7 +331,7 @@ struct Runner {
     bool next_takes_raw() const {
         if (!options().chain_lazy) return false;
         const LayerSpec& nx = specs[li + 1];
-        if (nx.cd.algo == T2V_ALGO_POLYPHASE) return true;
+        if (is_poly(nx.cd.algo)) return true;
         ConvPlan pl;
         return !nx.has_norm && build_conv_plan(&nx.cd, nx.x_cs, false, &pl) == T2V_OK && conv_plan_is_head7x7(pl);
     }

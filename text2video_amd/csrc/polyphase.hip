@@ -44,26 +44,13 @@ __global__ void polyphase_weight_kernel(const float* __restrict__ w, float* __re
                 const size_t at = UP ? (((size_t)c * Cout + n) * 3 + a) * 3 + b : (((size_t)n * Cin + c) * 3 + a) * 3 + b;
                 g[a][b] = (n < Cout && c < Cin) ? (double)w[at] : 0.0;
             }
-        double t[9][3];
-#pragma unroll
-        for (int p = 0; p < 9; ++p)
-#pragma unroll
-            for (int b = 0; b < 3; ++b) {
-                const double(&G)[9][3] = UP ? pp::kGU : pp::kGD;
-                t[p][b] = G[p][0] * g[0][b] + G[p][1] * g[1][b] + G[p][2] * g[2][b];
-            }
-#pragma unroll
-        for (int p = 0; p < 9; ++p)
-#pragma unroll
-            for (int q = 0; q < 9; ++q) {
-                const double(&G)[9][3] = UP ? pp::kGU : pp::kGD;
-                const double u = t[p][0] * G[q][0] + t[p][1] * G[q][1] + t[p][2] * G[q][2];
-                U[(size_t)(p * 9 + q) * Cout_p * Cin_s + (size_t)n * Cin_s + c] = (float)u;
-            }
+        polyphase_weight_transform<UP>(g, [&](int pos, float u) { U[(size_t)pos * Cout_p * Cin_s + (size_t)n * Cin_s + c] = u; });
     }
 }
-int launch_polyphase_weight(hipStream_t s, const float* w, float* U, int Cout, int Cin, int Cout_p, int Cin_s, int up) {
+int launch_polyphase_weight(hipStream_t s, const float* w, float* U, int Cout, int Cin, int Cout_p, int Cin_s, int up,
+                            bool split) {
     const int grid = pp_grid((long)Cout_p * Cin_s, 256);
+    if (split) return launch_polyphase_weight_split(s, w, U, Cout, Cin, Cout_p, Cin_s, up, grid);
     if (up)
         hipLaunchKernelGGL(polyphase_weight_kernel<true>, dim3(grid), dim3(256), 0, s, w, U, Cout, Cin, Cout_p, Cin_s);
     else
@@ -93,121 +80,29 @@ __global__ __launch_bounds__(256) void polyphase_input_kernel(const float2* __re
                                                              const float2* __restrict__ gamma,
                                                              const float2* __restrict__ beta, int relu) {
     constexpr int NSUB = UP ? 1 : 4;
-    const long total = (long)Tt * NSUB * C2;
+    const PolyInput in{x, H, W, C2, TW, T, mean_rstd, gamma, beta, relu};
+    const long total = (long)Tt * NSUB * C2, pitch = (long)Tt * C2;
     const long stride = (long)gridDim.x * blockDim.x;
     for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += stride) {
         const long ts = i / C2;
         const int c2 = (int)(i - ts * C2);
         const long tile = ts / NSUB;
-        const int sub = (int)(ts - tile * NSUB);      // DOWN: 0 = (1), .., 3 = (4) below; UP: all four
-        auto mine = [&](int s) { return UP || sub == s; };
-        if (tile >= T) {   // padding tiles: zeros (each sub-block's thread its own positions)
-#pragma unroll 1
-            for (int pos = 0; pos < 81; ++pos)
-                if (mine((pos / 9 >= 5 ? 2 : 0) + (pos % 9 >= 5 ? 1 : 0))) V[((long)pos * Tt + tile) * C2 + c2] = make_float2(0.f, 0.f);
-            continue;
-        }
-        const int ty = (int)(tile / TW), tx = (int)(tile - (long)ty * TW);
-        // sample k of the F(4,2) set / of the plain set, per dimension -> input index
-        auto wrow = [&](int k, int t) { return UP ? 4 * t + k : 8 * t - 1 + 2 * k; };       // k = 0..4
-        auto prow = [&](int k, int t) { return UP ? 4 * t + k : 8 * t + 2 * k; };           // k = 0..3
-        float2 mr0 = make_float2(0.f, 1.f), mr1 = make_float2(0.f, 1.f), gm = make_float2(1.f, 1.f), bt = make_float2(0.f, 0.f);
-        if (NORM) {
-            mr0 = mean_rstd[2 * c2];
-            mr1 = mean_rstd[2 * c2 + 1];
-            if (gamma) {
-                gm = gamma[c2];
-                bt = beta[c2];
-            }
-        }
-        auto load = [&](int yy, int xx) {
-            if (!((unsigned)yy < (unsigned)H && (unsigned)xx < (unsigned)W)) return make_float2(0.f, 0.f);
-            float2 v = x[((long)yy * W + xx) * C2 + c2];
-            if (NORM) {
-                v.x = norm_apply(v.x, mr0.x, mr0.y, gamma != nullptr, gm.x, bt.x, relu == 1);
-                v.y = norm_apply(v.y, mr1.x, mr1.y, gamma != nullptr, gm.y, bt.y, relu == 1);
-            }
-            return v;
-        };
-        auto store = [&](int pr, int pc, float vx, float vy) { V[((long)(pr * 9 + pc) * Tt + tile) * C2 + c2] = make_float2(vx, vy); };
-        // (1) transformed rows x transformed columns: 5 x 5 -> 5 x 5
-        if (mine(0)) {
-            float rx[5][5], ry[5][5];
-#pragma unroll
-            for (int a = 0; a < 5; ++a) {
-                float dx[5], dy[5];
-#pragma unroll
-                for (int b = 0; b < 5; ++b) {
-                    const float2 v = load(wrow(a, ty), wrow(b, tx));
-                    dx[b] = v.x;
-                    dy[b] = v.y;
-                }
-#pragma unroll
-                for (int q = 0; q < 5; ++q) {
-                    rx[a][q] = cdot<5>(pp::kBU[q], dx);
-                    ry[a][q] = cdot<5>(pp::kBU[q], dy);
-                }
-            }
-#pragma unroll
-            for (int q = 0; q < 5; ++q) {
-                float cx[5], cy[5];
-#pragma unroll
-                for (int a = 0; a < 5; ++a) {
-                    cx[a] = rx[a][q];
-                    cy[a] = ry[a][q];
-                }
-#pragma unroll
-                for (int p = 0; p < 5; ++p) store(p, q, cdot<5>(pp::kBU[p], cx), cdot<5>(pp::kBU[p], cy));
-            }
-        }
-        // (2) transformed rows x plain columns: per plain column a 5-vector down the rows
-        if (mine(1))
-#pragma unroll
-        for (int b = 0; b < 4; ++b) {
-            float cx[5], cy[5];
-#pragma unroll
-            for (int a = 0; a < 5; ++a) {
-                const float2 v = load(wrow(a, ty), prow(b, tx));
-                cx[a] = v.x;
-                cy[a] = v.y;
-            }
-#pragma unroll
-            for (int p = 0; p < 5; ++p) store(p, 5 + b, cdot<5>(pp::kBU[p], cx), cdot<5>(pp::kBU[p], cy));
-        }
-        // (3) plain rows x transformed columns
-        if (mine(2))
-#pragma unroll
-        for (int a = 0; a < 4; ++a) {
-            float dx[5], dy[5];
-#pragma unroll
-            for (int b = 0; b < 5; ++b) {
-                const float2 v = load(prow(a, ty), wrow(b, tx));
-                dx[b] = v.x;
-                dy[b] = v.y;
-            }
-#pragma unroll
-            for (int q = 0; q < 5; ++q) store(5 + a, q, cdot<5>(pp::kBU[q], dx), cdot<5>(pp::kBU[q], dy));
-        }
-        // (4) plain x plain: copies
-        if (mine(3))
-#pragma unroll
-        for (int a = 0; a < 4; ++a)
-#pragma unroll
-            for (int b = 0; b < 4; ++b) {
-                const float2 v = load(prow(a, ty), prow(b, tx));
-                store(5 + a, 5 + b, v.x, v.y);
-            }
+        const int sub = (int)(ts - tile * NSUB);      // DOWN: 0 = (1), .., 3 = (4) of polyphase_input_item; UP: all four
+        float2* const Vt = V + (tile * C2 + c2);      // this thread's element of position 0; the positions are Tt * C2 apart
+        polyphase_input_item<UP, NORM>(in, tile, sub, c2, [&](int pos, float2 v) { Vt[pos * pitch] = v; });
     }
 }
 // H, W: the INPUT map; tiles: 4x4 outputs of the H/2 x W/2 map (down) | 4x4 inputs (up); Tt = padded tile rows of V.
 // lazy != null: x still has to go through its norm layer (relu: 0 | 1 after it)
-int launch_polyphase_input(hipStream_t s, const float* x, float* V, int H, int W, int C, int up, int Tt, const LazyNorm* lazy) {
+int launch_polyphase_input(hipStream_t s, const float* x, float* V, int H, int W, int C, int up, int Tt, const LazyNorm* lazy,
+                           bool split) {
     const LazyNorm none{};
     const LazyNorm& ln = lazy ? *lazy : none;
     T2V_REQUIRE((ln.gamma == nullptr) == (ln.beta == nullptr) && (ln.relu == 0 || ln.relu == 1) && !ln.res && !ln.xout,
                 "polyphase_input: bad norm arguments");
     const TileGrid tg = up ? tile_grid(H, W, 4) : tile_grid(H / 2, W / 2, 4);
     const int grid = pp_grid((long)Tt * (up ? 1 : 4) * (C / 2), 256);
+    if (split) return launch_polyphase_input_split(s, x, V, H, W, C, up, tg, Tt, ln, grid);
     auto kern = up ? (ln.mean_rstd ? polyphase_input_kernel<true, true> : polyphase_input_kernel<true, false>)
                    : (ln.mean_rstd ? polyphase_input_kernel<false, true> : polyphase_input_kernel<false, false>);
     hipLaunchKernelGGL(kern, dim3(grid), dim3(256), 0, s, reinterpret_cast<const float2*>(x), reinterpret_cast<float2*>(V), H, W,

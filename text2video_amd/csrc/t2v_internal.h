@@ -231,13 +231,21 @@ int launch_winograd4_input_split(hipStream_t s, int mode, const float* x, float*
                                  int pad, int reflect, int Tt, int nimg, long img_stride, int last_tiles, const LazyNorm& ln,
                                  unsigned xcd_grid);
 int launch_winograd4_weight_split(hipStream_t s, const float* w, float* U, int Cout, int Cin, int Cout_p, int Cin_s);
-bool wino_split_gemm_ok(int Tt, int K, int N);
-int launch_wino_split_gemm(hipStream_t s, const float* V, const float* U, float* M, int Tt, int K, int N);
+bool wino_split_gemm_ok(int npos, int Tt, int K, int N);      // npos: 36 | 81 transform positions
+int launch_wino_split_gemm(hipStream_t s, int npos, const float* V, const float* U, float* M, int Tt, int K, int N);
 int launch_winograd4_dgrad_output(hipStream_t s, const float* dV, float* dxp, int H, int W, int C);
 // polyphase.hip
-int launch_polyphase_weight(hipStream_t s, const float* w, float* U, int Cout, int Cin, int Cout_p, int Cin_s, int up);
+// split: U / V receive the two bf16 planes of T2V_ALGO_POLYPHASE_BF16X2 (polyphase_split.hip) instead of fp32
+int launch_polyphase_weight(hipStream_t s, const float* w, float* U, int Cout, int Cin, int Cout_p, int Cin_s, int up,
+                            bool split = false);
 int launch_polyphase_input(hipStream_t s, const float* x, float* V, int H, int W, int C, int up, int Tt,
-                           const LazyNorm* lazy = nullptr);
+                           const LazyNorm* lazy = nullptr, bool split = false);
+// polyphase_split.hip: the split-bf16 form of the polyphase input transform and weight packing; geometry and grid are the
+// ones launch_polyphase_input / launch_polyphase_weight worked out
+int launch_polyphase_input_split(hipStream_t s, const float* x, float* V, int H, int W, int C, int up, const TileGrid& tg, int Tt,
+                                 const LazyNorm& ln, int grid);
+int launch_polyphase_weight_split(hipStream_t s, const float* w, float* U, int Cout, int Cin, int Cout_p, int Cin_s, int up,
+                                  int grid);
 int launch_polyphase_output(hipStream_t s, const float* Mm, const float* bias, float* y, float* stats, int Ho, int Wo, int N,
                             int up, int Tt);
 int launch_winograd4_dy(hipStream_t s, const float* dy, float* Md, int Ho, int Wo, int N, int dy_cs, int batch, int image);

@@ -4,6 +4,7 @@
 // bit by construction (the build uses -ffp-contract=off: inlining into different kernels cannot change a result).
 #pragma once
 #include <hip/hip_runtime.h>
+#include "polyphase_consts.h"
 #include "winograd_f4_consts.h"
 
 namespace t2v {
@@ -263,6 +264,163 @@ __device__ __forceinline__ void winograd4_input_item(const Wino4Input& p, const 
 #pragma unroll
         for (int a2 = 0; a2 < 6; ++a2) store(a2 * 6 + j, make_float2(cdot<6>(f4::kBT[a2], cx), cdot<6>(f4::kBT[a2], cy)));
     }
+}
+
+// U[pr*9+pq] = sum_{a,b} G[pr][a] G[pq][b] g[a][b] of one (n, c) filter of a polyphase layer (UP: the transposed conv's
+// matrices): transformed in fp64, rounded once; store(pos, u)
+template <bool UP, class Store>
+__device__ __forceinline__ void polyphase_weight_transform(const double (&g)[3][3], Store store) {
+    double t[9][3];
+#pragma unroll
+    for (int p = 0; p < 9; ++p)
+#pragma unroll
+        for (int b = 0; b < 3; ++b) {
+            const double(&G)[9][3] = UP ? pp::kGU : pp::kGD;
+            t[p][b] = G[p][0] * g[0][b] + G[p][1] * g[1][b] + G[p][2] * g[2][b];
+        }
+#pragma unroll
+    for (int p = 0; p < 9; ++p)
+#pragma unroll
+        for (int q = 0; q < 9; ++q) {
+            const double(&G)[9][3] = UP ? pp::kGU : pp::kGD;
+            const double u = t[p][0] * G[q][0] + t[p][1] * G[q][1] + t[p][2] * G[q][2];
+            store(p * 9 + q, (float)u);
+        }
+}
+
+// ---- the split-bf16 form of an fp32 value (winograd_split.hip, polyphase_split.hip): hi = bf16_rne(v), lo = bf16_rne(v - hi)
+// round to nearest even (finite values: what torch's .bfloat16() computes)
+__device__ __forceinline__ unsigned bf16_rne(float x) {
+    unsigned u = __float_as_uint(x);
+    u += 0x7fffu + ((u >> 16) & 1u);
+    return u >> 16;
+}
+__device__ __forceinline__ float bf16_float(unsigned h) { return __uint_as_float(h << 16); }
+struct SplitPair {
+    unsigned hi, lo;   // two bf16 each: .x in the low half
+};
+__device__ __forceinline__ SplitPair split_bf16x2(float2 v) {
+    const unsigned hx = bf16_rne(v.x), hy = bf16_rne(v.y);
+    const unsigned lx = bf16_rne(v.x - bf16_float(hx)), ly = bf16_rne(v.y - bf16_float(hy));
+    return {hx | (hy << 16), lx | (ly << 16)};
+}
+
+// ---- polyphase F(4,2) input transform (polyphase.hip) with a store policy, as winograd4_input_item above: the fp32 kernel
+// stores the finished value, the split-bf16 one (polyphase_split.hip) its two bf16 terms.
+struct PolyInput {
+    const float2* x;
+    int H, W, C2, TW, T;
+    const float2* mean_rstd;   // NORM
+    const float2* gamma;       // both or neither
+    const float2* beta;
+    int relu;
+};
+// The positions of sub-block `sub` (DOWN; UP: all four sub-blocks) of tile `tile` (tile >= T: a padding tile, zeros) for the
+// channel pair c2; out(pos, v) receives them, pos = pr * 9 + pc.
+template <bool UP, bool NORM, class Out>
+__device__ __forceinline__ void polyphase_input_item(const PolyInput& in, const long tile, const int sub, const int c2, Out out) {
+    const float2* __restrict__ x = in.x;
+    const float2* __restrict__ mean_rstd = in.mean_rstd;
+    const float2* __restrict__ gamma = in.gamma;
+    const float2* __restrict__ beta = in.beta;
+    const int H = in.H, W = in.W, C2 = in.C2, TW = in.TW, T = in.T, relu = in.relu;
+    auto mine = [&](int s) { return UP || sub == s; };
+    if (tile >= T) {   // padding tiles: zeros (each sub-block's thread its own positions)
+#pragma unroll 1
+        for (int pos = 0; pos < 81; ++pos)
+            if (mine((pos / 9 >= 5 ? 2 : 0) + (pos % 9 >= 5 ? 1 : 0))) out(pos, make_float2(0.f, 0.f));
+        return;
+    }
+    const int ty = (int)(tile / TW), tx = (int)(tile - (long)ty * TW);
+    // sample k of the F(4,2) set / of the plain set, per dimension -> input index
+    auto wrow = [&](int k, int t) { return UP ? 4 * t + k : 8 * t - 1 + 2 * k; };       // k = 0..4
+    auto prow = [&](int k, int t) { return UP ? 4 * t + k : 8 * t + 2 * k; };           // k = 0..3
+    float2 mr0 = make_float2(0.f, 1.f), mr1 = make_float2(0.f, 1.f), gm = make_float2(1.f, 1.f), bt = make_float2(0.f, 0.f);
+    if (NORM) {
+        mr0 = mean_rstd[2 * c2];
+        mr1 = mean_rstd[2 * c2 + 1];
+        if (gamma) {
+            gm = gamma[c2];
+            bt = beta[c2];
+        }
+    }
+    auto load = [&](int yy, int xx) {
+        if (!((unsigned)yy < (unsigned)H && (unsigned)xx < (unsigned)W)) return make_float2(0.f, 0.f);
+        float2 v = x[((long)yy * W + xx) * C2 + c2];
+        if (NORM) {
+            v.x = norm_apply(v.x, mr0.x, mr0.y, gamma != nullptr, gm.x, bt.x, relu == 1);
+            v.y = norm_apply(v.y, mr1.x, mr1.y, gamma != nullptr, gm.y, bt.y, relu == 1);
+        }
+        return v;
+    };
+    auto store = [&](int pr, int pc, float vx, float vy) { out(pr * 9 + pc, make_float2(vx, vy)); };
+    // (1) transformed rows x transformed columns: 5 x 5 -> 5 x 5
+    if (mine(0)) {
+        float rx[5][5], ry[5][5];
+#pragma unroll
+        for (int a = 0; a < 5; ++a) {
+            float dx[5], dy[5];
+#pragma unroll
+            for (int b = 0; b < 5; ++b) {
+                const float2 v = load(wrow(a, ty), wrow(b, tx));
+                dx[b] = v.x;
+                dy[b] = v.y;
+            }
+#pragma unroll
+            for (int q = 0; q < 5; ++q) {
+                rx[a][q] = cdot<5>(pp::kBU[q], dx);
+                ry[a][q] = cdot<5>(pp::kBU[q], dy);
+            }
+        }
+#pragma unroll
+        for (int q = 0; q < 5; ++q) {
+            float cx[5], cy[5];
+#pragma unroll
+            for (int a = 0; a < 5; ++a) {
+                cx[a] = rx[a][q];
+                cy[a] = ry[a][q];
+            }
+#pragma unroll
+            for (int p = 0; p < 5; ++p) store(p, q, cdot<5>(pp::kBU[p], cx), cdot<5>(pp::kBU[p], cy));
+        }
+    }
+    // (2) transformed rows x plain columns: per plain column a 5-vector down the rows
+    if (mine(1))
+#pragma unroll
+    for (int b = 0; b < 4; ++b) {
+        float cx[5], cy[5];
+#pragma unroll
+        for (int a = 0; a < 5; ++a) {
+            const float2 v = load(wrow(a, ty), prow(b, tx));
+            cx[a] = v.x;
+            cy[a] = v.y;
+        }
+#pragma unroll
+        for (int p = 0; p < 5; ++p) store(p, 5 + b, cdot<5>(pp::kBU[p], cx), cdot<5>(pp::kBU[p], cy));
+    }
+    // (3) plain rows x transformed columns
+    if (mine(2))
+#pragma unroll
+    for (int a = 0; a < 4; ++a) {
+        float dx[5], dy[5];
+#pragma unroll
+        for (int b = 0; b < 5; ++b) {
+            const float2 v = load(prow(a, ty), wrow(b, tx));
+            dx[b] = v.x;
+            dy[b] = v.y;
+        }
+#pragma unroll
+        for (int q = 0; q < 5; ++q) store(5 + a, q, cdot<5>(pp::kBU[q], dx), cdot<5>(pp::kBU[q], dy));
+    }
+    // (4) plain x plain: copies
+    if (mine(3))
+#pragma unroll
+    for (int a = 0; a < 4; ++a)
+#pragma unroll
+        for (int b = 0; b < 4; ++b) {
+            const float2 v = load(prow(a, ty), prow(b, tx));
+            store(5 + a, 5 + b, v.x, v.y);
+        }
 }
 
 }  // namespace t2v

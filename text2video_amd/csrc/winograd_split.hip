@@ -8,7 +8,8 @@
 // winograd4_output_kernel itself.
 //   winograd4_input_split_kernel  : V planes [2][36][Tt][C] bf16 (hi plane, lo plane) -- the bytes of the fp32 V
 //   winograd4_weight_split_kernel : U planes [2][36][Cout][Cin] bf16                   -- the bytes of the fp32 U
-//   wino_split_gemm_kernel        : M[pos][t][n] = V[pos][t] . U[pos][n], fp32 [36][Tt][N]
+//   wino_split_gemm_kernel        : M[pos][t][n] = V[pos][t] . U[pos][n], fp32 [npos][Tt][N]; npos = 36 here, 81 for the
+//                                   polyphase F(4,2) layers, whose split-emitting transforms are in polyphase_split.hip
 // One block per 128 x 128 output tile, nothing shared between blocks: every output is one block's fixed-order chain.
 #include "t2v_internal.h"
 #include "transform_common.h"
@@ -19,22 +20,6 @@ namespace {
 typedef unsigned short u16;
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-// round to nearest even (finite values: what torch's .bfloat16() computes)
-__device__ __forceinline__ unsigned bf16_rne(float x) {
-    unsigned u = __float_as_uint(x);
-    u += 0x7fffu + ((u >> 16) & 1u);
-    return u >> 16;
-}
-__device__ __forceinline__ float bf16_float(unsigned h) { return __uint_as_float(h << 16); }
-struct SplitPair {
-    unsigned hi, lo;   // two bf16 each: .x in the low half
-};
-__device__ __forceinline__ SplitPair split_bf16x2(float2 v) {
-    const unsigned hx = bf16_rne(v.x), hy = bf16_rne(v.y);
-    const unsigned lx = bf16_rne(v.x - bf16_float(hx)), ly = bf16_rne(v.y - bf16_float(hy));
-    return {hx | (hy << 16), lx | (ly << 16)};
-}
 
 // winograd4_input_kernel<MODE> (winograd.hip) with the split store; packed batch layout (image i owns rows [i*T, (i+1)*T) of
 // every position, the last image also the rows that pad the total to Tt).  Vp: [2][36][Tt][C2] channel pairs.
@@ -127,8 +112,8 @@ __device__ __forceinline__ void dma16(const void* base, unsigned nbytes, char* l
 }
 
 __global__ __launch_bounds__(512) void wino_split_gemm_kernel(const u16* __restrict__ A, const u16* __restrict__ B,
-                                                              float* __restrict__ C, int Tt, int N, int K, int mtiles,
-                                                              int ntiles) {
+                                                              float* __restrict__ C, int npos, int Tt, int N, int K,
+                                                              int mtiles, int ntiles) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -150,7 +135,7 @@ __global__ __launch_bounds__(512) void wino_split_gemm_kernel(const u16* __restr
     const bool half = m0 + 64 >= Tt;      // only rows m0 .. m0 + 63 exist
 
     if (is_loader) {
-        const unsigned a_bytes = (unsigned)((size_t)2 * 36 * Tt * K * 2), b_bytes = (unsigned)((size_t)2 * 36 * N * K * 2);
+        const unsigned a_bytes = (unsigned)((size_t)2 * npos * Tt * K * 2), b_bytes = (unsigned)((size_t)2 * npos * N * K * 2);
         int voff[kLd];
 #pragma unroll
         for (int n = 0; n < kLd; ++n) {
@@ -160,7 +145,7 @@ __global__ __launch_bounds__(512) void wino_split_gemm_kernel(const u16* __restr
             int r = 2 * rho + (sp >> 2);
             const int kc = sp & 3;
             if (op == 0 && half) r &= 63;
-            voff[n] = op == 0 ? (((plane * 36 + p) * Tt + m0 + r) * K + kc * 8) * 2 : (((plane * 36 + p) * N + n0 + r) * K + kc * 8) * 2;
+            voff[n] = op == 0 ? (((plane * npos + p) * Tt + m0 + r) * K + kc * 8) * 2 : (((plane * npos + p) * N + n0 + r) * K + kc * 8) * 2;
         }
         auto issue_stage = [&](int kt, int slot) {
 #pragma unroll
@@ -284,16 +269,19 @@ int launch_winograd4_weight_split(hipStream_t s, const float* w, float* U, int C
     return T2V_OK;
 }
 
-bool wino_split_gemm_ok(int Tt, int K, int N) {
-    return Tt >= 64 && Tt % 64 == 0 && N >= kBN && N % kBN == 0 && K >= kSBK && K % kSBK == 0 &&
-           // 32-bit byte offsets into each operand's buffer resource, and a 31-bit grid
-           (long)36 * Tt * K * 4 < 0x7fff0000L && (long)36 * N * K * 4 < 0x7fff0000L &&
-           (long)36 * ((Tt + kBM - 1) / kBM) * (N / kBN) < 0x7fffffffL;
+// npos transform positions: 36 (F(4x4,3x3)) | 81 (polyphase F(4,2))
+bool wino_split_gemm_ok(int npos, int Tt, int K, int N) {
+    return (npos == 36 || npos == 81) && Tt >= 64 && Tt % 64 == 0 && N >= kBN && N % kBN == 0 && K >= kSBK && K % kSBK == 0 &&
+           // 32-bit byte offsets into each operand's buffer resource (two planes of npos * rows * K bf16: the bytes of the
+           // fp32 tensor), and a 31-bit grid
+           (long)npos * Tt * K * 4 < 0x7fff0000L && (long)npos * N * K * 4 < 0x7fff0000L &&
+           (long)npos * ((Tt + kBM - 1) / kBM) * (N / kBN) < 0x7fffffffL;
 }
 
-// V planes [2][36][Tt][K], U planes [2][36][N][K] (bf16) -> M [36][Tt][N] fp32
-int launch_wino_split_gemm(hipStream_t s, const float* V, const float* U, float* M, int Tt, int K, int N) {
-    T2V_REQUIRE(wino_split_gemm_ok(Tt, K, N), "split-bf16 gemm: Tt=%d (%% 64), K=%d (%% 32), N=%d (%% 128) not supported", Tt, K, N);
+// V planes [2][npos][Tt][K], U planes [2][npos][N][K] (bf16) -> M [npos][Tt][N] fp32
+int launch_wino_split_gemm(hipStream_t s, int npos, const float* V, const float* U, float* M, int Tt, int K, int N) {
+    T2V_REQUIRE(wino_split_gemm_ok(npos, Tt, K, N), "split-bf16 gemm: %d positions, Tt=%d (%% 64), K=%d (%% 32), N=%d (%% 128) not supported",
+                npos, Tt, K, N);
     static bool attr_done = false;
     if (!attr_done) {
         T2V_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(wino_split_gemm_kernel),
@@ -301,8 +289,8 @@ int launch_wino_split_gemm(hipStream_t s, const float* V, const float* U, float*
         attr_done = true;
     }
     const int mtiles = (Tt + kBM - 1) / kBM, ntiles = N / kBN;
-    hipLaunchKernelGGL(wino_split_gemm_kernel, dim3(36 * mtiles * ntiles), dim3(512), kSplitGemmLds, s,
-                       reinterpret_cast<const u16*>(V), reinterpret_cast<const u16*>(U), M, Tt, N, K, mtiles, ntiles);
+    hipLaunchKernelGGL(wino_split_gemm_kernel, dim3(npos * mtiles * ntiles), dim3(512), kSplitGemmLds, s,
+                       reinterpret_cast<const u16*>(V), reinterpret_cast<const u16*>(U), M, npos, Tt, N, K, mtiles, ntiles);
     T2V_HIP_CHECK(hipGetLastError());
     return T2V_OK;
 }

@@ -171,6 +171,8 @@ def upload_tensors(tensors, device):
 
 
 ARITHS = ("fp32", "bf16x2")
+# the layers arith="bf16x2" covers: the ResnetBlock trunk | the trunk and the polyphase stride-2 / transposed layers
+ARITH_LAYERS = ("trunk", "trunk+stride2")
 
 
 class HipGenerator:
@@ -179,26 +181,42 @@ class HipGenerator:
     Weights are packed lazily per frame geometry: the ResnetBlock convs use Winograd-transformed
     weights wherever the geometry supports it (t2v_generator_layer_desc reports the algorithm)."""
 
-    def __init__(self, spec, device="cuda", conv_algo=None, arith="fp32"):
+    def __init__(self, spec, device="cuda", conv_algo=None, arith="fp32", arith_layers="trunk"):
         """arith: "fp32" (default: every kernel in exact fp32) | "bf16x2": the ResnetBlock trunk's F(4x4,3x3) GEMMs in
         split-bf16 arithmetic (t2v_gen_desc.conv_algo 3; inference only).  Measured (DESIGN.md section 0,
         profiles/split_bf16_accuracy.txt): 2.2e-5 of the output's rms per conv against 1.8e-7 for the fp32 pipeline -- the
         Winograd-domain operands are an order larger than the output they cancel to, which amplifies the split error -- and
         max |frame - float64| 1.8e-4 against 2.7e-5 (6.9x) on the 160 x 160 test generator, below the 1e-3 parity bar.
-        The mode is chosen by this argument only: conv_algo=3 without it, or T2V_CONV_ALGO=3, is refused."""
+        arith_layers (with arith="bf16x2"): "trunk" (default) | "trunk+stride2": also the polyphase stride-2 and transposed
+        layers' 81 GEMMs in split-bf16 arithmetic (t2v_gen_desc.conv_algo 4); 1.7e-5 of the output's rms per such conv in the
+        float64 emulation of the form.
+        The mode is chosen by these arguments only: conv_algo=3 | 4 without them, or T2V_CONV_ALGO=3 | 4, is refused."""
         import os
         if arith not in ARITHS:
             raise ValueError("arith=%r: one of %s" % (arith, ", ".join(ARITHS)))
+        if arith_layers not in ARITH_LAYERS:
+            raise ValueError("arith_layers=%r: one of %s" % (arith_layers, ", ".join(ARITH_LAYERS)))
+        if arith == "fp32" and arith_layers != "trunk":
+            raise ValueError("arith_layers=%r is the scope of arith='bf16x2' (arith='fp32' given)" % (arith_layers,))
         if arith == "bf16x2":
-            if conv_algo not in (None, 0, _lib.CONV_ALGO_BF16X2):
+            mode = _lib.CONV_ALGO_BF16X2_STRIDE2 if arith_layers == "trunk+stride2" else _lib.CONV_ALGO_BF16X2
+            if conv_algo not in (None, 0, mode):
                 raise ValueError("arith='bf16x2' selects the ResnetBlock algorithm itself (conv_algo=%r given)" % (conv_algo,))
-            conv_algo = _lib.CONV_ALGO_BF16X2
+            conv_algo = mode
         elif conv_algo == _lib.CONV_ALGO_BF16X2:
             raise ValueError("conv_algo=3 is the split-bf16 trunk: select it with arith='bf16x2'")
+        elif conv_algo == _lib.CONV_ALGO_BF16X2_STRIDE2:
+            raise ValueError("conv_algo=4 is the split-bf16 trunk and stride-2 layers: select it with arith='bf16x2', "
+                             "arith_layers='trunk+stride2'")
+        elif conv_algo is None and int(os.environ.get("T2V_CONV_ALGO", "0")) == _lib.CONV_ALGO_BF16X2_STRIDE2:
+            raise ValueError("T2V_CONV_ALGO=4: the split-bf16 trunk and stride-2 layers are selected with arith='bf16x2', "
+                             "arith_layers='trunk+stride2' (--arith bf16x2 --arith_layers trunk+stride2), not by the "
+                             "environment; T2V_CONV_ALGO takes 0, 1 or 2")
         elif conv_algo is None and int(os.environ.get("T2V_CONV_ALGO", "0")) == _lib.CONV_ALGO_BF16X2:
             raise ValueError("T2V_CONV_ALGO=3: the split-bf16 trunk is selected with arith='bf16x2' (--arith bf16x2), not by the "
                              "environment; T2V_CONV_ALGO takes 0, 1 or 2")
         self.arith = arith
+        self.arith_layers = arith_layers
         self.spec = spec
         self.device = torch.device(device)
         self.ctx = ops.context(self.device)

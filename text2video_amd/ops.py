@@ -12,7 +12,7 @@ from ._xp import torch     # the real torch, or leantorch under vid2vid/test.py'
 
 from . import _lib
 from ._lib import (ACT_FLOW_W, ACT_LRELU, ACT_NONE, ACT_TANH, ALGO_DIRECT, ALGO_WINOGRAD,  # noqa: F401
-                   ALGO_POLYPHASE, ALGO_WINOGRAD_F4, ALGO_WINOGRAD_F4_BF16X2, PAD_REFLECT, PAD_ZERO, ConvDesc, check)
+                   ALGO_POLYPHASE, ALGO_POLYPHASE_BF16X2, ALGO_WINOGRAD_F4, ALGO_WINOGRAD_F4_BF16X2, PAD_REFLECT, PAD_ZERO, ConvDesc, check)
 
 _contexts = {}
 
@@ -96,6 +96,13 @@ def polyphase_supported(desc, x_cs=None):
     return bool(_lib.load().t2v_conv_polyphase_supported(ctypes.byref(desc), x_cs) & 1)
 
 
+def polyphase_bf16x2_supported(desc, x_cs=None):
+    """True when `desc` can run as ALGO_POLYPHASE_BF16X2: ALGO_POLYPHASE with its 81 GEMMs in split-bf16 arithmetic (forward
+    only; V and the packed weight then hold two bf16 planes in the fp32 tensors' bytes)"""
+    x_cs = round_up(desc.Cin, 4) if x_cs is None else x_cs
+    return bool(_lib.load().t2v_conv_polyphase_bf16x2_supported(ctypes.byref(desc), x_cs))
+
+
 def polyphase_pays(desc, x_cs=None):
     """... and the library's own rule selects it for this shape (the faster form: both channel counts >= 256)"""
     x_cs = round_up(desc.Cin, 4) if x_cs is None else x_cs
@@ -110,7 +117,7 @@ def best_conv_algo(desc, x_cs=None, cap=0):
 
 def conv2d_auto(x, packed_w, bias, desc, y_cs=None, stats=None, out=None):
     """conv2d or conv2d_winograd, whichever desc.algo (and the weight packing that goes with it) says."""
-    if desc.algo in (ALGO_WINOGRAD, ALGO_WINOGRAD_F4, ALGO_WINOGRAD_F4_BF16X2, ALGO_POLYPHASE):
+    if desc.algo in (ALGO_WINOGRAD, ALGO_WINOGRAD_F4, ALGO_WINOGRAD_F4_BF16X2, ALGO_POLYPHASE, ALGO_POLYPHASE_BF16X2):
         assert y_cs is None or y_cs == desc.Cout
         return conv2d_winograd(x, packed_w, bias, desc, stats=stats, out=out)
     return conv2d(x, packed_w, bias, desc, y_cs=y_cs, stats=stats, out=out)

@@ -22,6 +22,10 @@ def _common(p):
       "bf16 terms (~16 mantissa bits per product, fp32 accumulation; everything else stays fp32).  Measured: 512x512 frames "
       "1.30x faster; 2.2e-5 of a conv's output rms against 1.8e-7 in fp32, frames 1.8e-4 from float64 against 2.7e-5 "
       "(DESIGN.md section 0)")
+    g("--arith_layers", type=str, default=None, choices=["trunk", "trunk+stride2"], help="with --arith bf16x2, the layers "
+      "that run in split-bf16 arithmetic: trunk (what --arith bf16x2 alone selects): the ResnetBlock convs; trunk+stride2: "
+      "also the polyphase stride-2 and transposed layers (the 81 GEMMs of each on the same kernel; the float64 emulation of "
+      "one such conv is 1.7e-5 of its output's rms from the exact one)")
     g("--batchSize", type=int, default=1)
     g("--loadSize", type=int, default=512)
     g("--fineSize", type=int, default=512)
@@ -93,6 +97,9 @@ class BaseOptions:
 
     def parse(self, argv=None, save=False):
         opt, unknown = self.parser.parse_known_args(argv)
+        if opt.arith_layers is not None and opt.arith != "bf16x2":
+            self.parser.error("--arith_layers %s: the scope of --arith bf16x2, which is not given" % opt.arith_layers)
+        opt.arith_layers = opt.arith_layers or "trunk"
         if unknown:
             print("warning: ignoring unknown options %s" % unknown, file=sys.stderr)
         opt.isTrain = self.is_train
