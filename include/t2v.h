@@ -628,6 +628,37 @@ int t2v_resample_crop_normalize_u8(t2v_ctx* ctx, void* stream, const uint8_t* sr
                                    int crop_x, int crop_y, int crop_w, int crop_h, float* dst, int dst_cs, int dst_c0);
 
 /* ------------------------------------------------------------------------------------------
+ * Picture-quality sums (additive to ABI 22): what PSNR, the mean absolute error and SSIM of two uint8 images are formed
+ * from, over the whole frame and up to T2V_METRICS_MAX_BOXES boxes, in two launches (vid2vid/test.py --metrics,
+ * python -m text2video_amd.evaluate).
+ *   a, b: [H][W][cs] uint8 device images, cs in {3, 4} chosen per image (a generated frame comes with stride 4, a decoded
+ *   real frame with 3); channels 0..2 are compared.
+ *   boxes: HOST memory, [nbox][4] = y0, y1, x0, x1 (half-open rows / columns); read before the call returns.
+ *   Region 0 is the whole frame, region r = 1..nbox is box r-1.  out (device, doubles) row r = {sse, sad, ssim_sum, ssim_n}:
+ *     sse = sum (a - b)^2 and sad = sum |a - b| over the region's pixels and 3 channels: exact integers (< 2^53);
+ *     ssim_sum = sum of the SSIM index s over the window positions whose WHOLE 11x11 window lies inside the region, and the
+ *       3 channels -- so a box's SSIM is the SSIM of the cropped pair; ssim_n = 3 (h - 10)(w - 10) of them, 0 for a region
+ *       narrower than 11 in either direction (ssim_sum is then 0).
+ *   s (Wang, Bovik, Sheikh, Simoncelli 2004), per channel on the 8-bit values, in float64 throughout:
+ *     window w = outer product of g[i] = exp(-(i - 5)^2 / 4.5), i = 0..10 (sigma 1.5), g normalised to sum 1;
+ *     mx = sum w x, my = sum w y, vx = sum w x^2 - mx^2, vy = sum w y^2 - my^2, cxy = sum w x y - mx my;
+ *     C1 = (0.01 * 255)^2, C2 = (0.03 * 255)^2;  s = (2 mx my + C1)(2 cxy + C2) / ((mx^2 + my^2 + C1)(vx + vy + C2)).
+ *     The window sums run separably (rows, then columns) with fused multiply-adds; another float64 order of the same sums
+ *     differs by ~1e-13 of s, a float32 evaluation by ~1e-5 on smooth images (the cancellation in vx, vy, cxy).
+ *   scratch: t2v_image_metrics_scratch_doubles(H, W, nbox) doubles of device memory (one partial per 32x32 tile, region and
+ *   sum; 0 for a shape the call refuses), any content; the caller vouches for its size.
+ * Every tile's partial sums are added in a fixed order by the second launch: no atomics, two calls give the same bits, and
+ * row 0 has the same bits whatever boxes are passed.  Rows of `out` past 1 + nbox are not touched.  No allocation, no host
+ * synchronisation.  Refused with T2V_ERR_INVALID and nothing launched: a channel stride outside {3, 4}, H or W outside
+ * 1..T2V_METRICS_MAX_SIDE, nbox outside 0..T2V_METRICS_MAX_BOXES, an empty box or one that leaves the frame.
+ * ------------------------------------------------------------------------------------------ */
+#define T2V_METRICS_MAX_BOXES 3
+#define T2V_METRICS_MAX_SIDE 8192
+size_t t2v_image_metrics_scratch_doubles(int H, int W, int nbox);
+int t2v_image_metrics_u8(t2v_ctx* ctx, void* stream, const uint8_t* a, int a_cs, const uint8_t* b, int b_cs, int H, int W,
+                         const int32_t* boxes /* HOST, [nbox][4] */, int nbox, double* scratch, double* out /* [1+nbox][4] */);
+
+/* ------------------------------------------------------------------------------------------
  * Host plumbing (ABI 14): device buffers, pinned host buffers, copies, streams and events for a host that has no HIP
  * binding of its own -- the reference's hosts got these from THC (THCudaMalloc / THCudaFree
  * $SP/torch/lib/include/THC/THCGeneral.h:143-144, THCudaHostAlloc :147, THCState_getCurrentStream :105,

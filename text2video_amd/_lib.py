@@ -180,6 +180,10 @@ SIGNATURES = {
     "t2v_resample_crop_normalize_u8": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
                                                c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int,
                                                c_int, c_void_p, c_int, c_int]),
+    # picture-quality sums of two uint8 images (additive to ABI 22); boxes: host int32 [nbox][4]
+    "t2v_image_metrics_scratch_doubles": (c_size_t, [c_int, c_int, c_int]),
+    "t2v_image_metrics_u8": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_int,
+                                     c_void_p, c_void_p]),
     # host plumbing (ABI 14): what text2video_amd/leantorch.py allocates, copies and synchronises with
     "t2v_device_malloc": (c_int, [c_void_p, c_size_t, POINTER(c_void_p)]),
     "t2v_device_free": (c_int, [c_void_p, c_void_p]),

@@ -1521,6 +1521,32 @@ int t2v_resample_crop_normalize_u8(t2v_ctx* ctx, void* stream, const uint8_t* sr
                                              y_coef, ky, crop_x, crop_y, crop_w, crop_h, dst, dst_cs, dst_c0);
 }
 
+// ---- picture-quality sums: PSNR / SSIM of two uint8 images (additive to ABI 22) ----
+static bool image_metrics_shape_ok(int H, int W, int nbox) {
+    return H >= 1 && W >= 1 && H <= T2V_METRICS_MAX_SIDE && W <= T2V_METRICS_MAX_SIDE && nbox >= 0 && nbox <= T2V_METRICS_MAX_BOXES;
+}
+size_t t2v_image_metrics_scratch_doubles(int H, int W, int nbox) {
+    return image_metrics_shape_ok(H, W, nbox) ? image_metrics_scratch_doubles(H, W, nbox) : 0;
+}
+int t2v_image_metrics_u8(t2v_ctx* ctx, void* stream, const uint8_t* a, int a_cs, const uint8_t* b, int b_cs, int H, int W,
+                         const int32_t* boxes, int nbox, double* scratch, double* out) {
+    T2V_REQUIRE(ctx && a && b && scratch && out, "image_metrics_u8: null pointer");
+    T2V_REQUIRE((a_cs == 3 || a_cs == 4) && (b_cs == 3 || b_cs == 4),
+                "image_metrics_u8: channel strides must be 3 or 4 (got %d and %d)", a_cs, b_cs);
+    T2V_REQUIRE(H >= 1 && W >= 1 && H <= T2V_METRICS_MAX_SIDE && W <= T2V_METRICS_MAX_SIDE,
+                "image_metrics_u8: H, W must be in 1..%d (got %d x %d)", T2V_METRICS_MAX_SIDE, H, W);
+    T2V_REQUIRE(nbox >= 0 && nbox <= T2V_METRICS_MAX_BOXES, "image_metrics_u8: nbox must be in 0..%d (got %d)",
+                T2V_METRICS_MAX_BOXES, nbox);
+    T2V_REQUIRE(nbox == 0 || boxes, "image_metrics_u8: %d boxes and a null box pointer", nbox);
+    for (int i = 0; i < nbox; ++i) {
+        const int32_t* q = boxes + 4 * i;
+        T2V_REQUIRE(q[0] >= 0 && q[0] < q[1] && q[1] <= H && q[2] >= 0 && q[2] < q[3] && q[3] <= W,
+                    "image_metrics_u8: box %d = rows [%d, %d) x columns [%d, %d) is empty or outside the %d x %d frame", i, q[0],
+                    q[1], q[2], q[3], H, W);
+    }
+    return launch_image_metrics_u8((hipStream_t)stream, a, a_cs, b, b_cs, H, W, boxes, nbox, scratch, out);
+}
+
 // ---- host plumbing (ABI 14): buffers, copies, streams, events for a host without a HIP binding of its own ----
 int t2v_device_malloc(t2v_ctx* ctx, size_t bytes, void** out) {
     T2V_REQUIRE(ctx && out, "device_malloc: null pointer");

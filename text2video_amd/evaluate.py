@@ -1,0 +1,101 @@
+"""python -m text2video_amd.evaluate DIR_A DIR_B [--pattern 'fake_B_*'] [--json OUT]
+
+PSNR / SSIM / MAE between the image files of two result trees, paired by relative path: the picture-level answer to "what
+does --arith bf16x2 do to my model" (the same test.py command run twice) and "epoch 20 against epoch 40".  The files are
+decoded with Pillow and compared on the GPU by the kernel of `test.py --metrics` (ops.image_metrics, whole frame only).
+Prints and (--json) writes one summary per sequence (= directory) and one overall.  Unpaired files and pairs of different
+sizes are listed and make the exit status 1.
+"""
+import argparse
+import fnmatch
+import json
+import os
+import sys
+
+IMG_EXT = (".jpg", ".jpeg", ".png", ".ppm", ".bmp", ".tiff")
+
+
+def list_images(root, pattern):
+    """relative paths (posix separators) of the image files under `root` whose base name matches `pattern`"""
+    out = []
+    for d, _, files in os.walk(root):
+        for f in files:
+            if f.lower().endswith(IMG_EXT) and fnmatch.fnmatch(f, pattern):
+                out.append(os.path.relpath(os.path.join(d, f), root).replace(os.sep, "/"))
+    return sorted(out)
+
+
+def pair_files(dir_a, dir_b, pattern="fake_B_*"):
+    """-> (paired relative paths, only under dir_a, only under dir_b), each sorted"""
+    a, b = list_images(dir_a, pattern), list_images(dir_b, pattern)
+    sa, sb = set(a), set(b)
+    return [p for p in a if p in sb], [p for p in a if p not in sb], [p for p in b if p not in sa]
+
+
+def compare_trees(dir_a, dir_b, pattern="fake_B_*", device="cuda:0"):
+    """-> the report: {"definition", "overall", "sequences": {dir: summary}, "unpaired_a", "unpaired_b", "size_mismatch"}"""
+    import numpy as np
+    from PIL import Image
+    from ._xp import torch
+    from . import metrics as M
+    from . import ops
+    pairs, only_a, only_b = pair_files(dir_a, dir_b, pattern)
+    per_seq, mismatch, pending = {}, [], []
+    for rel in pairs:
+        with Image.open(os.path.join(dir_a, rel)) as im:
+            a = np.array(im.convert("RGB"))
+        with Image.open(os.path.join(dir_b, rel)) as im:
+            b = np.array(im.convert("RGB"))
+        if a.shape != b.shape:
+            mismatch.append({"file": rel, "a": [a.shape[1], a.shape[0]], "b": [b.shape[1], b.shape[0]]})
+            continue
+        row = ops.image_metrics(torch.from_numpy(a).to(device), torch.from_numpy(b).to(device))
+        pending.append((rel, 3 * a.shape[0] * a.shape[1], row))
+    for rel, n_values, row in pending:       # (the copies wait for the GPU once everything is enqueued)
+        s = ops.metrics_summary(row.cpu().numpy()[0], n_values)
+        per_seq.setdefault(os.path.dirname(rel) or ".", []).append((s, n_values))
+    return {"definition": ops.METRICS_DEFINITION, "a": dir_a, "b": dir_b, "pattern": pattern,
+            "overall": M._pooled([p for parts in per_seq.values() for p in parts]),
+            "sequences": {seq: M._pooled(parts) for seq, parts in sorted(per_seq.items())},
+            "unpaired_a": only_a, "unpaired_b": only_b, "size_mismatch": mismatch}
+
+
+def _fmt(v, spec):
+    return "none" if v is None else format(v, spec)
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(prog="python -m text2video_amd.evaluate", description=__doc__.split("\n\n")[1])
+    ap.add_argument("dir_a")
+    ap.add_argument("dir_b")
+    ap.add_argument("--pattern", default="fake_B_*", help="shell pattern the files' base names must match")
+    ap.add_argument("--json", default=None, metavar="OUT", help="write the report to this file")
+    ap.add_argument("--gpu_ids", default="0")
+    args = ap.parse_args(argv)
+    for d in (args.dir_a, args.dir_b):
+        if not os.path.isdir(d):
+            ap.error("%s is not a directory" % d)
+    if os.environ.get("T2V_LEAN", "1") != "0":
+        from . import _xp
+        _xp.use_lean()          # no torch needed for an allocator and a stream (honoured when torch is not loaded yet)
+    rep = compare_trees(args.dir_a, args.dir_b, args.pattern, "cuda:%d" % int(str(args.gpu_ids).split(",")[0]))
+    for seq, s in list(rep["sequences"].items()) + [("overall", rep["overall"])]:
+        print("%-24s %4d frames  psnr %s dB  ssim %s  mae %s" % (seq, s["frames"], _fmt(s["psnr"], ".3f"), _fmt(s["ssim"], ".6f"),
+                                                               _fmt(s["mae"], ".4f")))
+    for key, what in (("unpaired_a", "only under %s" % args.dir_a), ("unpaired_b", "only under %s" % args.dir_b)):
+        for f in rep[key]:
+            print("unpaired (%s): %s" % (what, f), file=sys.stderr)
+    for m in rep["size_mismatch"]:
+        print("size mismatch: %s is %dx%d and %dx%d" % (m["file"], m["a"][0], m["a"][1], m["b"][0], m["b"][1]), file=sys.stderr)
+    if args.json:
+        with open(args.json, "w") as fh:
+            json.dump(rep, fh, indent=1, sort_keys=True)
+            fh.write("\n")
+    if not rep["overall"]["frames"] and not (rep["unpaired_a"] or rep["unpaired_b"] or rep["size_mismatch"]):
+        print("no file matches %r under both directories" % args.pattern, file=sys.stderr)
+        return 1
+    return 1 if (rep["unpaired_a"] or rep["unpaired_b"] or rep["size_mismatch"]) else 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

@@ -44,6 +44,30 @@ FACE_PARTS = (
 NOSE_NECK_RGB = POSE_RGB[0]  # the colour --add_face_disc keys its face crop on
 
 
+def get_face_region(pose_maps_u8, fine_size):
+    """(ys, ye, xs, xe) of the face crop for a chunk of frames, or None when no frame shows the key colour.
+
+    [RECALL upstream Vid2VidModelD.get_face_region, --openpose_only branch]: the pixels of ALL frames of the chunk
+    whose colour is the nose-neck limb's [153,0,51] (keypoint2img.py:180; upstream tests the normalised map for
+    R in (0.19,0.21), G < -0.99, B in (-0.61,-0.59), which is that uint8 colour) give one bounding box; the crop is
+    centred on the box's midpoint, side fine_size//32*8 (128 at fineSize 512), the centre clamped to
+    [side/2, dim-1-side/2]; with no such pixel upstream returns an empty region -- the face terms are skipped then.
+    pose_maps_u8: [H,W,3] or [F,H,W,3]."""
+    a = np.asarray(pose_maps_u8)
+    if a.ndim == 3:
+        a = a[None]
+    H, W = a.shape[1:3]
+    side = max(8, fine_size // 32 * 8)
+    r, g, b = NOSE_NECK_RGB      # (per channel: a third of the time of (a == rgb).all(3), which --metrics would pay per frame)
+    _, ys, xs = np.nonzero((a[..., 0] == r) & (a[..., 1] == g) & (a[..., 2] == b))
+    if not ys.size:
+        return None
+    yc, xc = (int(ys.min()) + int(ys.max())) // 2, (int(xs.min()) + int(xs.max())) // 2
+    yc = max(side // 2, min(H - 1 - side // 2, yc))
+    xc = max(side // 2, min(W - 1 - side // 2, xc))
+    return yc - side // 2, yc + side // 2, xc - side // 2, xc + side // 2
+
+
 def _affine(x, a, b):
     return a * x + b
 

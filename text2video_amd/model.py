@@ -171,6 +171,12 @@ def run_test(opt, model=None, device=None, dataset=None):
     n_lanes = max(1, min(int(getattr(opt, "batch_sequences", 2) or 1), _lib_max_batch()))
     # the first step's pose maps are rasterised by the pool while the model is created (checkpoint -> device)
     first_steps = dataset.iter_lanes(n_lanes, opt.pose_workers, limit=limit)
+    # --metrics: the real frames of the same items, decoded on threads ahead of the loop (text2video_amd/metrics.py)
+    want_metrics = bool(getattr(opt, "metrics", False))
+    real_frames, seq_metrics = None, []      # seq_metrics: (event, pinned rows, SequenceRows) per finished sequence
+    if want_metrics:
+        from . import metrics as M
+        real_frames = M.RealFrames(dataset, opt, n_lanes, limit)
     primer = None
     if model is None:
         import threading
@@ -214,6 +220,17 @@ def run_test(opt, model=None, device=None, dataset=None):
         def __init__(self):
             from .generator import Recurrence
             self.rec, self.window, self.dev_maps, self.unit = Recurrence(), None, None, None
+            self.metrics = self.real_dev = None      # --metrics: this sequence's rows, the real frame on the device
+
+    def close_metrics(L):
+        """the sequence of lane L has ended: its rows go to the host in one copy (read after the loop)"""
+        if L.metrics is not None and L.metrics.frames:
+            host = torch.empty(L.metrics.rows.shape, dtype=torch.float64, pin_memory=True)
+            host.copy_(L.metrics.rows, non_blocking=True)
+            ev = torch.cuda.Event()
+            ev.record()
+            seq_metrics.append((ev, host, L.metrics))
+        L.metrics = None
 
     def frame_loop(steps, tails, start_state=None):
         """steps: iterable of [(lane, item), ...] (PoseDataset.iter_lanes): the items of one step belong to independent
@@ -235,6 +252,30 @@ def run_test(opt, model=None, device=None, dataset=None):
                     from . import distributed as D
                     tails[L.unit] = D.pack_state(L.rec.prev)
 
+        def compare_with_real(k, L, data, u8):
+            """--metrics: this frame's bytes (before JPEG) against the real frame of the same index, whole frame and face
+            box; the rows stay on the device until the sequence ends -- no host synchronisation here"""
+            tw = time.perf_counter()
+            real = real_frames.get(data["A_path"])
+            split["metrics_wait_real_s"] = split.get("metrics_wait_real_s", 0.0) + time.perf_counter() - tw      # (part of metrics_s)
+            if real.shape[:2] != tuple(u8.shape[:2]):
+                raise ValueError("--metrics: %s is %dx%d after resize and crop, the generated frame %dx%d"
+                                 % ((data["A_path"],) + real.shape[:2] + tuple(u8.shape[:2])))
+            if L.metrics is None or L.metrics.seq != data["seq"]:
+                close_metrics(L)
+                L.metrics = M.SequenceRows(torch, data["seq"], dataset.seq_lengths()[data["seq"]], dev)
+            ring = pinned.get((k, "real") + real.shape)
+            if ring is None:
+                ring = pinned[(k, "real") + real.shape] = \
+                    [[torch.empty(real.shape, dtype=torch.uint8, pin_memory=True) for _ in range(3)], 0]
+            stage = ring[0][ring[1] % 3]     # (its upload of frame n-3 ran before the frame whose event finish(n-2) waited for)
+            ring[1] += 1
+            stage.numpy()[...] = real
+            if L.real_dev is None or tuple(L.real_dev.shape) != real.shape:
+                L.real_dev = torch.empty(real.shape, dtype=torch.uint8, device=dev)
+            L.real_dev.copy_(stage, non_blocking=True)
+            L.metrics.compare(u8, L.real_dev, os.path.basename(data["A_path"]), M.face_box(data["A"][-1]))
+
         steps = iter(steps)
         while True:
             tq = time.perf_counter()
@@ -254,6 +295,7 @@ def run_test(opt, model=None, device=None, dataset=None):
                 H, W = A.shape[1], A.shape[2]
                 if data["change_seq"] or L.dev_maps is None or L.window.shape[:2] != (H, W):
                     close_unit(L)
+                    close_metrics(L)
                     L.rec.reset()
                     if start_state is not None:      # stitch pass: continue from the predecessor chunk's last frames
                         st0 = start_state[data["unit"]]
@@ -294,6 +336,9 @@ def run_test(opt, model=None, device=None, dataset=None):
                     t3 = time.perf_counter()
                     ev = torch.cuda.Event()
                     ev.record()
+                    if want_metrics:      # (after the event: the frame's JPEG does not wait for the comparison)
+                        compare_with_real(k, L, data, u8)
+                        split["metrics_s"] = split.get("metrics_s", 0.0) + time.perf_counter() - t3
                     split["tensor2im_s"] = split.get("tensor2im_s", 0.0) + t2 - t1
                     split["d2h_s"] = split.get("d2h_s", 0.0) + t3 - t2
                     now.append((ev, host, data["A_path"], _real_A_u8(data["A"][-1])))
@@ -312,6 +357,7 @@ def run_test(opt, model=None, device=None, dataset=None):
             finish(p)
         for L in lanes.values():
             close_unit(L)
+            close_metrics(L)
 
     frame_loop(primed_steps(), tails)
     marks["loop_s"] = time.perf_counter() - counters["t_loop0"] if counters["n"] else 0.0
@@ -335,6 +381,14 @@ def run_test(opt, model=None, device=None, dataset=None):
                     if stitch >= u[2] - u[3]:      # re-generated to its end: this chunk's tail is the new one
                         tails[j] = redone[jj]
     vis.flush()
+    metrics_out = {}
+    if want_metrics:
+        real_frames.close()
+        for ev, host, rows in seq_metrics:       # <results>/<seq>/metrics.json, by the process that generated the sequence
+            ev.synchronize()
+            doc = M.summarise(rows.frames, host.numpy())
+            M.write_json(os.path.join(vis.save_dir, rows.seq, "metrics.json"), doc)
+            metrics_out[rows.seq] = doc["summary"]
     marks["to_last_jpeg_s"] = time.perf_counter() - t_start
     videos = []
     if getattr(opt, "write_video", False):
@@ -365,6 +419,8 @@ def run_test(opt, model=None, device=None, dataset=None):
                                 pack_s=round(sum(getattr(net, "pack_seconds", 0.0) for net in model.nets), 4),
                                 torch_imported="torch" in sys.modules,
                                 mux_s=round(t_end - t_start - marks["to_last_jpeg_s"], 4))}
+    if want_metrics:
+        stats["metrics"] = metrics_out
     if opt.timing_json:
         with open(opt.timing_json, "w") as fh:
             json.dump(stats, fh)

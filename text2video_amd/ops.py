@@ -546,6 +546,68 @@ def tensor2im_u8(x):
     return y
 
 
+_metrics_scratch = {}      # device -> float64 scratch of t2v_image_metrics_u8 (grown on demand; uses are stream-ordered)
+METRICS_DEFINITION = ("psnr = 10 log10(255^2 / mse) and mae over the pixels' 3 channels; ssim = mean SSIM index (Wang et al. "
+                      "2004: 11x11 Gaussian window, sigma 1.5, K1 0.01, K2 0.03, L 255, per channel on the 8-bit values, "
+                      "float64) over the window positions wholly inside the region")
+
+
+def image_metrics_scratch_doubles(H, W, nbox=0):
+    """doubles of scratch t2v_image_metrics_u8 needs for an H x W pair with nbox boxes (0: a shape the call refuses)"""
+    return int(_lib.load().t2v_image_metrics_scratch_doubles(int(H), int(W), int(nbox)))
+
+
+def image_metrics(a, b, boxes=(), out=None, out_row=0, scratch=None):
+    """The sums PSNR / MAE / SSIM are formed from (t2v_image_metrics_u8, include/t2v.h), of two uint8 device images
+    [H,W,3 or 4] (channels 0..2 compared) over the whole frame (row 0) and over boxes = [(y0, y1, x0, x1), ...] (half-open,
+    at most 3; rows 1..): a float64 device tensor [1+nbox, 4] of rows {sse, sad, ssim_sum, ssim_n} -- see metrics_summary.
+    out: a float64 device tensor [R, 4] to write rows [out_row, out_row + 1 + nbox) of instead (its other rows keep their
+    values; returned as it is).  scratch: a float64 device tensor of at least image_metrics_scratch_doubles(H, W, nbox)
+    elements (default: one kept per device).  Two launches, no host synchronisation; a refused call (status
+    T2V_ERR_INVALID) or a scratch / out that is too small raises with nothing launched."""
+    c = context()
+    for t, name in ((a, "a"), (b, "b")):
+        if not (t.is_cuda and t.dtype == torch.uint8 and t.is_contiguous() and t.dim() == 3):
+            raise ValueError("image_metrics: %s must be a contiguous uint8 device tensor [H,W,cs]" % name)
+    H, W = a.shape[0], a.shape[1]
+    if tuple(b.shape[:2]) != (H, W):
+        raise ValueError("image_metrics: a is %dx%d, b is %dx%d" % (H, W, b.shape[0], b.shape[1]))
+    boxes = [tuple(int(v) for v in bx) for bx in boxes]
+    if any(len(bx) != 4 for bx in boxes):
+        raise ValueError("image_metrics: a box is (y0, y1, x0, x1)")
+    nbox = len(boxes)
+    if out is None:
+        out, out_row = torch.empty(1 + nbox, 4, dtype=torch.float64, device=a.device), 0
+    if not (out.is_cuda and out.dtype == torch.float64 and out.is_contiguous() and out.dim() == 2 and out.shape[1] == 4
+            and 0 <= out_row and out_row + 1 + nbox <= out.shape[0]):
+        raise ValueError("image_metrics: out must be a contiguous float64 device tensor [R,4] with rows [%d, %d)"
+                         % (out_row, out_row + 1 + nbox))
+    need = image_metrics_scratch_doubles(H, W, nbox)
+    if scratch is None:
+        scratch = _metrics_scratch.get(str(a.device))
+        if need and (scratch is None or scratch.numel() < need):
+            scratch = _metrics_scratch[str(a.device)] = torch.empty(max(need, 4096), dtype=torch.float64, device=a.device)
+    elif not (scratch.is_cuda and scratch.dtype == torch.float64 and scratch.is_contiguous()):
+        raise ValueError("image_metrics: scratch must be a contiguous float64 device tensor")
+    if need and scratch.numel() < need:
+        raise ValueError("image_metrics: scratch holds %d doubles, %dx%d with %d boxes needs %d" % (scratch.numel(), H, W, nbox, need))
+    host_boxes = (ctypes.c_int32 * (4 * nbox))(*[v for bx in boxes for v in bx]) if nbox else None
+    check(c.lib.t2v_image_metrics_u8(c.handle, _stream(), _p(a), a.shape[2], _p(b), b.shape[2], H, W, host_boxes, nbox,
+                                     _p(scratch), ctypes.c_void_p(out.data_ptr() + out_row * 32)), "image_metrics_u8")
+    return out
+
+
+def metrics_summary(row, n_values):
+    """Host helper: one row {sse, sad, ssim_sum, ssim_n} of image_metrics over n_values compared values (pixels x 3)
+    -> {"mse", "mae", "psnr", "ssim"}; psnr = 10 log10(255^2 / mse), None for identical regions (sse == 0);
+    ssim = ssim_sum / ssim_n, None for a region narrower than the 11x11 window (ssim_n == 0)."""
+    import math
+    sse, sad, ssim_sum, ssim_n = (float(v) for v in row)
+    mse = sse / n_values
+    return {"mse": mse, "mae": sad / n_values, "psnr": None if sse == 0 else 10.0 * math.log10(255.0 * 255.0 / mse),
+            "ssim": None if ssim_n == 0 else ssim_sum / ssim_n}
+
+
 def copy_channels(src, src_c0, dst, dst_c0, nc):
     c = context()
     npix = src.numel() // src.shape[-1]

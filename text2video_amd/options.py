@@ -133,9 +133,15 @@ class TestOptions(BaseOptions):
         g("--use_real_img", action="store_true")
         g("--start_frame", type=int, default=0)
         g("--fifo", type=str, default=None, help="test_fifo.py: named pipe to read requests from")
+        g("--metrics", action="store_true", help="compare every generated frame (before JPEG) with the real frame "
+          "<dataroot>/<phase>_img/<seq>/<same index> on the GPU (ops.image_metrics): PSNR, SSIM and MAE of the frame and of "
+          "its face region, written to <results>/<seq>/metrics.json and under \"metrics\" in --timing_json")
 
     def parse(self, argv=None, save=False):
         opt = super().parse(argv, save)
+        if opt.metrics and opt.shard_chunks:
+            self.parser.error("--metrics with --shard_chunks: a sequence's frames are then spread over the ranks; "
+                              "evaluate whole sequences (drop --shard_chunks)")
         # test.py forces these upstream
         opt.nThreads = 1
         opt.batchSize = 1

@@ -1008,29 +1008,7 @@ class FusedAdam:
 # ------------------------------------------------------------------------------------------------
 # face discriminator crop (--add_face_disc) and the training loop
 # ------------------------------------------------------------------------------------------------
-def get_face_region(pose_maps_u8, fine_size):
-    """(ys, ye, xs, xe) of the face crop for a chunk of frames, or None when no frame shows the key colour.
-
-    [RECALL upstream Vid2VidModelD.get_face_region, --openpose_only branch]: the pixels of ALL frames of the chunk
-    whose colour is the nose-neck limb's [153,0,51] (keypoint2img.py:180; upstream tests the normalised map for
-    R in (0.19,0.21), G < -0.99, B in (-0.61,-0.59), which is that uint8 colour) give one bounding box; the crop is
-    centred on the box's midpoint, side fine_size//32*8 (128 at fineSize 512), the centre clamped to
-    [side/2, dim-1-side/2]; with no such pixel upstream returns an empty region -- the face terms are skipped then.
-    pose_maps_u8: [H,W,3] or [F,H,W,3]."""
-    import numpy as np
-    from .keypoints import NOSE_NECK_RGB
-    a = np.asarray(pose_maps_u8)
-    if a.ndim == 3:
-        a = a[None]
-    H, W = a.shape[1:3]
-    side = max(8, fine_size // 32 * 8)
-    _, ys, xs = np.nonzero((a == np.array(NOSE_NECK_RGB, np.uint8)).all(3))
-    if not ys.size:
-        return None
-    yc, xc = (int(ys.min()) + int(ys.max())) // 2, (int(xs.min()) + int(xs.max())) // 2
-    yc = max(side // 2, min(H - 1 - side // 2, yc))
-    xc = max(side // 2, min(W - 1 - side // 2, xc))
-    return yc - side // 2, yc + side // 2, xc - side // 2, xc + side // 2
+from .keypoints import get_face_region      # noqa: E402,F401 -- the face crop of --add_face_disc (also test.py --metrics)
 
 
 def discriminator_state_dict(input_nc, ndf, n_layers, num_D, norm, seed):
