@@ -595,6 +595,16 @@ int t2v_optical_flow(t2v_ctx* ctx, void* stream, const float* cur, int cur_cs, i
                      int prev_c0, int H, int W, int levels, int iters, int radius, float lambda, float* workspace,
                      float* flow_out);
 
+/* The same flow on the delivered bytes (additive to ABI 22): cur, prev are uint8 HWC frames [H][W][cs] with cs in {3, 4}
+ * chosen per image (a generated frame comes with stride 4, a decoded real frame with 3); channels 0..2 are read.
+ *   grey = (x0 + x1 + x2) / 3.0f with x_c = (v_c / 255.0f - 0.5f) / 0.5f, the value t2v_pose_u8_to_f32 forms: the result is
+ *   bit for bit t2v_optical_flow on the fp32 images that call makes of the same bytes.
+ * Only the launch that forms the grey images differs: workspace size (t2v_optical_flow_workspace_floats), launch count,
+ * refusals (plus a channel stride outside {3, 4}) and the clamped-gather guarantee are those of t2v_optical_flow.
+ * uint8 input cannot be non-finite and det >= (lambda n)^2 > 0, so every flow this call returns is finite. */
+int t2v_optical_flow_u8(t2v_ctx* ctx, void* stream, const uint8_t* cur, int cur_cs, const uint8_t* prev, int prev_cs, int H,
+                        int W, int levels, int iters, int radius, float lambda, float* workspace, float* flow_out);
+
 /* ------------------------------------------------------------------------------------------
  * Image resampling for the training loader (ABI 21): PIL's `Image.resize` of a clip's frames, the crop and
  * torchvision's ToTensor + Normalize(.5, .5) in ONE launch, bit for bit what the CPU path computes.
@@ -657,6 +667,45 @@ int t2v_resample_crop_normalize_u8(t2v_ctx* ctx, void* stream, const uint8_t* sr
 size_t t2v_image_metrics_scratch_doubles(int H, int W, int nbox);
 int t2v_image_metrics_u8(t2v_ctx* ctx, void* stream, const uint8_t* a, int a_cs, const uint8_t* b, int b_cs, int H, int W,
                          const int32_t* boxes /* HOST, [nbox][4] */, int nbox, double* scratch, double* out /* [1+nbox][4] */);
+
+/* ------------------------------------------------------------------------------------------
+ * Temporal-consistency sums (additive to ABI 22): how a generated pair of consecutive frames (a_cur, a_prev) moves, read
+ * against the real pair (b_cur, b_prev) of the same two instants, over the whole frame and up to T2V_METRICS_MAX_BOXES
+ * boxes, in two launches (vid2vid/test.py --metrics_temporal, python -m text2video_amd.evaluate --temporal).
+ *   a_cur, a_prev, b_cur, b_prev: [H][W][cs] uint8 device images, cs in {3, 4} chosen per image; channels 0..2 are read.
+ *   flow_fwd, flow_bwd, flow_a: fp32 [H][W][4] = (u, v, -, -) in pixels, the layout t2v_optical_flow writes:
+ *     flow_fwd on b_cur's grid, pointing into b_prev; flow_bwd on b_prev's grid, pointing into b_cur; flow_a on a_cur's
+ *     grid, pointing into a_prev -- flow_a may be NULL.
+ *   boxes: HOST memory, [nbox][4] = y0, y1, x0, x1 (half-open); regions and their refusals are those of
+ *   t2v_image_metrics_u8: region 0 is the whole frame, region r = 1..nbox is box r-1.
+ *   out (device, doubles) row r = {n_valid, warp_sse_a, warp_sse_b, n_flow, epe_sum, tdiff_sse} of region r.
+ * Everything in float64, evaluated from the fp32 / uint8 inputs.  For a pixel p = (x, y) of the region, f = flow_fwd(p):
+ *   q = (x + f.u, y + f.v); p is INSIDE when f is finite and 0 <= q.x <= W-1 and 0 <= q.y <= H-1;
+ *   bilinear(I; q) = (1-fy)((1-fx) I(x0,y0) + fx I(x1,y0)) + fy((1-fx) I(x0,y1) + fx I(x1,y1)), x0 = floor(q.x),
+ *     x1 = min(x0+1, W-1), fx = q.x - x0, likewise in y;  bq = bilinear(flow_bwd; q);
+ *   p is VALID when it is inside, bq is finite and |f + bq|^2 <= 0.01 (|f|^2 + |bq|^2) + 0.5 -- the forward-backward check
+ *     of Sundaram, Brox, Keutzer 2010, the occlusion mask Ruder et al. 2016 and Lai et al. 2018 use for their warping error;
+ *   n_valid = number of valid pixels;
+ *   warp_sse_a = sum over valid p and the 3 channels of (a_cur_c(p) - bilinear(a_prev_c; q))^2;
+ *   warp_sse_b = the same sum on b: the floor the flow's own error leaves on the real pair, what warp_sse_a is read against;
+ *   n_flow, epe_sum: over ALL pixels of the region where f and ga = flow_a(p) are both finite, their number and
+ *     sum sqrt((ga.u - f.u)^2 + (ga.v - f.v)^2) -- the tOF of Chu et al. 2020 (TecoGAN); both 0 when flow_a is NULL;
+ *   tdiff_sse = sum over ALL pixels and the 3 channels of ((a_cur - a_prev) - (b_cur - b_prev))^2, an exact integer
+ *     (< 2^53): the flicker term that depends on no flow.  n_valid and n_flow are exact integers too.
+ *   scratch: t2v_temporal_metrics_scratch_doubles(H, W, nbox) doubles of device memory (one partial per 32x16 tile, region
+ *   and quantity; 0 for a shape the call refuses), any content; the caller vouches for its size.
+ * Every gather coordinate is clamped (fmin / fmax) before it becomes an index: a non-finite or huge flow value makes its
+ * pixel invalid / not counted and can never address outside a plane.  Every tile's partial sums are added in a fixed order
+ * by the second launch: no atomics, two calls give the same bits, and row 0 has the same bits whatever boxes are passed.
+ * Rows of `out` past 1 + nbox are not touched.  No allocation, no host synchronisation.  Refused with T2V_ERR_INVALID and
+ * nothing launched: a null image, flow_fwd, flow_bwd, scratch or out, a channel stride outside {3, 4}, H or W outside
+ * 1..T2V_METRICS_MAX_SIDE, nbox outside 0..T2V_METRICS_MAX_BOXES, an empty box or one that leaves the frame.
+ * ------------------------------------------------------------------------------------------ */
+size_t t2v_temporal_metrics_scratch_doubles(int H, int W, int nbox);
+int t2v_temporal_metrics_u8(t2v_ctx* ctx, void* stream, const uint8_t* a_cur, int a_cur_cs, const uint8_t* a_prev, int a_prev_cs,
+                            const uint8_t* b_cur, int b_cur_cs, const uint8_t* b_prev, int b_prev_cs, const float* flow_fwd,
+                            const float* flow_bwd, const float* flow_a /* may be NULL */, int H, int W,
+                            const int32_t* boxes /* HOST, [nbox][4] */, int nbox, double* scratch, double* out /* [1+nbox][6] */);
 
 /* ------------------------------------------------------------------------------------------
  * Host plumbing (ABI 14): device buffers, pinned host buffers, copies, streams and events for a host that has no HIP

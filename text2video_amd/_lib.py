@@ -184,6 +184,13 @@ SIGNATURES = {
     "t2v_image_metrics_scratch_doubles": (c_size_t, [c_int, c_int, c_int]),
     "t2v_image_metrics_u8": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_int,
                                      c_void_p, c_void_p]),
+    # temporal consistency (additive to ABI 22): the flow on uint8 frames, and the sums of a generated pair against the real
+    # pair (four uint8 images with their strides, three fp32 flows -- the last may be None --, host boxes)
+    "t2v_optical_flow_u8": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int,
+                                    c_float, c_void_p, c_void_p]),
+    "t2v_temporal_metrics_scratch_doubles": (c_size_t, [c_int, c_int, c_int]),
+    "t2v_temporal_metrics_u8": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int,
+                                        c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p]),
     # host plumbing (ABI 14): what text2video_amd/leantorch.py allocates, copies and synchronises with
     "t2v_device_malloc": (c_int, [c_void_p, c_size_t, POINTER(c_void_p)]),
     "t2v_device_free": (c_int, [c_void_p, c_void_p]),

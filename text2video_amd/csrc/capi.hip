@@ -1502,6 +1502,21 @@ int t2v_optical_flow(t2v_ctx* ctx, void* stream, const float* cur, int cur_cs, i
                                lambda, workspace, flow_out);
 }
 
+// the same flow on uint8 HWC frames (additive to ABI 22): only the grey launch differs
+int t2v_optical_flow_u8(t2v_ctx* ctx, void* stream, const uint8_t* cur, int cur_cs, const uint8_t* prev, int prev_cs, int H,
+                        int W, int levels, int iters, int radius, float lambda, float* workspace, float* flow_out) {
+    T2V_REQUIRE(ctx && cur && prev && workspace && flow_out, "optical_flow_u8: null pointer");
+    T2V_REQUIRE(H >= 8 && W >= 8, "optical_flow_u8: H, W must be >= 8 (got %d x %d)", H, W);
+    T2V_REQUIRE(optical_flow_shape_ok(H, W, levels), "optical_flow_u8: unsupported size %d x %d or level count %d", H, W, levels);
+    T2V_REQUIRE(radius >= 1 && radius <= 7, "optical_flow_u8: radius must be in 1..7 (got %d)", radius);
+    T2V_REQUIRE(iters >= 1, "optical_flow_u8: iters must be >= 1 (got %d)", iters);
+    T2V_REQUIRE(lambda > 0.f, "optical_flow_u8: lambda must be > 0");
+    T2V_REQUIRE((cur_cs == 3 || cur_cs == 4) && (prev_cs == 3 || prev_cs == 4),
+                "optical_flow_u8: channel strides must be 3 or 4 (got %d and %d)", cur_cs, prev_cs);
+    return launch_optical_flow_u8((hipStream_t)stream, cur, cur_cs, prev, prev_cs, H, W, levels, iters, radius, lambda, workspace,
+                                  flow_out);
+}
+
 // ---- image resampling for the training loader (ABI 21) ----
 int t2v_resample_crop_normalize_u8(t2v_ctx* ctx, void* stream, const uint8_t* src, int T, int h, int w,
                                    const int32_t* x_first, const int32_t* x_count, const int32_t* x_coef, int kx, int out_w,
@@ -1545,6 +1560,35 @@ int t2v_image_metrics_u8(t2v_ctx* ctx, void* stream, const uint8_t* a, int a_cs,
                     q[1], q[2], q[3], H, W);
     }
     return launch_image_metrics_u8((hipStream_t)stream, a, a_cs, b, b_cs, H, W, boxes, nbox, scratch, out);
+}
+
+// ---- temporal-consistency sums of a generated pair against the real pair (additive to ABI 22) ----
+size_t t2v_temporal_metrics_scratch_doubles(int H, int W, int nbox) {
+    return image_metrics_shape_ok(H, W, nbox) ? temporal_metrics_scratch_doubles(H, W, nbox) : 0;
+}
+int t2v_temporal_metrics_u8(t2v_ctx* ctx, void* stream, const uint8_t* a_cur, int a_cur_cs, const uint8_t* a_prev, int a_prev_cs,
+                            const uint8_t* b_cur, int b_cur_cs, const uint8_t* b_prev, int b_prev_cs, const float* flow_fwd,
+                            const float* flow_bwd, const float* flow_a, int H, int W, const int32_t* boxes, int nbox,
+                            double* scratch, double* out) {
+    T2V_REQUIRE(ctx && a_cur && a_prev && b_cur && b_prev && flow_fwd && flow_bwd && scratch && out,
+                "temporal_metrics_u8: null pointer");
+    const int cs[4] = {a_cur_cs, a_prev_cs, b_cur_cs, b_prev_cs};
+    for (int i = 0; i < 4; ++i)
+        T2V_REQUIRE(cs[i] == 3 || cs[i] == 4, "temporal_metrics_u8: channel strides must be 3 or 4 (got %d, %d, %d, %d)", cs[0],
+                    cs[1], cs[2], cs[3]);
+    T2V_REQUIRE(H >= 1 && W >= 1 && H <= T2V_METRICS_MAX_SIDE && W <= T2V_METRICS_MAX_SIDE,
+                "temporal_metrics_u8: H, W must be in 1..%d (got %d x %d)", T2V_METRICS_MAX_SIDE, H, W);
+    T2V_REQUIRE(nbox >= 0 && nbox <= T2V_METRICS_MAX_BOXES, "temporal_metrics_u8: nbox must be in 0..%d (got %d)",
+                T2V_METRICS_MAX_BOXES, nbox);
+    T2V_REQUIRE(nbox == 0 || boxes, "temporal_metrics_u8: %d boxes and a null box pointer", nbox);
+    for (int i = 0; i < nbox; ++i) {
+        const int32_t* q = boxes + 4 * i;
+        T2V_REQUIRE(q[0] >= 0 && q[0] < q[1] && q[1] <= H && q[2] >= 0 && q[2] < q[3] && q[3] <= W,
+                    "temporal_metrics_u8: box %d = rows [%d, %d) x columns [%d, %d) is empty or outside the %d x %d frame", i,
+                    q[0], q[1], q[2], q[3], H, W);
+    }
+    return launch_temporal_metrics_u8((hipStream_t)stream, a_cur, a_cur_cs, a_prev, a_prev_cs, b_cur, b_cur_cs, b_prev, b_prev_cs,
+                                      flow_fwd, flow_bwd, flow_a, H, W, boxes, nbox, scratch, out);
 }
 
 // ---- host plumbing (ABI 14): buffers, copies, streams, events for a host without a HIP binding of its own ----

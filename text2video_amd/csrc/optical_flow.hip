@@ -1,5 +1,5 @@
-// Dense optical flow between two frames: coarse-to-fine iterative Lucas-Kanade on the grey images (t2v_optical_flow,
-// include/t2v.h) -- the reference flow of the train step's flow / warp losses, which upstream takes from FlowNet2.
+// Dense optical flow between two frames: coarse-to-fine iterative Lucas-Kanade on the grey images (t2v_optical_flow and
+// t2v_optical_flow_u8, which differ in the launch that forms the grey images only; include/t2v.h) -- the reference flow of the train step's flow / warp losses, which upstream takes from FlowNet2.
 // Fully local: every output pixel is a fixed function of a fixed neighbourhood, no atomics, no global solve, so two
 // calls give the same bits.  tests/flow_reference.py restates the algorithm in float64.
 //
@@ -37,6 +37,24 @@ __global__ __launch_bounds__(256) void flow_grey_kernel(const float* __restrict_
     for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < npix; i += stride) {
         const float* p = src + i * cs + c0;
         dst[i] = (p[0] + p[1] + p[2]) / 3.0f;
+    }
+}
+
+// the same grey images from uint8 HWC frames (t2v_optical_flow_u8): x_c = (v_c / 255 - 0.5) / 0.5 as t2v_pose_u8_to_f32 forms
+// it (the true quotient), then (x0 + x1 + x2) / 3 -- bit for bit flow_grey_kernel on the fp32 image of the same bytes
+__global__ __launch_bounds__(256) void flow_grey_u8_kernel(const uint8_t* __restrict__ cur, int cur_cs,
+                                                           const uint8_t* __restrict__ prev, int prev_cs,
+                                                           float* __restrict__ g_cur, float* __restrict__ g_prev, long npix) {
+    const uint8_t* src = blockIdx.y ? prev : cur;
+    const int cs = blockIdx.y ? prev_cs : cur_cs;
+    float* dst = blockIdx.y ? g_prev : g_cur;
+    const long stride = (long)gridDim.x * blockDim.x;
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < npix; i += stride) {
+        const uint8_t* p = src + i * cs;
+        const float x0 = ((float)p[0] / 255.0f - 0.5f) / 0.5f;
+        const float x1 = ((float)p[1] / 255.0f - 0.5f) / 0.5f;
+        const float x2 = ((float)p[2] / 255.0f - 0.5f) / 0.5f;
+        dst[i] = (x0 + x1 + x2) / 3.0f;
     }
 }
 
@@ -275,8 +293,12 @@ size_t optical_flow_workspace_floats(int H, int W, int levels) {
     return n;
 }
 
-int launch_optical_flow(hipStream_t s, const float* cur, int cur_cs, int cur_c0, const float* prev, int prev_cs, int prev_c0,
-                        int H, int W, int levels, int iters, int radius, float lambda, float* workspace, float* flow_out) {
+namespace {
+
+// everything but the source of the finest level's grey images: grey(g_cur, g_prev) enqueues the one launch that writes them
+template <class GreyLaunch>
+int launch_flow(hipStream_t s, GreyLaunch grey, int H, int W, int levels, int iters, int radius, float lambda, float* workspace,
+                float* flow_out) {
     if (levels == 0) levels = optical_flow_default_levels(H, W);
     int hs[kMaxLevels], ws[kMaxLevels];
     float *g_cur[kMaxLevels], *g_prev[kMaxLevels];
@@ -292,8 +314,7 @@ int launch_optical_flow(hipStream_t s, const float* cur, int cur_cs, int cur_c0,
         uv[l][1] = reinterpret_cast<float2*>(p + 4 * n);
         p += 6 * n;
     }
-    hipLaunchKernelGGL(flow_grey_kernel, dim3(blocks_for((long)H * W), 2), dim3(256), 0, s, cur, cur_cs, cur_c0, prev, prev_cs,
-                       prev_c0, g_cur[0], g_prev[0], (long)H * W);
+    grey(g_cur[0], g_prev[0]);
     for (int l = 1; l < levels; ++l)
         hipLaunchKernelGGL(flow_pool_kernel, dim3(blocks_for((long)hs[l] * ws[l]), 2), dim3(256), 0, s, g_cur[l - 1],
                            g_prev[l - 1], g_cur[l], g_prev[l], hs[l - 1], ws[l - 1], hs[l], ws[l]);
@@ -331,6 +352,30 @@ int launch_optical_flow(hipStream_t s, const float* cur, int cur_cs, int cur_c0,
                        reinterpret_cast<float4*>(flow_out), H, W);
     T2V_HIP_CHECK(hipGetLastError());
     return T2V_OK;
+}
+
+}  // namespace
+
+int launch_optical_flow(hipStream_t s, const float* cur, int cur_cs, int cur_c0, const float* prev, int prev_cs, int prev_c0,
+                        int H, int W, int levels, int iters, int radius, float lambda, float* workspace, float* flow_out) {
+    return launch_flow(
+        s,
+        [&](float* g_cur, float* g_prev) {
+            hipLaunchKernelGGL(flow_grey_kernel, dim3(blocks_for((long)H * W), 2), dim3(256), 0, s, cur, cur_cs, cur_c0, prev,
+                               prev_cs, prev_c0, g_cur, g_prev, (long)H * W);
+        },
+        H, W, levels, iters, radius, lambda, workspace, flow_out);
+}
+
+int launch_optical_flow_u8(hipStream_t s, const uint8_t* cur, int cur_cs, const uint8_t* prev, int prev_cs, int H, int W,
+                           int levels, int iters, int radius, float lambda, float* workspace, float* flow_out) {
+    return launch_flow(
+        s,
+        [&](float* g_cur, float* g_prev) {
+            hipLaunchKernelGGL(flow_grey_u8_kernel, dim3(blocks_for((long)H * W), 2), dim3(256), 0, s, cur, cur_cs, prev, prev_cs,
+                               g_cur, g_prev, (long)H * W);
+        },
+        H, W, levels, iters, radius, lambda, workspace, flow_out);
 }
 
 }  // namespace t2v

@@ -421,6 +421,8 @@ bool optical_flow_shape_ok(int H, int W, int levels);
 size_t optical_flow_workspace_floats(int H, int W, int levels);
 int launch_optical_flow(hipStream_t s, const float* cur, int cur_cs, int cur_c0, const float* prev, int prev_cs, int prev_c0,
                         int H, int W, int levels, int iters, int radius, float lambda, float* workspace, float* flow_out);
+int launch_optical_flow_u8(hipStream_t s, const uint8_t* cur, int cur_cs, const uint8_t* prev, int prev_cs, int H, int W,
+                           int levels, int iters, int radius, float lambda, float* workspace, float* flow_out);
 
 // image_resample.hip: table-driven 8-bit resampling + crop + normalise (t2v_resample_crop_normalize_u8)
 int resample_max_taps();
@@ -433,6 +435,13 @@ int launch_resample_crop_normalize_u8(hipStream_t s, const uint8_t* src, int T, 
 size_t image_metrics_scratch_doubles(int H, int W, int nbox);
 int launch_image_metrics_u8(hipStream_t s, const uint8_t* a, int a_cs, const uint8_t* b, int b_cs, int H, int W,
                             const int32_t* boxes, int nbox, double* scratch, double* out);
+
+// temporal_metrics.hip: arguments already validated (t2v_temporal_metrics_u8); flow_a may be null
+size_t temporal_metrics_scratch_doubles(int H, int W, int nbox);
+int launch_temporal_metrics_u8(hipStream_t s, const uint8_t* a_cur, int a_cur_cs, const uint8_t* a_prev, int a_prev_cs,
+                               const uint8_t* b_cur, int b_cur_cs, const uint8_t* b_prev, int b_prev_cs, const float* flow_fwd,
+                               const float* flow_bwd, const float* flow_a, int H, int W, const int32_t* boxes, int nbox,
+                               double* scratch, double* out);
 
 }  // namespace t2v
 

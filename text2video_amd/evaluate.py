@@ -1,10 +1,14 @@
-"""python -m text2video_amd.evaluate DIR_A DIR_B [--pattern 'fake_B_*'] [--json OUT]
+"""python -m text2video_amd.evaluate DIR_A DIR_B [--pattern 'fake_B_*'] [--temporal] [--json OUT]
 
 PSNR / SSIM / MAE between the image files of two result trees, paired by relative path: the picture-level answer to "what
 does --arith bf16x2 do to my model" (the same test.py command run twice) and "epoch 20 against epoch 40".  The files are
 decoded with Pillow and compared on the GPU by the kernel of `test.py --metrics` (ops.image_metrics, whole frame only).
 Prints and (--json) writes one summary per sequence (= directory) and one overall.  Unpaired files and pairs of different
 sizes are listed and make the exit status 1.
+
+--temporal adds the temporal-consistency figures of `test.py --metrics_temporal` (ops.optical_flow_u8 + ops.temporal_metrics):
+within each directory, files that are consecutive in the sorted paired list form the pairs (t-1, t); A = DIR_A is read against
+B = DIR_B, whose flows give the forward-backward mask.  Every summary gains a "temporal" entry, pooled over sums.
 """
 import argparse
 import fnmatch
@@ -32,8 +36,13 @@ def pair_files(dir_a, dir_b, pattern="fake_B_*"):
     return [p for p in a if p in sb], [p for p in a if p not in sb], [p for p in b if p not in sa]
 
 
-def compare_trees(dir_a, dir_b, pattern="fake_B_*", device="cuda:0"):
-    """-> the report: {"definition", "overall", "sequences": {dir: summary}, "unpaired_a", "unpaired_b", "size_mismatch"}"""
+MIN_FLOW_SIDE = 8        # ops.optical_flow_u8 refuses smaller frames
+
+
+def compare_trees(dir_a, dir_b, pattern="fake_B_*", device="cuda:0", temporal=False):
+    """-> the report: {"definition", "overall", "sequences": {dir: summary}, "unpaired_a", "unpaired_b", "size_mismatch"};
+    temporal: every summary gains "temporal" (metrics.pool_temporal over the directory's consecutive pairs), the report
+    "temporal_definition" and "temporal_skipped" (second files of pairs that changed size or are narrower than 8 pixels)"""
     import numpy as np
     from PIL import Image
     from ._xp import torch
@@ -41,6 +50,7 @@ def compare_trees(dir_a, dir_b, pattern="fake_B_*", device="cuda:0"):
     from . import ops
     pairs, only_a, only_b = pair_files(dir_a, dir_b, pattern)
     per_seq, mismatch, pending = {}, [], []
+    t_pending, t_skipped, last = [], [], None      # last: (directory, device a, device b) of the previous paired file
     for rel in pairs:
         with Image.open(os.path.join(dir_a, rel)) as im:
             a = np.array(im.convert("RGB"))
@@ -48,16 +58,38 @@ def compare_trees(dir_a, dir_b, pattern="fake_B_*", device="cuda:0"):
             b = np.array(im.convert("RGB"))
         if a.shape != b.shape:
             mismatch.append({"file": rel, "a": [a.shape[1], a.shape[0]], "b": [b.shape[1], b.shape[0]]})
+            last = None
             continue
-        row = ops.image_metrics(torch.from_numpy(a).to(device), torch.from_numpy(b).to(device))
+        da, db = torch.from_numpy(a).to(device), torch.from_numpy(b).to(device)
+        row = ops.image_metrics(da, db)
         pending.append((rel, 3 * a.shape[0] * a.shape[1], row))
+        if temporal:
+            seq = os.path.dirname(rel) or "."
+            if last is not None and last[0] == seq:
+                if tuple(last[1].shape) != a.shape or min(a.shape[:2]) < MIN_FLOW_SIDE:
+                    t_skipped.append(rel)
+                else:
+                    pa, pb = last[1], last[2]
+                    trow = ops.temporal_metrics(da, pa, db, pb, ops.optical_flow_u8(db, pb), ops.optical_flow_u8(pb, db),
+                                                ops.optical_flow_u8(da, pa))
+                    t_pending.append((seq, a.shape[0] * a.shape[1], trow))
+            last = (seq, da, db)
     for rel, n_values, row in pending:       # (the copies wait for the GPU once everything is enqueued)
         s = ops.metrics_summary(row.cpu().numpy()[0], n_values)
         per_seq.setdefault(os.path.dirname(rel) or ".", []).append((s, n_values))
-    return {"definition": ops.METRICS_DEFINITION, "a": dir_a, "b": dir_b, "pattern": pattern,
-            "overall": M._pooled([p for parts in per_seq.values() for p in parts]),
-            "sequences": {seq: M._pooled(parts) for seq, parts in sorted(per_seq.items())},
-            "unpaired_a": only_a, "unpaired_b": only_b, "size_mismatch": mismatch}
+    rep = {"definition": ops.METRICS_DEFINITION, "a": dir_a, "b": dir_b, "pattern": pattern,
+           "overall": M._pooled([p for parts in per_seq.values() for p in parts]),
+           "sequences": {seq: M._pooled(parts) for seq, parts in sorted(per_seq.items())},
+           "unpaired_a": only_a, "unpaired_b": only_b, "size_mismatch": mismatch}
+    if temporal:
+        t_seq = {}
+        for seq, n_pixels, trow in t_pending:
+            t_seq.setdefault(seq, []).append((trow.cpu().numpy()[0], n_pixels))
+        rep["overall"]["temporal"] = M.pool_temporal([p for parts in t_seq.values() for p in parts])
+        for seq, summary in rep["sequences"].items():
+            summary["temporal"] = M.pool_temporal(t_seq.get(seq, []))
+        rep["temporal_definition"], rep["temporal_skipped"] = ops.TEMPORAL_DEFINITION, t_skipped
+    return rep
 
 
 def _fmt(v, spec):
@@ -69,6 +101,7 @@ def main(argv=None):
     ap.add_argument("dir_a")
     ap.add_argument("dir_b")
     ap.add_argument("--pattern", default="fake_B_*", help="shell pattern the files' base names must match")
+    ap.add_argument("--temporal", action="store_true", help="add warping error, tOF and the flicker term of consecutive files")
     ap.add_argument("--json", default=None, metavar="OUT", help="write the report to this file")
     ap.add_argument("--gpu_ids", default="0")
     args = ap.parse_args(argv)
@@ -78,10 +111,15 @@ def main(argv=None):
     if os.environ.get("T2V_LEAN", "1") != "0":
         from . import _xp
         _xp.use_lean()          # no torch needed for an allocator and a stream (honoured when torch is not loaded yet)
-    rep = compare_trees(args.dir_a, args.dir_b, args.pattern, "cuda:%d" % int(str(args.gpu_ids).split(",")[0]))
+    rep = compare_trees(args.dir_a, args.dir_b, args.pattern, "cuda:%d" % int(str(args.gpu_ids).split(",")[0]), args.temporal)
     for seq, s in list(rep["sequences"].items()) + [("overall", rep["overall"])]:
         print("%-24s %4d frames  psnr %s dB  ssim %s  mae %s" % (seq, s["frames"], _fmt(s["psnr"], ".3f"), _fmt(s["ssim"], ".6f"),
                                                                _fmt(s["mae"], ".4f")))
+        if args.temporal:
+            t = s["temporal"]
+            print("%-24s %4d pairs   warp_mse %s (real %s, valid %s)  tof %s px  tdiff_mse %s"
+                  % ("", t["pairs"], _fmt(t["warp_mse"], ".3f"), _fmt(t["warp_mse_real"], ".3f"), _fmt(t["valid"], ".3f"),
+                     _fmt(t["tof"], ".4f"), _fmt(t["tdiff_mse"], ".3f")))
     for key, what in (("unpaired_a", "only under %s" % args.dir_a), ("unpaired_b", "only under %s" % args.dir_b)):
         for f in rep[key]:
             print("unpaired (%s): %s" % (what, f), file=sys.stderr)

@@ -420,6 +420,29 @@ class Tensor:
             empty(self.shape, dtype=self.dtype, pin_memory=True)
         return out.copy_(self)
 
+    # -- device views (dim 0 only; they keep the owner alive and give nothing back themselves) ---------
+    def _view_of(self, shape, byte_offset):
+        if self._where != "cuda":
+            raise TypeError("leantorch: views of %s tensors" % self._where)
+        v = Tensor(shape, self.dtype, "cuda", ptr=self._ptr + byte_offset, size=0, dev=self._dev)
+        v._base = self if self._base is None else self._base
+        return v
+
+    def narrow(self, dim, start, length):
+        if dim != 0 or not (0 <= start and 0 <= length and start + length <= self.shape[0]):
+            raise ValueError("leantorch.narrow: dim 0 within the tensor only")
+        row = self.nbytes() // self.shape[0] if self.shape[0] else 0
+        return self._view_of((length,) + self.shape[1:], start * row)
+
+    def view(self, *shape):
+        shp = _shape(shape)
+        n = 1
+        for v in shp:
+            n *= v
+        if n != self.numel():
+            raise ValueError("leantorch.view: %s as %s" % (self.shape, shp))
+        return self._view_of(shp, 0)
+
     def zero_(self):
         if self._where == "cuda":
             d = self._dev

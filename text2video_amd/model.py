@@ -173,6 +173,7 @@ def run_test(opt, model=None, device=None, dataset=None):
     first_steps = dataset.iter_lanes(n_lanes, opt.pose_workers, limit=limit)
     # --metrics: the real frames of the same items, decoded on threads ahead of the loop (text2video_amd/metrics.py)
     want_metrics = bool(getattr(opt, "metrics", False))
+    want_temporal = want_metrics and bool(getattr(opt, "metrics_temporal", False))      # (+ the pair (t-1, t): metrics.py)
     real_frames, seq_metrics = None, []      # seq_metrics: (event, pinned rows, SequenceRows) per finished sequence
     if want_metrics:
         from . import metrics as M
@@ -221,12 +222,13 @@ def run_test(opt, model=None, device=None, dataset=None):
             from .generator import Recurrence
             self.rec, self.window, self.dev_maps, self.unit = Recurrence(), None, None, None
             self.metrics = self.real_dev = None      # --metrics: this sequence's rows, the real frame on the device
+            self.real_other = None                   # --metrics_temporal: the buffer the previous real frame stays in
 
     def close_metrics(L):
         """the sequence of lane L has ended: its rows go to the host in one copy (read after the loop)"""
         if L.metrics is not None and L.metrics.frames:
-            host = torch.empty(L.metrics.rows.shape, dtype=torch.float64, pin_memory=True)
-            host.copy_(L.metrics.rows, non_blocking=True)
+            host = torch.empty(L.metrics.buf.shape, dtype=torch.float64, pin_memory=True)
+            host.copy_(L.metrics.buf, non_blocking=True)
             ev = torch.cuda.Event()
             ev.record()
             seq_metrics.append((ev, host, L.metrics))
@@ -263,7 +265,7 @@ def run_test(opt, model=None, device=None, dataset=None):
                                  % ((data["A_path"],) + real.shape[:2] + tuple(u8.shape[:2])))
             if L.metrics is None or L.metrics.seq != data["seq"]:
                 close_metrics(L)
-                L.metrics = M.SequenceRows(torch, data["seq"], dataset.seq_lengths()[data["seq"]], dev)
+                L.metrics = M.SequenceRows(torch, data["seq"], dataset.seq_lengths()[data["seq"]], dev, want_temporal)
             ring = pinned.get((k, "real") + real.shape)
             if ring is None:
                 ring = pinned[(k, "real") + real.shape] = \
@@ -271,6 +273,8 @@ def run_test(opt, model=None, device=None, dataset=None):
             stage = ring[0][ring[1] % 3]     # (its upload of frame n-3 ran before the frame whose event finish(n-2) waited for)
             ring[1] += 1
             stage.numpy()[...] = real
+            if want_temporal:      # the previous real frame stays where it is until this frame's pair has been compared
+                L.real_dev, L.real_other = L.real_other, L.real_dev
             if L.real_dev is None or tuple(L.real_dev.shape) != real.shape:
                 L.real_dev = torch.empty(real.shape, dtype=torch.uint8, device=dev)
             L.real_dev.copy_(stage, non_blocking=True)
@@ -322,6 +326,7 @@ def run_test(opt, model=None, device=None, dataset=None):
                 else:
                     outs = model.inference_nhwc_batch([L.window for _, L, _ in members], [L.rec for _, L, _ in members])
                 split["generator_s"] = split.get("generator_s", 0.0) + time.perf_counter() - tg
+                compare = []      # --metrics: after EVERY member's D2H event, so that no frame's JPEG waits for a comparison
                 for (k, L, data), out in zip(members, outs):
                     t1 = time.perf_counter()
                     u8 = ops.tensor2im_u8(out)
@@ -336,14 +341,17 @@ def run_test(opt, model=None, device=None, dataset=None):
                     t3 = time.perf_counter()
                     ev = torch.cuda.Event()
                     ev.record()
-                    if want_metrics:      # (after the event: the frame's JPEG does not wait for the comparison)
-                        compare_with_real(k, L, data, u8)
-                        split["metrics_s"] = split.get("metrics_s", 0.0) + time.perf_counter() - t3
+                    if want_metrics:
+                        compare.append((k, L, data, u8))
                     split["tensor2im_s"] = split.get("tensor2im_s", 0.0) + t2 - t1
                     split["d2h_s"] = split.get("d2h_s", 0.0) + t3 - t2
                     now.append((ev, host, data["A_path"], _real_A_u8(data["A"][-1])))
                     print("process image... %s" % data["A_path"])
                     counters["n"] += 1
+                for k, L, data, u8 in compare:
+                    t3 = time.perf_counter()
+                    compare_with_real(k, L, data, u8)
+                    split["metrics_s"] = split.get("metrics_s", 0.0) + time.perf_counter() - t3
             split["enqueue_s"] += time.perf_counter() - tq
             if "first_step_s" not in marks:       # incl. the weight pack / Winograd filter transforms of this geometry
                 torch.cuda.synchronize(dev)
@@ -386,7 +394,7 @@ def run_test(opt, model=None, device=None, dataset=None):
         real_frames.close()
         for ev, host, rows in seq_metrics:       # <results>/<seq>/metrics.json, by the process that generated the sequence
             ev.synchronize()
-            doc = M.summarise(rows.frames, host.numpy())
+            doc = M.summarise(rows.frames, *rows.split_host(host.numpy()))
             M.write_json(os.path.join(vis.save_dir, rows.seq, "metrics.json"), doc)
             metrics_out[rows.seq] = doc["summary"]
     marks["to_last_jpeg_s"] = time.perf_counter() - t_start

@@ -408,6 +408,37 @@ def optical_flow(cur, prev, cur_c0=0, prev_c0=0, levels=None, iters=3, radius=3,
     return out
 
 
+def optical_flow_u8(cur, prev, levels=None, iters=3, radius=3, lam=1e-3, out=None, workspace=None):
+    """optical_flow on the delivered bytes (t2v_optical_flow_u8): cur, prev uint8 device images [H,W,3 or 4] (channels 0..2,
+    the stride chosen per image) -> [H,W,4] = (u, v, 0, 0), bit for bit optical_flow on the fp32 images pose_u8_to_f32 makes
+    of the same bytes.  Workspace, level rule and refusals as optical_flow; the flows are finite."""
+    c = context()
+    for t, name in ((cur, "cur"), (prev, "prev")):
+        if not (t.is_cuda and t.dtype == torch.uint8 and t.is_contiguous() and t.dim() == 3):
+            raise ValueError("optical_flow_u8: %s must be a contiguous uint8 device tensor [H,W,cs]" % name)
+    H, W = cur.shape[0], cur.shape[1]
+    if tuple(prev.shape[:2]) != (H, W):
+        raise ValueError("optical_flow_u8: cur and prev must be [H,W,C] of one size")
+    lv = int(levels or 0)
+    need = c.lib.t2v_optical_flow_workspace_floats(H, W, lv)
+    if workspace is None:
+        key = (cur.device, H, W, lv)
+        workspace = _flow_workspaces.get(key)
+        if workspace is None and need:
+            workspace = _flow_workspaces[key] = optical_flow_workspace(H, W, levels, cur.device)
+    elif not (workspace.is_cuda and workspace.dtype == torch.float32 and workspace.is_contiguous()) or workspace.numel() < need:
+        raise ValueError("optical_flow_u8: workspace must be a contiguous fp32 device tensor of the stated size")
+    if workspace is None:      # a shape the library refuses: let it say so (nothing is launched, the pointer is not read)
+        workspace = cur
+    out = torch.empty(H, W, 4, dtype=torch.float32, device=cur.device) if out is None else out
+    _chk(out, "out")
+    if tuple(out.shape) != (H, W, 4):
+        raise ValueError("optical_flow_u8: out must be [H,W,4]")
+    check(c.lib.t2v_optical_flow_u8(c.handle, _stream(), _p(cur), cur.shape[2], _p(prev), prev.shape[2], H, W, lv, int(iters),
+                                    int(radius), float(lam), _p(workspace), _p(out)), "optical_flow_u8")
+    return out
+
+
 def avgpool3x3s2(x):
     """AvgPool2d(3, 2, 1, count_include_pad=False) on [H,W,C]."""
     c = context()
@@ -606,6 +637,80 @@ def metrics_summary(row, n_values):
     mse = sse / n_values
     return {"mse": mse, "mae": sad / n_values, "psnr": None if sse == 0 else 10.0 * math.log10(255.0 * 255.0 / mse),
             "ssim": None if ssim_n == 0 else ssim_sum / ssim_n}
+
+
+TEMPORAL_DEFINITION = ("warp_mse = mean squared error (8-bit units) between frame t and frame t-1 warped by the REAL pair's flow, "
+                       "over pixels passing the forward-backward check |f+b|^2 <= 0.01(|f|^2+|b|^2)+0.5 (valid = their share); "
+                       "warp_mse_real = the same on the real pair (the floor); tof = mean endpoint error in px between the "
+                       "generated pair's flow and the real pair's; tdiff_mse = mean ((a_t - a_t-1) - (b_t - b_t-1))^2; flows: "
+                       "ops.optical_flow_u8 (coarse-to-fine Lucas-Kanade), float64 sums")
+TEMPORAL_COLUMNS = 6       # n_valid, warp_sse_a, warp_sse_b, n_flow, epe_sum, tdiff_sse
+
+
+def temporal_metrics_scratch_doubles(H, W, nbox=0):
+    """doubles of scratch t2v_temporal_metrics_u8 needs for H x W frames with nbox boxes (0: a shape the call refuses)"""
+    return int(_lib.load().t2v_temporal_metrics_scratch_doubles(int(H), int(W), int(nbox)))
+
+
+def temporal_metrics(a_cur, a_prev, b_cur, b_prev, flow_fwd, flow_bwd, flow_a=None, boxes=(), out=None, out_row=0, scratch=None):
+    """The sums the temporal-consistency figures are formed from (t2v_temporal_metrics_u8, include/t2v.h): a_cur, a_prev
+    (generated, frames t and t-1) and b_cur, b_prev (real) are uint8 device images [H,W,3 or 4]; flow_fwd = the flow from
+    b_cur to b_prev, flow_bwd = from b_prev to b_cur, flow_a = from a_cur to a_prev or None, fp32 [H,W,4] as optical_flow
+    writes them.  -> a float64 device tensor [1+nbox, 6] of rows {n_valid, warp_sse_a, warp_sse_b, n_flow, epe_sum,
+    tdiff_sse} over the whole frame (row 0) and boxes = [(y0, y1, x0, x1), ...] (at most 3) -- see temporal_summary.
+    out / out_row / scratch: as image_metrics (rows of 6; temporal_metrics_scratch_doubles).  Two launches, no host
+    synchronisation; a refused call or a scratch / out that is too small raises with nothing launched."""
+    c = context()
+    H, W = a_cur.shape[0], a_cur.shape[1]
+    for t, name in ((a_cur, "a_cur"), (a_prev, "a_prev"), (b_cur, "b_cur"), (b_prev, "b_prev")):
+        if not (t.is_cuda and t.dtype == torch.uint8 and t.is_contiguous() and t.dim() == 3):
+            raise ValueError("temporal_metrics: %s must be a contiguous uint8 device tensor [H,W,cs]" % name)
+        if tuple(t.shape[:2]) != (H, W):
+            raise ValueError("temporal_metrics: a_cur is %dx%d, %s is %dx%d" % (H, W, name, t.shape[0], t.shape[1]))
+    for t, name in ((flow_fwd, "flow_fwd"), (flow_bwd, "flow_bwd"), (flow_a, "flow_a")):
+        if t is None and name == "flow_a":
+            continue
+        if t is None or not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == (H, W, 4)):
+            raise ValueError("temporal_metrics: %s must be a contiguous fp32 device tensor [%d,%d,4]" % (name, H, W))
+    boxes = [tuple(int(v) for v in bx) for bx in boxes]
+    if any(len(bx) != 4 for bx in boxes):
+        raise ValueError("temporal_metrics: a box is (y0, y1, x0, x1)")
+    nbox = len(boxes)
+    if out is None:
+        out, out_row = torch.empty(1 + nbox, TEMPORAL_COLUMNS, dtype=torch.float64, device=a_cur.device), 0
+    if not (out.is_cuda and out.dtype == torch.float64 and out.is_contiguous() and out.dim() == 2
+            and out.shape[1] == TEMPORAL_COLUMNS and 0 <= out_row and out_row + 1 + nbox <= out.shape[0]):
+        raise ValueError("temporal_metrics: out must be a contiguous float64 device tensor [R,6] with rows [%d, %d)"
+                         % (out_row, out_row + 1 + nbox))
+    need = temporal_metrics_scratch_doubles(H, W, nbox)
+    if scratch is None:
+        scratch = _metrics_scratch.get(str(a_cur.device))
+        if need and (scratch is None or scratch.numel() < need):
+            scratch = _metrics_scratch[str(a_cur.device)] = torch.empty(max(need, 4096), dtype=torch.float64, device=a_cur.device)
+    elif not (scratch.is_cuda and scratch.dtype == torch.float64 and scratch.is_contiguous()):
+        raise ValueError("temporal_metrics: scratch must be a contiguous float64 device tensor")
+    if need and scratch.numel() < need:
+        raise ValueError("temporal_metrics: scratch holds %d doubles, %dx%d with %d boxes needs %d"
+                         % (scratch.numel(), H, W, nbox, need))
+    host_boxes = (ctypes.c_int32 * (4 * nbox))(*[v for bx in boxes for v in bx]) if nbox else None
+    check(c.lib.t2v_temporal_metrics_u8(c.handle, _stream(), _p(a_cur), a_cur.shape[2], _p(a_prev), a_prev.shape[2], _p(b_cur),
+                                        b_cur.shape[2], _p(b_prev), b_prev.shape[2], _p(flow_fwd), _p(flow_bwd), _p(flow_a), H, W,
+                                        host_boxes, nbox, _p(scratch),
+                                        ctypes.c_void_p(out.data_ptr() + out_row * 8 * TEMPORAL_COLUMNS)), "temporal_metrics_u8")
+    return out
+
+
+def temporal_summary(row, n_pixels):
+    """Host helper: one row {n_valid, warp_sse_a, warp_sse_b, n_flow, epe_sum, tdiff_sse} of temporal_metrics over a region of
+    n_pixels pixels -> {"warp_mse": warp_sse_a / (3 n_valid), "warp_mse_real": warp_sse_b / (3 n_valid), "valid": n_valid /
+    n_pixels, "tof": epe_sum / n_flow (px), "tdiff_mse": tdiff_sse / (3 n_pixels)}, in 8-bit units squared; None wherever a
+    denominator is 0."""
+    n_valid, sse_a, sse_b, n_flow, epe, tdiff = (float(v) for v in row)
+    return {"warp_mse": sse_a / (3.0 * n_valid) if n_valid else None,
+            "warp_mse_real": sse_b / (3.0 * n_valid) if n_valid else None,
+            "valid": n_valid / n_pixels if n_pixels else None,
+            "tof": epe / n_flow if n_flow else None,
+            "tdiff_mse": tdiff / (3.0 * n_pixels) if n_pixels else None}
 
 
 def copy_channels(src, src_c0, dst, dst_c0, nc):

@@ -137,8 +137,15 @@ class TestOptions(BaseOptions):
           "<dataroot>/<phase>_img/<seq>/<same index> on the GPU (ops.image_metrics): PSNR, SSIM and MAE of the frame and of "
           "its face region, written to <results>/<seq>/metrics.json and under \"metrics\" in --timing_json")
 
+        g("--metrics_temporal", action="store_true", help="--metrics plus, for every frame after a sequence's first, the "
+          "temporal-consistency figures of the pair (t-1, t) against the real pair (ops.optical_flow_u8 + ops.temporal_metrics): "
+          "warping error under the real flow's forward-backward mask, tOF, and the flow-free flicker term, under "
+          "\"temporal\" in metrics.json and --timing_json")
+
     def parse(self, argv=None, save=False):
         opt = super().parse(argv, save)
+        if opt.metrics_temporal:
+            opt.metrics = True
         if opt.metrics and opt.shard_chunks:
             self.parser.error("--metrics with --shard_chunks: a sequence's frames are then spread over the ranks; "
                               "evaluate whole sequences (drop --shard_chunks)")
