@@ -708,6 +708,39 @@ int t2v_temporal_metrics_u8(t2v_ctx* ctx, void* stream, const uint8_t* a_cur, in
                             const int32_t* boxes /* HOST, [nbox][4] */, int nbox, double* scratch, double* out /* [1+nbox][6] */);
 
 /* ------------------------------------------------------------------------------------------
+ * Training visuals (additive to ABI 22): the pictures a training run shows of one frame (vid2vid/train.py --display_web,
+ * text2video_amd/train_display.py), up to T2V_VISUALS_MAX_PANELS panels rendered as uint8 RGB in two launches.
+ *   panel_ptrs: HOST memory, npanels device pointers to fp32 NHWC tensors [H][W][cs]; panel_ints: HOST memory,
+ *   [npanels][3] = kind, c0, cs: the panel reads channels from c0 on of a pixel of cs floats.  Both are read before the call
+ *   returns.  out: [npanels][H/scale][W/scale][3] uint8 device memory, 4-byte aligned.
+ *   T2V_VISUALS_IMAGE (channels c0..c0+2): the byte t2v_tensor2im_u8 writes, uint8((x+1)/2*255 clipped), fp32.
+ *   T2V_VISUALS_UNIT (channel c0): uint8(x*255 clipped to [0,255]) in fp32, NaN -> 0, the byte repeated as R, G and B.
+ *   T2V_VISUALS_FLOW (channels c0, c0+1 = u, v in pixels): HSV with saturation 1, hue = direction, value = magnitude
+ *   normalised over the panel, in float64 from the fp32 inputs.  A pixel is finite when u and v are; m = sqrt(u^2 + v^2);
+ *     lo, hi = min, max of m over the panel's finite pixels (every FLOW panel has its own);  V = (m - lo) / (hi - lo), and
+ *     V = 0 for a non-finite pixel, for a panel without a finite pixel and for hi == lo;
+ *     a = atan2(v, u), + 2 pi if negative;  h6 = 3 a / pi;  i = floor(h6) mod 6;  f = h6 - floor(h6);
+ *     (r, g, b) = (1,f,0), (1-f,1,0), (0,1,f), (0,1-f,1), (f,0,1), (1,0,1-f) for i = 0..5;  byte = floor(255 V c + 0.5).
+ *     (The colour wheel of upstream's util.tensor2flow as recalled; pinned to this definition, not to OpenCV's bytes.)
+ *   scale in {1, 2, 4}: every output byte = (sum of the scale x scale full-resolution bytes above + scale^2 / 2) / scale^2 in
+ *   integers; H and W must be multiples of scale.
+ *   scratch: scratch_doubles >= t2v_train_visuals_scratch_doubles(H, W, npanels) doubles of device memory, any content
+ *   (the per-slice min / max of the FLOW panels; 0 for a shape the call refuses).
+ * Launch 1 writes every FLOW panel's per-block min / max (skipped without a FLOW panel), launch 2 reduces them per block
+ * and renders: min and max do not depend on the order, so two calls give the same bytes.  No atomics, no allocation, no
+ * host synchronisation.  Refused with T2V_ERR_INVALID, nothing launched and `out` untouched: a null pointer, npanels
+ * outside 1..T2V_VISUALS_MAX_PANELS, H or W outside 1..T2V_METRICS_MAX_SIDE, scale outside {1, 2, 4} or not dividing H and
+ * W, an unknown kind, c0 < 0 or c0 + the kind's channels > cs, an `out` that is not 4-byte aligned, a scratch that is too
+ * small.
+ * ------------------------------------------------------------------------------------------ */
+#define T2V_VISUALS_MAX_PANELS 8
+enum { T2V_VISUALS_IMAGE = 0, T2V_VISUALS_UNIT = 1, T2V_VISUALS_FLOW = 2 };
+size_t t2v_train_visuals_scratch_doubles(int H, int W, int npanels);
+int t2v_train_visuals_u8(t2v_ctx* ctx, void* stream, const float* const* panel_ptrs /* HOST, [npanels] */,
+                         const int32_t* panel_ints /* HOST, [npanels][3] = kind, c0, cs */, int npanels, int H, int W, int scale,
+                         double* scratch, size_t scratch_doubles, uint8_t* out /* [npanels][H/scale][W/scale][3] */);
+
+/* ------------------------------------------------------------------------------------------
  * Host plumbing (ABI 14): device buffers, pinned host buffers, copies, streams and events for a host that has no HIP
  * binding of its own -- the reference's hosts got these from THC (THCudaMalloc / THCudaFree
  * $SP/torch/lib/include/THC/THCGeneral.h:143-144, THCudaHostAlloc :147, THCState_getCurrentStream :105,

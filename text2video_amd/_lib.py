@@ -191,6 +191,10 @@ SIGNATURES = {
     "t2v_temporal_metrics_scratch_doubles": (c_size_t, [c_int, c_int, c_int]),
     "t2v_temporal_metrics_u8": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int,
                                         c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p]),
+    # training visuals (additive to ABI 22): host arrays of panel pointers and [n][3] = kind, c0, cs
+    "t2v_train_visuals_scratch_doubles": (c_size_t, [c_int, c_int, c_int]),
+    "t2v_train_visuals_u8": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_size_t,
+                                     c_void_p]),
     # host plumbing (ABI 14): what text2video_amd/leantorch.py allocates, copies and synchronises with
     "t2v_device_malloc": (c_int, [c_void_p, c_size_t, POINTER(c_void_p)]),
     "t2v_device_free": (c_int, [c_void_p, c_void_p]),
@@ -207,6 +211,8 @@ SIGNATURES = {
     "t2v_device_synchronize": (c_int, [c_void_p]),
 }
 COPY_H2D, COPY_D2H, COPY_D2D = 1, 2, 3
+VISUALS_IMAGE, VISUALS_UNIT, VISUALS_FLOW = 0, 1, 2      # T2V_VISUALS_*: the panel kinds of t2v_train_visuals_u8
+VISUALS_MAX_PANELS = 8
 
 _lib = None
 _load_lock = __import__("threading").RLock()

@@ -1591,6 +1591,39 @@ int t2v_temporal_metrics_u8(t2v_ctx* ctx, void* stream, const uint8_t* a_cur, in
                                       flow_fwd, flow_bwd, flow_a, H, W, boxes, nbox, scratch, out);
 }
 
+// ---- training visuals: image / unit-map / flow panels of one frame as uint8 RGB (additive to ABI 22) ----
+static bool train_visuals_shape_ok(int H, int W, int npanels) {
+    return H >= 1 && W >= 1 && H <= T2V_METRICS_MAX_SIDE && W <= T2V_METRICS_MAX_SIDE && npanels >= 1 &&
+           npanels <= T2V_VISUALS_MAX_PANELS;
+}
+size_t t2v_train_visuals_scratch_doubles(int H, int W, int npanels) {
+    return train_visuals_shape_ok(H, W, npanels) ? train_visuals_scratch_doubles(H, W, npanels) : 0;
+}
+int t2v_train_visuals_u8(t2v_ctx* ctx, void* stream, const float* const* panel_ptrs, const int32_t* panel_ints, int npanels,
+                         int H, int W, int scale, double* scratch, size_t scratch_doubles, uint8_t* out) {
+    T2V_REQUIRE(ctx && panel_ptrs && panel_ints && scratch && out, "train_visuals_u8: null pointer");
+    T2V_REQUIRE(npanels >= 1 && npanels <= T2V_VISUALS_MAX_PANELS, "train_visuals_u8: npanels must be in 1..%d (got %d)",
+                T2V_VISUALS_MAX_PANELS, npanels);
+    T2V_REQUIRE(H >= 1 && W >= 1 && H <= T2V_METRICS_MAX_SIDE && W <= T2V_METRICS_MAX_SIDE,
+                "train_visuals_u8: H, W must be in 1..%d (got %d x %d)", T2V_METRICS_MAX_SIDE, H, W);
+    T2V_REQUIRE(scale == 1 || scale == 2 || scale == 4, "train_visuals_u8: scale must be 1, 2 or 4 (got %d)", scale);
+    T2V_REQUIRE(H % scale == 0 && W % scale == 0, "train_visuals_u8: scale %d does not divide %d x %d", scale, H, W);
+    for (int i = 0; i < npanels; ++i) {
+        const int kind = panel_ints[3 * i], c0 = panel_ints[3 * i + 1], cs = panel_ints[3 * i + 2];
+        T2V_REQUIRE(panel_ptrs[i], "train_visuals_u8: panel %d is a null pointer", i);
+        T2V_REQUIRE(kind == T2V_VISUALS_IMAGE || kind == T2V_VISUALS_UNIT || kind == T2V_VISUALS_FLOW,
+                    "train_visuals_u8: panel %d has the unknown kind %d", i, kind);
+        const int nc = kind == T2V_VISUALS_IMAGE ? 3 : (kind == T2V_VISUALS_FLOW ? 2 : 1);
+        T2V_REQUIRE(c0 >= 0 && cs >= 1 && c0 <= cs - nc, "train_visuals_u8: panel %d reads channels [%d, %d) of %d", i, c0,
+                    c0 + nc, cs);
+    }
+    T2V_REQUIRE((uintptr_t)out % 4 == 0, "train_visuals_u8: out must be 4-byte aligned");
+    T2V_REQUIRE(scratch_doubles >= train_visuals_scratch_doubles(H, W, npanels),
+                "train_visuals_u8: scratch holds %zu doubles, %d panels of %d x %d need %zu", scratch_doubles, npanels, H, W,
+                train_visuals_scratch_doubles(H, W, npanels));
+    return launch_train_visuals_u8((hipStream_t)stream, panel_ptrs, panel_ints, npanels, H, W, scale, scratch, out);
+}
+
 // ---- host plumbing (ABI 14): buffers, copies, streams, events for a host without a HIP binding of its own ----
 int t2v_device_malloc(t2v_ctx* ctx, size_t bytes, void** out) {
     T2V_REQUIRE(ctx && out, "device_malloc: null pointer");

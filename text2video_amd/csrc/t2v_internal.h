@@ -431,6 +431,10 @@ int launch_resample_crop_normalize_u8(hipStream_t s, const uint8_t* src, int T, 
                                       const int* y_coef, int ky, int crop_x, int crop_y, int crop_w, int crop_h, float* dst,
                                       int dst_cs, int dst_c0);
 
+// train_visuals.hip: arguments already validated (t2v_train_visuals_u8)
+size_t train_visuals_scratch_doubles(int H, int W, int npanels);
+int launch_train_visuals_u8(hipStream_t s, const float* const* ptrs, const int32_t* ints, int npanels, int H, int W, int scale,
+                            double* scratch, uint8_t* out);
 // image_metrics.hip: arguments already validated (t2v_image_metrics_u8)
 size_t image_metrics_scratch_doubles(int H, int W, int nbox);
 int launch_image_metrics_u8(hipStream_t s, const uint8_t* a, int a_cs, const uint8_t* b, int b_cs, int H, int W,

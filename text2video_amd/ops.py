@@ -12,7 +12,8 @@ from ._xp import torch     # the real torch, or leantorch under vid2vid/test.py'
 
 from . import _lib
 from ._lib import (ACT_FLOW_W, ACT_LRELU, ACT_NONE, ACT_TANH, ALGO_DIRECT, ALGO_WINOGRAD,  # noqa: F401
-                   ALGO_POLYPHASE, ALGO_POLYPHASE_BF16X2, ALGO_WINOGRAD_F4, ALGO_WINOGRAD_F4_BF16X2, PAD_REFLECT, PAD_ZERO, ConvDesc, check)
+                   ALGO_POLYPHASE, ALGO_POLYPHASE_BF16X2, ALGO_WINOGRAD_F4, ALGO_WINOGRAD_F4_BF16X2, PAD_REFLECT, PAD_ZERO, VISUALS_FLOW, VISUALS_IMAGE, VISUALS_MAX_PANELS,
+                   VISUALS_UNIT, ConvDesc, check)
 
 _contexts = {}
 
@@ -711,6 +712,61 @@ def temporal_summary(row, n_pixels):
             "valid": n_valid / n_pixels if n_pixels else None,
             "tof": epe / n_flow if n_flow else None,
             "tdiff_mse": tdiff / (3.0 * n_pixels) if n_pixels else None}
+
+
+_VISUALS_CHANNELS = {VISUALS_IMAGE: 3, VISUALS_UNIT: 1, VISUALS_FLOW: 2}
+
+
+def train_visuals_scratch_doubles(H, W, npanels):
+    """doubles of scratch t2v_train_visuals_u8 needs for npanels panels of H x W (0: a shape the call refuses)"""
+    return int(_lib.load().t2v_train_visuals_scratch_doubles(int(H), int(W), int(npanels)))
+
+
+def train_visuals(panels, scale=1, out=None, scratch=None):
+    """The pictures of one training frame (t2v_train_visuals_u8, include/t2v.h): panels = [(kind, tensor [H,W,cs], c0), ...],
+    at most 8, every tensor a contiguous fp32 device tensor of the same H x W (a [H,W] tensor counts as cs 1), read from
+    channel c0 on; kind = VISUALS_IMAGE (3 channels: tensor2im_u8's bytes), VISUALS_UNIT (1 channel in [0,1] as grey) or
+    VISUALS_FLOW (2 channels u, v in pixels: hue = direction, brightness = the panel's min-max-normalised magnitude).
+    -> a uint8 device tensor [n, H/scale, W/scale, 3]; scale in (1, 2, 4) averages scale x scale blocks of bytes.
+    out: that tensor to write instead; scratch: a float64 device tensor of at least train_visuals_scratch_doubles(H, W, n)
+    elements (default: one kept per device).  Two launches on the current stream, no host synchronisation; a refused call
+    (status T2V_ERR_INVALID) or a scratch / out that does not fit raises with nothing launched."""
+    c = context()
+    panels = [(int(kind), t, int(c0)) for kind, t, c0 in panels]
+    n = len(panels)
+    if n == 0:
+        raise ValueError("train_visuals: no panel")
+    for i, (kind, t, c0) in enumerate(panels):
+        if not (torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.dim() in (2, 3)):
+            raise ValueError("train_visuals: panel %d must be a contiguous fp32 device tensor [H,W,cs]" % i)
+        if kind not in _VISUALS_CHANNELS:
+            raise ValueError("train_visuals: panel %d has the unknown kind %d" % (i, kind))
+    H, W = panels[0][1].shape[0], panels[0][1].shape[1]
+    for i, (kind, t, c0) in enumerate(panels):
+        if tuple(t.shape[:2]) != (H, W):
+            raise ValueError("train_visuals: panel 0 is %dx%d, panel %d is %dx%d" % (H, W, i, t.shape[0], t.shape[1]))
+    scale = int(scale)
+    dev = panels[0][1].device
+    if out is None:
+        if scale not in (1, 2, 4) or H % scale or W % scale:
+            raise ValueError("train_visuals: scale must be 1, 2 or 4 and divide %dx%d (got %d)" % (H, W, scale))
+        out = torch.empty(n, H // scale, W // scale, 3, dtype=torch.uint8, device=dev)
+    if not (out.is_cuda and out.dtype == torch.uint8 and out.is_contiguous()
+                                and out.numel() >= n * (H // max(1, scale)) * (W // max(1, scale)) * 3):
+        raise ValueError("train_visuals: out must be a contiguous uint8 device tensor [%d,H/scale,W/scale,3]" % n)
+    need = train_visuals_scratch_doubles(H, W, n)
+    if scratch is None:
+        scratch = _metrics_scratch.get(str(dev))
+        if scratch is None or scratch.numel() < need:
+            scratch = _metrics_scratch[str(dev)] = torch.empty(max(need, 4096), dtype=torch.float64, device=dev)
+    elif not (scratch.is_cuda and scratch.dtype == torch.float64 and scratch.is_contiguous()):
+        raise ValueError("train_visuals: scratch must be a contiguous float64 device tensor")
+    ptrs = (ctypes.c_void_p * n)(*[t.data_ptr() for _, t, _ in panels])
+    ints = (ctypes.c_int32 * (3 * n))(*[v for kind, t, c0 in panels for v in (kind, c0, t.shape[2] if t.dim() == 3 else 1)])
+    # (too many panels, a bad scale, channels outside the stride, a scratch that is too small: the library refuses)
+    check(c.lib.t2v_train_visuals_u8(c.handle, _stream(), ptrs, ints, n, H, W, scale, _p(scratch), scratch.numel(), _p(out)),
+          "train_visuals_u8")
+    return out
 
 
 def copy_channels(src, src_c0, dst, dst_c0, nc):

@@ -164,6 +164,13 @@ class TrainOptions(BaseOptions):
         g = self.parser.add_argument
         g("--display_freq", type=int, default=100)
         g("--print_freq", type=int, default=100)
+        g("--display_web", action="store_true", help="rank 0 writes checkpoints/<name>/web/index.html with sample pictures of "
+          "the step that completes every --display_freq samples (pose, generated frame, raw frame, real frame and, with the "
+          "flow branch, predicted flow, weight map, reference flow and its confidence; rendered on the GPU by "
+          "ops.train_visuals) and appends every printed loss line to checkpoints/<name>/loss_log.txt; without it "
+          "--display_freq has no effect (upstream: on unless --no_html)")
+        g("--display_scale", type=int, default=1, choices=[1, 2, 4], help="--display_web: the pictures at 1/N of the frame's "
+          "size (N x N blocks of bytes averaged)")
         g("--save_latest_freq", type=int, default=1000)
         g("--save_epoch_freq", type=int, default=1)
         g("--continue_train", action="store_true")

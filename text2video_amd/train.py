@@ -1112,6 +1112,10 @@ class Vid2VidTrainer:
             self.load(opt.which_epoch, opt.load_pretrain)
         self.comm_bytes, self.comm_ms = 0, 0.0
         self.time_comm = os.environ.get("T2V_TRAIN_COMM_TIMING", "0") == "1"
+        # keep_visuals: a step leaves `visuals` = {name: tensor of the chunk's LAST frame} for TrainDisplay (train.py
+        # --display_web): pose [H,W,12], fake, raw, real [H,W,4] and, with the flow branch, fw [H,W,4] = (flow_x, flow_y,
+        # weight, 0), flow_ref [H,W,4], conf_ref [H,W].  References into the step's own tensors: no copy, no kernel.
+        self.keep_visuals, self.visuals = False, None
 
     def _d_input(self, A3, img4):
         z = torch.zeros(A3.shape[:-1] + (2,), dtype=torch.float32, device=A3.device)
@@ -1153,6 +1157,8 @@ class Vid2VidTrainer:
                 real_prev_warp = torch.stack([ops.flow_warp(flow_ref[i], real_prev[i], 0) for i in range(F_)])
             if conf_ref is None:
                 conf_ref = ((real[..., :3] - real_prev_warp[..., :3]).norm(dim=-1) < 0.02).float()
+            if self.keep_visuals:
+                self.visuals["flow_ref"], self.visuals["conf_ref"] = flow_ref[-1], conf_ref[-1]
             fake_prev = torch.cat(prevs, 0)
             fake_prev_warp = torch.stack([ops.flow_warp(flow_ref[i], fake_prev[i], self.spec.prev_nc - 3)
                                           for i in range(F_)])
@@ -1412,6 +1418,11 @@ class Vid2VidTrainer:
             prev = nprev
         fake = torch.cat(fakes, 0)
         A3 = pose[..., 6:9]
+        if self.keep_visuals:
+            self.visuals = {"pose": pose[-1], "fake": fakes[-1][0].detach(), "real": real[-1],
+                            "raw": (raws[-1] if raws[-1] is not None else fakes[-1])[0].detach()}
+            if fws[-1] is not None:
+                self.visuals["fw"] = fws[-1][0].detach()
         # compute_loss_D(netD, real_A, real_B, fake) [RECALL upstream Vid2VidModelD]: real pass, fake pass on the
         # detached frame (D's loss), fake pass for G's GAN + feature-matching loss.  The generator-side passes run
         # with D's parameters detached: only their data gradient is wanted.
@@ -1717,7 +1728,7 @@ class _ClipFeeder:
         self._it.close()
 
 
-def run_train(opt, steps=None):
+def run_train(opt, steps=None, watch=None):
     """train.py main: one process per GPU under torchrun (the reference used nn.DataParallel threads).
 
     Epoch structure of upstream train.py [RECALL]: `niter` epochs at the initial learning rate + `niter_decay` epochs
@@ -1725,7 +1736,12 @@ def run_train(opt, steps=None):
     iteration); `latest` checkpoints every `save_latest_freq` samples and at every `save_epoch_freq`-th epoch end (also
     under the epoch number), with `iter.txt` = (epoch, samples done in it) beside them; `--continue_train` reloads
     the `which_epoch` nets, reads iter.txt and resumes there (fresh Adam moments: upstream saves none).
-    `steps` caps the total number of iterations (tests, benches)."""
+    `steps` caps the total number of iterations (tests, benches); `watch`: a dict that receives the run's "trainer" and,
+    under --display_web on rank 0, its "display" (tests).
+
+    --display_web: rank 0 shows the last frame of the step that completes every `display_freq` samples (the rule of
+    `save_latest_freq`) through TrainDisplay -- rendered on the GPU behind the step, written by a thread -- and appends
+    every printed iteration line to loss_log.txt."""
     import os
     import time
     import numpy as np
@@ -1737,6 +1753,13 @@ def run_train(opt, steps=None):
     dev = "cuda:%d" % local_rank
     torch.cuda.set_device(local_rank)
     trainer = Vid2VidTrainer(opt, dev)
+    display = None
+    if rank == 0 and getattr(opt, "display_web", False):
+        from .train_display import TrainDisplay
+        display = TrainDisplay(opt)
+        trainer.keep_visuals = True
+    if watch is not None:
+        watch["trainer"], watch["display"] = trainer, display
     Dm.rendezvous("trainer built")      # (before the first gradient exchange: a rank that died building its replica is named)
     if rank == 0 and getattr(opt, "batchSize", world) not in (1, world):
         print("warning: --batchSize %d, but the batch is one clip per rank = %d (list %d devices in --gpu_ids)"
@@ -1864,15 +1887,20 @@ def run_train(opt, steps=None):
                     if steps is None or it + 1 < steps:
                         feeder.stage()      # the next clip's upload runs beside this clip's chunks
                 what = ", seq %s, %d frames %dx%d step %d" % (clip["seq"], T_ - tG + 1, H, W, clip["t_step"])
+            if display is not None and (total_samples + world) % max(1, opt.display_freq) < world:
+                display.show(trainer.visuals, epoch, total_samples + world)      # (enqueued behind the step; no host wait)
             torch.cuda.synchronize()
             stats.append(time.perf_counter() - ts)
             it += 1
             total_samples += world
             if rank == 0 and ((it - 1) % max(1, opt.print_freq // 100) == 0 or it == steps):
-                print("(iter %d, epoch %d%s, %.0f ms, all-reduce %.1f MB%s) %s"
-                      % (it - 1, epoch, what, 1e3 * stats[-1], trainer.comm_bytes / 2**20,
-                         ", %.1f ms exposed" % trainer.comm_ms if trainer.time_comm else "",
-                         " ".join("%s: %.3f" % kv for kv in losses.items())), flush=True)
+                line = "(iter %d, epoch %d%s, %.0f ms, all-reduce %.1f MB%s) %s" \
+                    % (it - 1, epoch, what, 1e3 * stats[-1], trainer.comm_bytes / 2**20,
+                       ", %.1f ms exposed" % trainer.comm_ms if trainer.time_comm else "",
+                       " ".join("%s: %.3f" % kv for kv in losses.items()))
+                print(line, flush=True)
+                if display is not None:
+                    display.log(line)
             last_pos = (epoch, (k + 1) * world)
             if total_samples % max(1, opt.save_latest_freq) < world:
                 checkpoint("latest", epoch, (k + 1) * world)
@@ -1902,6 +1930,8 @@ def run_train(opt, steps=None):
         if rank == 0:
             print("replicas in sync after %d steps (parameter checksum %.9g on all %d ranks)" % (it, float(allc[0]), world),
                   flush=True)
+    if display is not None:
+        display.close()      # (every picture, the page and the log are on disk before the final checkpoint)
     if rank == 0:      # the final (or step-capped) save carries its position too
         trainer.save("latest", last_pos)
     if world > 1:
