@@ -268,6 +268,17 @@ int t2v_batch_norm_update_running(t2v_ctx* ctx, void* stream, const float* mean_
 int t2v_batch_norm_finalize_running(t2v_ctx* ctx, void* stream, const t2v_conv_desc* producer, int batch,
                                     const float* stats_partial, float eps, float* mean_rstd, float* running_mean,
                                     float* running_var, float momentum, int times);
+/* The same finalize with a scratch buffer (additive to ABI 22): t2v_batch_norm_finalize, the running-statistics arguments of
+ * t2v_batch_norm_finalize_running (running_mean and running_var both NULL: no update, momentum and times ignored), and
+ * `scratch`, scratch_doubles doubles of device memory.  With a scratch buffer a launch that pools 2048 partials or more
+ * spreads them over several groups of blocks, which leave their sums in the buffer, and a second kernel merges the groups
+ * (and moves the running statistics); the tables are the same sums added in another order.  scratch == NULL: exactly the
+ * call without it.  A scratch buffer shorter than t2v_norm_finalize_scratch_doubles(producer) is refused (T2V_ERR_INVALID)
+ * before anything is launched.  batch = 1: an instance norm. */
+size_t t2v_norm_finalize_scratch_doubles(const t2v_conv_desc* producer);
+int t2v_batch_norm_finalize_scratch(t2v_ctx* ctx, void* stream, const t2v_conv_desc* producer, int batch,
+                                    const float* stats_partial, float eps, float* mean_rstd, float* running_mean,
+                                    float* running_var, float momentum, int times, double* scratch, size_t scratch_doubles);
 int t2v_instance_norm_apply(t2v_ctx* ctx, void* stream, const float* x, const float* mean_rstd,
                             const float* gamma, const float* beta, const float* res1,
                             const float* res2, float* y, long npix, int C, int relu);

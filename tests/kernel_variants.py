@@ -3,8 +3,8 @@
 A plain helper module (no fixtures, no pytest hooks), imported by tests/test_cpu_kernel_variants.py,
 tests/test_gpu_kernel_variants.py and tests/test_gpu_pipeline_variants.py.
 
-TABLE maps every `t2v::` kernel instantiation of libt2v_hip.so (the `__device_stub__` symbols, names normalised by
-normalise()) to one of
+TABLE maps every `t2v::` kernel instantiation of libt2v_hip.so (the `__device_stub__` symbols, those of
+`t2v::(anonymous namespace)::` included; names normalised by normalise()) to one of
   * Cases(...)       the ids of CONV_CASES or PIPE_CASES below -- tests/test_gpu_kernel_variants.py and
                      tests/test_gpu_pipeline_variants.py run each one, assert with the profiler that exactly this
                      instantiation of its family ran, and compare with float64 elementwise;
@@ -34,8 +34,10 @@ C_DIRECT = 2.1
 
 def normalise(name):
     """'void t2v::f<t2v::T<1, 2>, 3>(t2v::P)' -> 't2v::f<t2v::T<1,2>,3>': no 'void ', no argument list, no whitespace;
-    '__device_stub__' removed (nm's host-side stub names)."""
-    name = name.replace("__device_stub__", "").strip()
+    '__device_stub__' removed (nm's host-side stub names).  Every '(anonymous namespace)::' component goes first of all (its
+    '(' would otherwise be taken for the argument list): a kernel of `namespace t2v { namespace { ... } }` has the name
+    't2v::f' whether nm spells it ('t2v::(anonymous namespace)::__device_stub__f(...)') or the profiler does."""
+    name = name.replace("(anonymous namespace)::", "").replace("__device_stub__", "").strip()
     if name.startswith("void "):
         name = name[5:]
     depth = 0
@@ -814,7 +816,7 @@ TABLE = {
     "t2v::adam_kernel":
         Existing(("tests/test_gpu_train_pieces.py::test_fused_adam_matches_torch041_semantics",)),
     "t2v::adam_multi_kernel":
-        Uncovered('compared with adam_kernel bit for bit and inside train-step oracle tests only; no float64 case of its own'),
+        Existing(("tests/test_gpu_train_pieces.py::test_multi_tensor_adam_against_float64_on_both_paths",)),
     "t2v::add_kernel":
         Uncovered('no Python entry point; reached only inside generator frames compared end to end with the oracle'),
     "t2v::avgpool3s2_backward_kernel":
@@ -980,15 +982,16 @@ TABLE = {
     "t2v::inorm_bwd_reduce_kernel":
         Existing(("tests/test_gpu_backward.py::test_norm_backward_with_fused_activation",)),
     "t2v::inorm_finalize_kernel":
-        Existing(("tests/test_gpu_ops.py::test_instance_norm_affine_residual_matches_trainmode_batchnorm", "tests/test_gpu_ops.py::test_instance_norm_large_mean_is_stable",)),
+        Existing(("tests/test_gpu_ops.py::test_instance_norm_affine_residual_matches_trainmode_batchnorm", "tests/test_gpu_ops.py::test_instance_norm_large_mean_is_stable",
+                  "tests/test_gpu_norm_finalize_grouped.py::test_grouped_tables_against_float64_and_the_single_kernel_form",)),
     "t2v::inorm_finalize_merge_kernel":
-        Uncovered('reached only by full-size frames compared end to end with the oracle'),
+        Existing(("tests/test_gpu_norm_finalize_grouped.py::test_grouped_tables_against_float64_and_the_single_kernel_form",)),
     "t2v::loss_backward_kernel":
         Existing(("tests/test_gpu_backward.py::test_pointwise_and_pooling_backward",)),
     "t2v::loss_terms_final_kernel":
-        Uncovered('reached only inside train steps compared end to end with the device oracle'),
+        Existing(("tests/test_gpu_loss_terms.py::test_values_against_float64_and_seeds_bit_for_bit_in_one_run",)),
     "t2v::loss_terms_kernel":
-        Uncovered('reached only inside train steps compared end to end with the device oracle'),
+        Existing(("tests/test_gpu_loss_terms.py::test_values_against_float64_and_seeds_bit_for_bit_in_one_run",)),
     "t2v::masked_l1_backward_kernel":
         Existing(("tests/test_gpu_backward.py::test_masked_l1_and_flow_head_activation_backward",)),
     "t2v::maxpool2x2_backward_kernel":
@@ -1104,3 +1107,88 @@ TABLE = {
     "t2v::winograd_weight_kernel":
         Cases(("w2_fwd",)),
 }
+
+# ---- kernels of `namespace t2v { namespace { ... } }` (optical_flow, image_metrics, temporal_metrics, train_visuals,
+# image_resample, winograd_split, polyphase_split .hip): nm spells them 't2v::(anonymous namespace)::...', normalise() drops
+# that component.  Which parametrisation reaches which template instantiation is read off the dispatch code named in each
+# comment and was confirmed with the profiler on an MI355X (profiles/ledger_float64.txt).
+_OF = "tests/test_gpu_optical_flow.py::"
+_S4 = "tests/test_gpu_split_bf16.py::"
+_S5 = "tests/test_gpu_split_polyphase.py::"
+_IN_PLANES = "test_input_transform_planes_are_the_split_of_the_fp32_transform"
+_W_PLANES = "test_packed_weight_planes_are_the_split_of_the_fp32_packing"
+_GEMM_EMU = "test_gemm_stage_against_the_emulation_of_its_own_planes"
+_WHOLE = "test_whole_conv_against_float64"
+TABLE.update({
+    # launch_flow (optical_flow.hip): <0> is the coarsest level's first iteration (every call); <1> every iteration k > 0
+    # (iters >= 2: cases A, B with the default 3, C with 2); <2> the first iteration of every finer level (levels >= 2: A, B, C
+    # take the default rule's 3 levels).  Float64 restatement at every pixel.
+    "t2v::flow_lk_kernel<0>":
+        Existing((_OF + "test_kernel_matches_the_float64_restatement_at_every_pixel",
+                  _OF + "test_kernel_matches_the_float64_restatement_at_the_edges_of_its_geometry",)),
+    "t2v::flow_lk_kernel<1>":
+        Existing((_OF + "test_kernel_matches_the_float64_restatement_at_every_pixel",)),
+    "t2v::flow_lk_kernel<2>":
+        Existing((_OF + "test_kernel_matches_the_float64_restatement_at_every_pixel",)),
+    "t2v::flow_grey_kernel":
+        Existing((_OF + "test_kernel_matches_the_float64_restatement_at_every_pixel",)),
+    "t2v::flow_pool_kernel":
+        Existing((_OF + "test_kernel_matches_the_float64_restatement_at_every_pixel",)),
+    "t2v::flow_out_kernel":
+        Existing((_OF + "test_kernel_matches_the_float64_restatement_at_every_pixel",)),
+    # an exact identity: the flow of the bytes == the flow of the frames u8_pose_to_f32_kernel converts (both pinned)
+    "t2v::flow_grey_u8_kernel":
+        Existing(("tests/test_gpu_temporal_metrics.py::test_optical_flow_u8_is_bit_equal_to_optical_flow_on_the_converted_frames",)),
+    "t2v::image_metrics_u8_kernel":
+        Existing(("tests/test_gpu_image_metrics.py::test_whole_frame_against_reference",
+                  "tests/test_gpu_image_metrics.py::test_boxes_equal_the_cropped_pair",)),
+    "t2v::image_metrics_finalize_kernel":
+        Existing(("tests/test_gpu_image_metrics.py::test_whole_frame_against_reference",)),
+    "t2v::temporal_metrics_u8_kernel":
+        Existing(("tests/test_gpu_temporal_metrics.py::test_whole_frame_against_reference",
+                  "tests/test_gpu_temporal_metrics.py::test_boxes_equal_the_reference_on_the_box",)),
+    "t2v::temporal_metrics_finalize_kernel":
+        Existing(("tests/test_gpu_temporal_metrics.py::test_whole_frame_against_reference",)),
+    "t2v::train_visuals_minmax_kernel":
+        Existing(("tests/test_gpu_train_display.py::test_eight_panels_against_the_reference",)),
+    "t2v::train_visuals_render_kernel":
+        Existing(("tests/test_gpu_train_display.py::test_eight_panels_against_the_reference",)),
+    "t2v::resample_crop_normalize_u8_kernel":
+        Existing(("tests/test_gpu_image_resample.py::test_kernel_equals_pillow_crop_normalize_bitwise",)),
+    # the 36- and 81-position split GEMM: the float64 emulation of its own bf16 planes
+    "t2v::wino_split_gemm_kernel":
+        Existing((_S4 + _GEMM_EMU, _S5 + _GEMM_EMU,)),
+    # launch_winograd4_input_split (winograd_split.hip): MODE 0 = no lazy norm ("plain"), 1 = mean_rstd without a residual
+    # ("relu", "relu_affine"), 2 = with res / xout ("res"); XCD = xcd_slice_grid() != 0, i.e. C / 2 % 512 == 0: the
+    # 1024-channel maps, every other map takes <MODE, false>.  The planes must be split() -- tests/split_reference.py's own
+    # restatement -- of what the float64-pinned fp32 kernel stores, bit for bit; the whole conv is then held to float64.
+    "t2v::winograd4_input_split_kernel<0,false>":
+        Existing((_S4 + _IN_PLANES, _S4 + _WHOLE,)),
+    "t2v::winograd4_input_split_kernel<0,true>":
+        Existing((_S4 + _IN_PLANES,)),
+    "t2v::winograd4_input_split_kernel<1,false>":
+        Existing((_S4 + _IN_PLANES,)),
+    "t2v::winograd4_input_split_kernel<1,true>":
+        Existing((_S4 + _IN_PLANES,)),
+    "t2v::winograd4_input_split_kernel<2,false>":
+        Existing((_S4 + _IN_PLANES,)),
+    "t2v::winograd4_input_split_kernel<2,true>":
+        Existing((_S4 + _IN_PLANES,)),
+    "t2v::winograd4_weight_split_kernel":
+        Existing((_S4 + _W_PLANES, _S4 + _WHOLE,)),
+    # launch_polyphase_input_split (polyphase_split.hip): UP = the desc is transposed (INPUT_MAPS' up column), NORM =
+    # mean_rstd given ("relu", "relu_affine"; "plain" takes <UP, false>)
+    "t2v::polyphase_input_split_kernel<false,false>":
+        Existing((_S5 + _IN_PLANES, _S5 + _WHOLE,)),
+    "t2v::polyphase_input_split_kernel<false,true>":
+        Existing((_S5 + _IN_PLANES,)),
+    "t2v::polyphase_input_split_kernel<true,false>":
+        Existing((_S5 + _IN_PLANES, _S5 + _WHOLE,)),
+    "t2v::polyphase_input_split_kernel<true,true>":
+        Existing((_S5 + _IN_PLANES,)),
+    # launch_polyphase_weight_split: <false> the "conv2d" id, <true> the "convtranspose2d" id
+    "t2v::polyphase_weight_split_kernel<false>":
+        Existing((_S5 + _W_PLANES, _S5 + _WHOLE,)),
+    "t2v::polyphase_weight_split_kernel<true>":
+        Existing((_S5 + _W_PLANES, _S5 + _WHOLE,)),
+})

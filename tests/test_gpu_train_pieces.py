@@ -341,6 +341,148 @@ def test_multi_tensor_adam_equals_the_per_tensor_kernel(t2v_env):
     assert not torch.equal(outs["1"][0][0], init[0])
 
 
+def _adam_error_bound(e, p, g, m, v, m1, v1, lr, b1, b2, eps, step):
+    """Running first-order bound on |fp32 kernel - float64 oracle| per element, advanced through one step.  e = (e_p, e_m, e_v)
+    before the step; p, m, v the oracle's float64 values before it, m1, v1 after.  The kernel's roundings (fp32, no fused
+    multiply-add), u = 2^-24 each:
+      m' = fl(fl(m b1) + fl(omb1 g)):       b1 and 1 - b1 converted from double (2), two products, one add
+      v' = fl(fl(v b2) + fl(fl(omb2 g) g)): b2 and 1 - b2 converted (2), three products, one add
+      den = fl(fl(sqrt(v')) + eps):         the square root, the add, eps converted
+      q = fl(m' / den), p' = fl(p - fl(ss q)): the division, ss converted, the product, the subtraction
+    sqrtf and the division are correctly rounded (hipcc's default); incoming errors propagate with the update's own
+    derivatives.  5 % on top for the second-order terms."""
+    u = 2.0 ** -24
+    e_p, e_m, e_v = e
+    e_m = b1 * e_m + u * (2 * b1 * m.abs() + 2 * (1 - b1) * g.abs() + m1.abs())
+    e_v = b2 * e_v + u * (2 * b2 * v + 3 * (1 - b2) * g * g + v1)
+    root = v1.sqrt()
+    den = root + eps
+    e_den = torch.where(root > 0, e_v / (2 * root).clamp_min(1e-300), torch.zeros_like(root)) + u * (root + den + eps)
+    q = m1 / den
+    e_q = e_m / den + q.abs() * e_den / den + u * q.abs()
+    ss = lr * (1 - b2 ** step) ** 0.5 / (1 - b1 ** step)
+    p1 = p - ss * q
+    e_p = e_p + ss * e_q + 2 * u * ss * q.abs() + u * p1.abs()
+    return e_p, e_m, e_v
+
+
+def test_multi_tensor_adam_against_float64_on_both_paths(t2v_env):
+    """adam_multi_kernel through FusedAdam (T2V_ADAM_MULTI at its default) against the float64 restatement of torch 0.4.1's
+    step, per element: tensors of 1 .. 2 CHUNK + 6 elements, two of them views base[1:1 + n] of NaN-margined buffers (their
+    address is 4 mod 16: the kernel's scalar path), one parameter without a gradient in steps 1 and 3, gradients from 1e-6
+    to 30 with exact zeros.  Then the same inputs through the per-tensor kernel: identical bits."""
+    import kernel_variants as kv
+    from text2video_amd import ops
+    from text2video_amd import train as T
+    assert os.environ.get("T2V_ADAM_MULTI", "1") != "0"
+    CH = T.FusedAdam.CHUNK
+    sizes = [1, 3, 5, 64, CH - 1, CH + 1, 2 * CH + 6]
+    views, idle, MARGIN = {1, 5}, 3, 64           # sizes[1] = 3 (short) and sizes[5] = CHUNK + 1 (longer than a chunk)
+    lr_, b1, b2, eps, steps = 2e-4, 0.5, 0.999, 1e-8, 4
+    rng = np.random.default_rng(41)
+    init = [torch.from_numpy((rng.standard_normal(n) * 0.1).astype(np.float32)) for n in sizes]
+
+    def grad(n):
+        g = np.exp(rng.uniform(np.log(1e-6), np.log(30.0), n)) * rng.choice([-1.0, 1.0], n)
+        g[rng.random(n) < 0.05] = 0.0
+        g[-1] = 30.0                                # the last element and the first behind a chunk edge carry the largest
+        if n > CH:
+            g[CH] = -30.0
+        return torch.from_numpy(g.astype(np.float32))
+    grads = [[None if (i == idle and s in (0, 2)) else grad(n) for i, n in enumerate(sizes)] for s in range(steps)]
+    assert any(float(g.abs().max()) == 30.0 and (g == 0).any() and float(g[g != 0].abs().min()) < 1e-5 for g in grads[0] if g is not None)
+
+    # the float64 oracle and the running error bound; every parameter keeps its own step count
+    ref = [(t.double().clone(), torch.zeros(n, dtype=torch.float64), torch.zeros(n, dtype=torch.float64)) for t, n in zip(init, sizes)]
+    err = [tuple(torch.zeros(n, dtype=torch.float64) for _ in range(3)) for n in sizes]
+    count = [0] * len(sizes)
+    for s in range(steps):
+        for i, (p, m, v) in enumerate(ref):
+            if grads[s][i] is None:
+                continue
+            count[i] += 1
+            g = grads[s][i].double()
+            p0, m0, v0 = p.clone(), m.clone(), v.clone()
+            _adam_041(p, g, m, v, lr_, b1, b2, eps, count[i])
+            err[i] = _adam_error_bound(err[i], p0, g, m0, v0, m, v, lr_, b1, b2, eps, count[i])
+    assert count == [4, 4, 4, 2, 4, 4, 4]
+
+    def run(profile):
+        bases, ps = [], []
+        for i, t in enumerate(init):
+            if i in views:
+                base = torch.full((1 + t.numel() + MARGIN,), float("nan"), device="cuda:0")
+                view = base[1:1 + t.numel()]
+                view.copy_(t)
+                assert view.data_ptr() % 16 == 4
+                bases.append(base)
+                ps.append(torch.nn.Parameter(view))
+                assert ps[-1].data_ptr() == view.data_ptr()
+            else:
+                bases.append(None)
+                ps.append(torch.nn.Parameter(t.clone().cuda()))
+        opt = T.FusedAdam(ps, lr=lr_, betas=(b1, b2), eps=eps)
+        held = []                                   # every gradient stays referenced until after the synchronize
+        ran = set()
+        snap = None
+        for s in range(steps):
+            for i, p in enumerate(ps):
+                p.grad = None if grads[s][i] is None else grads[s][i].cuda()
+                held.append(p.grad)
+            if s == 2:                              # step 3: the idle parameter must keep p, m, v bit for bit
+                torch.cuda.synchronize()
+                snap = [x.clone() for x in (ps[idle].detach(), opt.m[idle], opt.v[idle])]
+            if profile and s == 0:
+                torch.cuda.synchronize()
+                with torch.profiler.profile(activities=[torch.profiler.ProfilerActivity.CUDA]) as prof:
+                    opt.step()
+                    torch.cuda.synchronize()
+                ran = {kv.normalise(e.name) for e in prof.events() if "t2v::" in e.name}
+            else:
+                opt.step()
+            if s == 0:                              # step 1: it has not moved at all
+                torch.cuda.synchronize()
+                assert torch.equal(ps[idle].detach().cpu(), init[idle]) and not opt.m[idle].any() and not opt.v[idle].any()
+            if s == 2:
+                torch.cuda.synchronize()
+                for x, y in zip(snap, (ps[idle].detach(), opt.m[idle], opt.v[idle])):
+                    assert torch.equal(x.view(torch.int32), y.view(torch.int32))
+        torch.cuda.synchronize()
+        ops.check_async_errors()
+        for i, base in enumerate(bases):
+            if base is not None:                    # the margins of the view bases keep their NaN bits
+                b = base.cpu().view(torch.int32)
+                n = sizes[i]
+                assert (b[:1] == 0x7FC00000).all() and (b[1 + n:] == 0x7FC00000).all(), "size %d: a margin was written" % n
+        out = ([p.detach().cpu() for p in ps], [m.cpu() for m in opt.m], [v.cpu() for v in opt.v], list(opt.steps))
+        del held
+        return out, ran
+
+    multi, ran = run(True)
+    assert "t2v::adam_multi_kernel" in ran and "t2v::adam_kernel" not in ran, ran
+    assert multi[3] == count
+    for i, n in enumerate(sizes):
+        for what, got, want, bound in zip("pmv", (multi[0][i], multi[1][i], multi[2][i]), ref[i], err[i]):
+            assert torch.isfinite(got).all(), (n, what)
+            bound = bound * 1.05
+            d = (got.double() - want).abs()
+            ratio = torch.where(d > 0, d / bound.clamp_min(1e-300), torch.zeros_like(d))
+            at = int(ratio.argmax())
+            print("adam_multi n=%-7d%s %s: worst |got - f64| / bound %.3g at %d" % (
+                n, " (view)" if i in views else "", what, ratio[at].item(), at))
+            assert ratio[at].item() <= 1.0, (n, what, at, got[at].item(), want[at].item(), bound[at].item())
+            # no looser than test_fused_adam_matches_torch041_semantics: 6e-7 on p (|p| < 8), 1e-6 of the largest moment
+            assert d.max().item() <= (6e-7 if what == "p" else 1e-6 * want.abs().max().item()), (n, what, d.max().item())
+    # the per-tensor kernel on the same inputs: identical bits
+    t2v_env("T2V_ADAM_MULTI", "0")
+    single, ran0 = run(True)
+    assert "t2v::adam_kernel" in ran0 and "t2v::adam_multi_kernel" not in ran0, ran0
+    assert single[3] == count
+    for k in range(3):
+        for a, b in zip(multi[k], single[k]):
+            assert torch.equal(a.view(torch.int32), b.view(torch.int32))
+
+
 def test_batchnorm_running_statistics_follow_torch_and_reach_the_checkpoint(tmp_path):
     """Training-mode BatchNorm2d also moves running_mean / running_var (momentum 0.1, UNBIASED variance;
     /root/reference/venv_vid2vid/lib/python3.7/site-packages/torch/nn/modules/batchnorm.py:57-64).  The discriminator

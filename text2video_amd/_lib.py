@@ -97,6 +97,10 @@ SIGNATURES = {
     "t2v_batch_norm_finalize": (c_int, [c_void_p, c_void_p, POINTER(ConvDesc), c_int, c_void_p, c_float, c_void_p]),
     "t2v_batch_norm_finalize_running": (c_int, [c_void_p, c_void_p, POINTER(ConvDesc), c_int, c_void_p, c_float, c_void_p,
                                                 c_void_p, c_void_p, c_float, c_int]),
+    # the finalize with a scratch buffer (additive to ABI 22): running statistics nullable, scratch double* + its length
+    "t2v_norm_finalize_scratch_doubles": (c_size_t, [POINTER(ConvDesc)]),
+    "t2v_batch_norm_finalize_scratch": (c_int, [c_void_p, c_void_p, POINTER(ConvDesc), c_int, c_void_p, c_float, c_void_p,
+                                                c_void_p, c_void_p, c_float, c_int, c_void_p, c_size_t]),
     "t2v_conv_backward_weight_workspace_floats": (c_size_t, [POINTER(ConvDesc), c_int, c_int]),
     "t2v_conv_backward_weight_winograd_supported": (c_int, [POINTER(ConvDesc), c_int, c_int]),
     "t2v_conv_backward_weight_winograd_workspace_floats": (c_size_t, [POINTER(ConvDesc), c_int, c_int]),

@@ -908,6 +908,29 @@ int t2v_batch_norm_finalize_running(t2v_ctx* ctx, void* stream, const t2v_conv_d
     const RunningUpdate ru{running_mean, running_var, (float)n, momentum, times};
     return finalize_norm((hipStream_t)stream, producer, round_up(producer->Cin, 4), stats_partial, batch, eps, mean_rstd, nullptr, &ru);
 }
+// the same with a scratch buffer, which lets a launch of >= 2048 partials pool them in groups (additive to ABI 22)
+size_t t2v_norm_finalize_scratch_doubles(const t2v_conv_desc* producer) {
+    return producer ? (size_t)kFinalizeMaxGroups * producer->Cout * 4 : 0;
+}
+int t2v_batch_norm_finalize_scratch(t2v_ctx* ctx, void* stream, const t2v_conv_desc* producer, int batch,
+                                    const float* stats_partial, float eps, float* mean_rstd, float* running_mean,
+                                    float* running_var, float momentum, int times, double* scratch, size_t scratch_doubles) {
+    T2V_REQUIRE(ctx && producer && stats_partial && mean_rstd && batch >= 1, "batch_norm_finalize_scratch: bad arguments");
+    T2V_REQUIRE((running_mean == nullptr) == (running_var == nullptr),
+                "batch_norm_finalize_scratch: running_mean and running_var go together");
+    T2V_REQUIRE(scratch == nullptr || scratch_doubles >= t2v_norm_finalize_scratch_doubles(producer),
+                "batch_norm_finalize_scratch: scratch of %zu doubles, %zu needed", scratch_doubles,
+                t2v_norm_finalize_scratch_doubles(producer));
+    const int x_cs = round_up(producer->Cin, 4);
+    if (!running_mean) return finalize_norm((hipStream_t)stream, producer, x_cs, stats_partial, batch, eps, mean_rstd, scratch);
+    T2V_REQUIRE(times >= 1, "batch_norm_finalize_scratch: times %d", times);
+    int ho = 0, wo = 0;
+    T2V_TRY(t2v_conv_out_dims(producer, &ho, &wo));
+    const long n = (long)batch * ho * wo;
+    T2V_REQUIRE(n >= 2, "batch_norm_finalize_scratch: the unbiased variance needs at least two values per channel");
+    const RunningUpdate ru{running_mean, running_var, (float)n, momentum, times};
+    return finalize_norm((hipStream_t)stream, producer, x_cs, stats_partial, batch, eps, mean_rstd, scratch, &ru);
+}
 
 // narrow-input regular convs (7x7 stems: 12 / 8 channels; the discriminators' 4x4 first layers: 8): fold the taps
 // into the 128-wide channel side of the block tile

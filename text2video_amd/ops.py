@@ -302,11 +302,30 @@ def conv2d_auto_batch(x, packed_w, bias, desc, y_cs=None, stats=None, out=None):
     return out
 
 
-def instance_norm_finalize(stats, desc, eps=1e-5, out=None, running=None):
+def norm_finalize_scratch(desc, device):
+    """the scratch buffer instance_norm_finalize / batch_norm_finalize take as scratch= (t2v_norm_finalize_scratch_doubles)"""
+    return torch.empty(_lib.load().t2v_norm_finalize_scratch_doubles(ctypes.byref(desc)), dtype=torch.float64, device=device)
+
+
+def _finalize_scratch(c, desc, batch, stats, eps, mr, running, scratch):
+    """t2v_batch_norm_finalize_scratch: a launch of >= 2048 partials pools them in groups through `scratch` (float64)"""
+    if not (scratch.is_cuda and scratch.dtype == torch.float64 and scratch.is_contiguous()):
+        raise ValueError("scratch must be a contiguous float64 device tensor")
+    rm, rv, momentum, times = running if running is not None else (None, None, 0.0, 0)
+    check(c.lib.t2v_batch_norm_finalize_scratch(c.handle, _stream(), ctypes.byref(desc), int(batch), _p(stats), eps, _p(mr), _p(rm),
+                                                _p(rv), momentum, int(times), _p(scratch), scratch.numel()),
+          "batch_norm_finalize_scratch")
+    return mr
+
+
+def instance_norm_finalize(stats, desc, eps=1e-5, out=None, running=None, scratch=None):
     """running = (running_mean, running_var, momentum, times): BatchNorm2d(train)'s running statistics (a batch of one) are
-    moved `times` times by these statistics in the same launch (t2v_batch_norm_finalize_running)."""
+    moved `times` times by these statistics in the same launch (t2v_batch_norm_finalize_running).  scratch: a float64 device
+    tensor of norm_finalize_scratch()'s size, see t2v_batch_norm_finalize_scratch."""
     c = context()
     mr = out if out is not None else torch.empty(desc.Cout, 2, dtype=torch.float32, device=stats.device)
+    if scratch is not None:
+        return _finalize_scratch(c, desc, 1, stats, eps, mr, running, scratch)
     if running is not None:
         rm, rv, momentum, times = running
         check(c.lib.t2v_batch_norm_finalize_running(c.handle, _stream(), ctypes.byref(desc), 1, _p(stats), eps, _p(mr), _p(rm), _p(rv),
@@ -780,11 +799,13 @@ def copy_channels(src, src_c0, dst, dst_c0, nc):
 # ------------------------------------------------------------------------------------------------
 # train-step pieces
 # ------------------------------------------------------------------------------------------------
-def batch_norm_finalize(stats, desc, batch, eps=1e-5, running=None):
+def batch_norm_finalize(stats, desc, batch, eps=1e-5, running=None, scratch=None):
     """BatchNorm2d(train) statistics over a batch: `stats` holds `batch` consecutive per-image
-    partial blocks written by conv2d(..., stats=stats[b * n : (b + 1) * n]).  running: as instance_norm_finalize."""
+    partial blocks written by conv2d(..., stats=stats[b * n : (b + 1) * n]).  running, scratch: as instance_norm_finalize."""
     c = context()
     mr = torch.empty(desc.Cout, 2, dtype=torch.float32, device=stats.device)
+    if scratch is not None:
+        return _finalize_scratch(c, desc, batch, stats, eps, mr, running, scratch)
     if running is not None:
         rm, rv, momentum, times = running
         check(c.lib.t2v_batch_norm_finalize_running(c.handle, _stream(), ctypes.byref(desc), batch, _p(stats), eps, _p(mr), _p(rm),
