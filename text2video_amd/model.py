@@ -120,6 +120,17 @@ def _real_A_u8(pose_map_u8):
     return np.clip((x + 1) / 2.0 * 255.0, 0, 255).astype(np.uint8)
 
 
+_REAL_A_LUT = _real_A_u8(np.arange(256, dtype=np.uint8)).tobytes()      # the same round trip as a byte-to-byte map
+
+
+class _JpegStep:
+    """--gpu_jpeg: the frames of one step and geometry whose JPEG scans one encode call produced (run_test's frame loop)"""
+    __slots__ = ("encoder", "step", "paths")
+
+    def __init__(self, encoder, step, paths):
+        self.encoder, self.step, self.paths = encoder, step, paths
+
+
 def run_test(opt, model=None, device=None, dataset=None):
     """The frame loop.  Returns a dict of counters/timings.  `dataset`: a ready PoseDataset (e.g.
     PoseDataset.from_memory for the in-memory L2 driver) instead of the one scanned from opt.dataroot.
@@ -206,11 +217,15 @@ def run_test(opt, model=None, device=None, dataset=None):
             yield primed["step"]
         for st in first_steps:
             yield st
-    vis = Visualizer(opt)
+    # --gpu_jpeg: the JPEG files are encoded on the GPU (ops.jpeg_encode_u8), the writer threads only write them
+    want_jpeg = bool(getattr(opt, "gpu_jpeg", False))
+    jpeg_quality = int(getattr(opt, "jpeg_quality", None) or 75)
+    jpeg_state, jpeg_refused = {}, set()      # (H, W, frames per step) -> StepEncoder; geometries the encoder does not take
+    vis = Visualizer(opt, quality=jpeg_quality if want_jpeg else None)
     dev = torch.device(device)
     cs = ops.round_up(3 * opt.n_frames_G, 4)
     pinned = {}      # shape -> ring of 3 pinned host buffers (allocating pinned memory per frame costs ~0.2 ms)
-    counters = {"n": 0, "t_loop0": 0.0}
+    counters = {"n": 0, "t_loop0": 0.0, "d2h_bytes": 0}
     # where the host spends the loop: waiting for the next step's pose maps (rasteriser), uploading them, enqueueing the
     # generator / tensor2im / D2H, and waiting for the previous step's frames (the GPU) + handing them to the JPEG threads
     split = marks.setdefault("loop_split", {"wait_pose_s": 0.0, "upload_s": 0.0, "enqueue_s": 0.0, "finish_s": 0.0})
@@ -240,7 +255,16 @@ def run_test(opt, model=None, device=None, dataset=None):
         lanes = {}
         pending = []   # (event, pinned uint8 frame, path, real_A) of the previous step: D2H overlaps the next step
 
+        def finish_jpeg(p):
+            """header + scan + EOI of every frame of the step to the writer threads, which only write them"""
+            files = p.encoder.files(p.step)      # (waits for the step's event)
+            ops.check_async_errors()
+            for m, a_path in enumerate(p.paths):
+                vis.save_bytes({"real_A": files[2 * m + 1], "fake_B": files[2 * m]}, a_path)
+
         def finish(p):
+            if isinstance(p, _JpegStep):
+                return finish_jpeg(p)
             ev, host, a_path, real_a = p
             ev.synchronize()
             ops.check_async_errors()      # e.g. a fixed-grid hand-over that timed out while this frame was computed
@@ -279,6 +303,27 @@ def run_test(opt, model=None, device=None, dataset=None):
                 L.real_dev = torch.empty(real.shape, dtype=torch.uint8, device=dev)
             L.real_dev.copy_(stage, non_blocking=True)
             L.metrics.compare(u8, L.real_dev, os.path.basename(data["A_path"]), M.face_box(data["A"][-1]))
+
+        def encode_group(H, W, members, outs, now, compare):
+            """--gpu_jpeg: fake_B (tensor2im_u8) and real_A (the pose map on the device, through the byte map of its
+            round trip) of every member into one batch, ONE encode call, then the lengths and a first window of every scan
+            to a pinned buffer (jpeg_frames.StepEncoder); no host synchronisation -- finish_jpeg waits for the step's event"""
+            enc = jpeg_state.get((H, W, len(members)))
+            if enc is None:
+                from .jpeg_frames import StepEncoder
+                enc = jpeg_state[(H, W, len(members))] = StepEncoder(H, W, 2 * len(members), jpeg_quality, dev)
+            t1 = time.perf_counter()
+            for m, ((k, L, data), out) in enumerate(zip(members, outs)):
+                u8 = ops.tensor2im_u8(out, out=enc.image(2 * m))
+                ops.jpeg_stage_u8(L.dev_maps[-1], enc.image(2 * m + 1), _REAL_A_LUT)
+                if want_metrics:      # (--metrics_temporal keeps a frame for the next pair: the batch slot is rewritten by then)
+                    compare.append((k, L, data, u8.clone() if want_temporal else u8))
+            split["tensor2im_s"] = split.get("tensor2im_s", 0.0) + time.perf_counter() - t1
+            step = enc.encode()      # (its host time: jpeg_s and d2h_s, added up after the loop)
+            now.append(_JpegStep(enc, step, [data["A_path"] for _, _, data in members]))
+            for _, _, data in members:
+                print("process image... %s" % data["A_path"])
+                counters["n"] += 1
 
         steps = iter(steps)
         while True:
@@ -327,6 +372,17 @@ def run_test(opt, model=None, device=None, dataset=None):
                     outs = model.inference_nhwc_batch([L.window for _, L, _ in members], [L.rec for _, L, _ in members])
                 split["generator_s"] = split.get("generator_s", 0.0) + time.perf_counter() - tg
                 compare = []      # --metrics: after EVERY member's D2H event, so that no frame's JPEG waits for a comparison
+                if want_jpeg and (gh, gw) not in jpeg_refused:
+                    if ops.jpeg_supported(gh, gw):
+                        encode_group(gh, gw, members, outs, now, compare)
+                        for k, L, data, u8 in compare:
+                            t3 = time.perf_counter()
+                            compare_with_real(k, L, data, u8)
+                            split["metrics_s"] = split.get("metrics_s", 0.0) + time.perf_counter() - t3
+                        continue
+                    jpeg_refused.add((gh, gw))
+                    print("warning: --gpu_jpeg: the encoder does not take %dx%d frames; these are written by Pillow"
+                          % (gh, gw), file=sys.stderr)
                 for (k, L, data), out in zip(members, outs):
                     t1 = time.perf_counter()
                     u8 = ops.tensor2im_u8(out)
@@ -345,6 +401,7 @@ def run_test(opt, model=None, device=None, dataset=None):
                         compare.append((k, L, data, u8))
                     split["tensor2im_s"] = split.get("tensor2im_s", 0.0) + t2 - t1
                     split["d2h_s"] = split.get("d2h_s", 0.0) + t3 - t2
+                    counters["d2h_bytes"] += u8.numel()
                     now.append((ev, host, data["A_path"], _real_A_u8(data["A"][-1])))
                     print("process image... %s" % data["A_path"])
                     counters["n"] += 1
@@ -398,6 +455,12 @@ def run_test(opt, model=None, device=None, dataset=None):
             M.write_json(os.path.join(vis.save_dir, rows.seq, "metrics.json"), doc)
             metrics_out[rows.seq] = doc["summary"]
     marks["to_last_jpeg_s"] = time.perf_counter() - t_start
+    d2h_bytes = counters["d2h_bytes"] + sum(enc.d2h_bytes for enc in jpeg_state.values())
+    marks["d2h_bytes_per_frame"] = d2h_bytes // counters["n"] if counters["n"] else 0
+    if want_jpeg:
+        split["jpeg_s"] = sum(enc.encode_s for enc in jpeg_state.values())
+        split["d2h_s"] = split.get("d2h_s", 0.0) + sum(enc.d2h_s for enc in jpeg_state.values())
+        split["jpeg_second_copies"] = sum(enc.second_copies for enc in jpeg_state.values())
     videos = []
     if getattr(opt, "write_video", False):
         # the reference's next stage (image2video*.py, text2video_audio.sh:44) on the frames just written; under

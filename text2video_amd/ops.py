@@ -588,13 +588,155 @@ def resample_crop_normalize_u8(src_u8, new_size, crop_pos, crop_size, out=None, 
     return out
 
 
-def tensor2im_u8(x):
-    """util.tensor2im on the device: uint8 of (x+1)/2*255, same layout."""
+def tensor2im_u8(x, out=None):
+    """util.tensor2im on the device: uint8 of (x+1)/2*255, same layout.  out: a contiguous uint8 device tensor of x's
+    element count to write instead (e.g. one image of a batch for jpeg_encode_u8)."""
     c = context()
     _chk(x, "x")
-    y = torch.empty(x.shape, dtype=torch.uint8, device=x.device)
-    check(c.lib.t2v_tensor2im_u8(c.handle, _stream(), _p(x), _p(y), x.numel()), "tensor2im_u8")
-    return y
+    if out is None:
+        out = torch.empty(x.shape, dtype=torch.uint8, device=x.device)
+    elif not (out.is_cuda and out.dtype == torch.uint8 and out.is_contiguous() and out.numel() == x.numel()):
+        raise ValueError("tensor2im_u8: out must be a contiguous uint8 device tensor of %d elements" % x.numel())
+    check(c.lib.t2v_tensor2im_u8(c.handle, _stream(), _p(x), _p(out), x.numel()), "tensor2im_u8")
+    return out
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# JPEG encoding (libt2v_jpeg.so, include/t2v_jpeg.h; the host part of the file: text2video_amd/jpeg.py)
+# ----------------------------------------------------------------------------------------------------------------------
+_jpeg_workspace = {}      # device -> uint8 workspace of t2v_jpeg_encode_u8 (grown on demand; uses are stream-ordered)
+
+
+def _jpeg():
+    from . import _jpeglib
+    return _jpeglib
+
+
+def jpeg_supported(H, W):
+    """whether jpeg_encode_u8 takes H x W images (t2v_jpeg_supported)"""
+    return bool(_jpeg().load().t2v_jpeg_supported(int(H), int(W)))
+
+
+def jpeg_scan_capacity(H, W):
+    """bytes no scan of an H x W image exceeds (t2v_jpeg_scan_capacity; 0: a geometry jpeg_encode_u8 refuses)"""
+    return int(_jpeg().load().t2v_jpeg_scan_capacity(int(H), int(W)))
+
+
+def jpeg_workspace_bytes(H, W, nimg):
+    """bytes of workspace jpeg_encode_u8 needs for nimg H x W images (0: a call it refuses)"""
+    return int(_jpeg().load().t2v_jpeg_workspace_bytes(int(H), int(W), int(nimg)))
+
+
+def jpeg_stage_u8(src, dst, lut=None):
+    """Copy the uint8 device image src [H,W,3|4] into dst [H,W,3|4] (another channel stride allowed), channels 0..2 through
+    the 256-entry byte map `lut` (bytes / uint8 array on the host; None: unchanged); a fourth channel of dst is written
+    as 0 (t2v_jpeg_stage_u8).  One launch; returns dst."""
+    J = _jpeg()
+    context()
+    for t, name in ((src, "src"), (dst, "dst")):
+        if not (t.is_cuda and t.dtype == torch.uint8 and t.is_contiguous() and t.dim() == 3 and t.shape[2] in (3, 4)):
+            raise ValueError("jpeg_stage_u8: %s must be a contiguous uint8 device tensor [H,W,3|4]" % name)
+    if tuple(src.shape[:2]) != tuple(dst.shape[:2]):
+        raise ValueError("jpeg_stage_u8: src is %dx%d, dst is %dx%d" % (src.shape[0], src.shape[1], dst.shape[0], dst.shape[1]))
+    host_lut = None
+    if lut is not None:
+        lut = bytes(bytearray(lut))
+        if len(lut) != 256:
+            raise ValueError("jpeg_stage_u8: lut must hold 256 bytes")
+        host_lut = ctypes.cast(ctypes.c_char_p(lut), ctypes.c_void_p)
+    J.check(J.load().t2v_jpeg_stage_u8(_stream(), _p(src), src.shape[2], _p(dst), dst.shape[2], src.shape[0] * src.shape[1],
+                                       host_lut), "stage_u8")
+    return dst
+
+
+def jpeg_encode_u8(images, quality=75, out=None, lengths=None, workspace=None):
+    """The entropy-coded JPEG scans of uint8 device images (t2v_jpeg_encode_u8, include/t2v_jpeg.h): images is a contiguous
+    uint8 device tensor [N,H,W,3|4] or [H,W,3|4] (R, G, B in channels 0..2), quality the IJG quality 1..100.
+    -> (out, lengths): out a uint8 device tensor [N, capacity] whose row i starts with image i's scan, lengths an int32
+    device tensor [N] of the scans' byte lengths.  jpeg.file_bytes(jpeg.header(H, W, quality), scan) is the file Pillow's
+    Image.save(format="JPEG", quality=quality) writes.
+    out: that tensor to write instead, any capacity >= 1 per row: a scan longer than the row is reported through
+    lengths[i] > capacity, its first `capacity` bytes are valid and nothing behind them is written (default: rows of
+    jpeg_scan_capacity(H, W) bytes, which every scan fits).  lengths: an int32 device tensor [N] to write instead.
+    workspace: a uint8 device tensor of at least jpeg_workspace_bytes(H, W, N) bytes, 256-byte aligned (default: one kept
+    per device).  One memset and seven launches on the current stream, no host synchronisation; an unsupported geometry
+    (jpeg_supported) or an argument that does not fit raises with nothing launched."""
+    J = _jpeg()
+    context()
+    if not (images.is_cuda and images.dtype == torch.uint8 and images.is_contiguous() and images.dim() in (3, 4)
+            and images.shape[-1] in (3, 4)):
+        raise ValueError("jpeg_encode_u8: images must be a contiguous uint8 device tensor [N,H,W,3|4] or [H,W,3|4]")
+    N = images.shape[0] if images.dim() == 4 else 1
+    H, W, cs = (int(v) for v in images.shape[-3:])
+    quality = int(quality)
+    if not 1 <= quality <= 100:
+        raise ValueError("jpeg_encode_u8: quality %d is not in 1..100" % quality)
+    if not jpeg_supported(H, W):
+        raise ValueError("jpeg_encode_u8: %dx%d is outside %d..%d per dimension" % (H, W, J.MIN_DIM, J.MAX_DIM))
+    if not 1 <= N <= J.MAX_IMAGES:
+        raise ValueError("jpeg_encode_u8: %d images (1..%d per call)" % (N, J.MAX_IMAGES))
+    dev = images.device
+    if out is None:
+        out = torch.empty(N, jpeg_scan_capacity(H, W), dtype=torch.uint8, device=dev)
+    if not (out.is_cuda and out.dtype == torch.uint8 and out.is_contiguous() and out.dim() == 2 and out.shape[0] == N
+            and out.shape[1] >= 1):
+        raise ValueError("jpeg_encode_u8: out must be a contiguous uint8 device tensor [%d, capacity]" % N)
+    if lengths is None:
+        lengths = torch.empty(N, dtype=torch.int32, device=dev)
+    if not (lengths.is_cuda and lengths.dtype == torch.int32 and lengths.is_contiguous() and lengths.numel() == N):
+        raise ValueError("jpeg_encode_u8: lengths must be a contiguous int32 device tensor [%d]" % N)
+    need = jpeg_workspace_bytes(H, W, N)
+    if workspace is None:
+        workspace = _jpeg_workspace.get(str(dev))
+        if workspace is None or workspace.numel() < need:
+            workspace = _jpeg_workspace[str(dev)] = torch.empty(need, dtype=torch.uint8, device=dev)
+    elif not (workspace.is_cuda and workspace.dtype == torch.uint8 and workspace.is_contiguous()):
+        raise ValueError("jpeg_encode_u8: workspace must be a contiguous uint8 device tensor")
+    if workspace.numel() < need or workspace.data_ptr() % 256:
+        raise ValueError("jpeg_encode_u8: workspace holds %d bytes at an address that is %d mod 256; %d images of %dx%d need "
+                         "%d aligned bytes" % (workspace.numel(), workspace.data_ptr() % 256, N, H, W, need))
+    J.check(J.load().t2v_jpeg_encode_u8(_stream(), _p(images), cs, H, W, N, quality, _p(workspace), _p(out), out.shape[1],
+                                        _p(lengths)), "encode_u8")
+    return out, lengths
+
+
+_side_streams = {}      # device -> a stream of the library's own beside the current one (created on first use)
+
+
+def side_stream():
+    """A second stream on the current device (t2v_stream_create: non-blocking), for a copy that must not queue behind the
+    work the current stream already holds.  The caller orders it against that work itself (an event it has waited for)."""
+    c = context()
+    h = _side_streams.get(c.device)
+    if h is None:
+        p = ctypes.c_void_p()
+        check(c.lib.t2v_stream_create(c.handle, ctypes.byref(p)), "stream_create")
+        h = _side_streams[c.device] = p.value
+    return h
+
+
+def stream_synchronize(stream):
+    """wait on the host for a stream side_stream() returned"""
+    c = context()
+    check(c.lib.t2v_stream_synchronize(c.handle, ctypes.c_void_p(stream)), "stream_synchronize")
+
+
+def copy_bytes_to_host(dst_pinned, dst_offset, src, src_offset, nbytes, stream=None):
+    """Asynchronous D2H copy of nbytes bytes on the current stream (or on `stream`, a side_stream()): from byte src_offset of
+    the device tensor src to byte dst_offset of the page-locked host tensor dst_pinned (both contiguous).  Parts of tensors,
+    which neither tensor provider's copy_ does without building views."""
+    c = context()
+
+    def size(t):      # (torch: a property; leantorch: a method)
+        n = t.nbytes
+        return n() if callable(n) else n
+    if not (0 <= src_offset and 0 <= dst_offset and 0 <= nbytes and src_offset + nbytes <= size(src)
+            and dst_offset + nbytes <= size(dst_pinned)):
+        raise ValueError("copy_bytes_to_host: %d bytes from offset %d to offset %d do not fit" % (nbytes, src_offset, dst_offset))
+    if nbytes:
+        check(c.lib.t2v_memcpy(c.handle, _stream() if stream is None else ctypes.c_void_p(stream),
+                               ctypes.c_void_p(dst_pinned.data_ptr() + dst_offset),
+                               ctypes.c_void_p(src.data_ptr() + src_offset), nbytes, _lib.COPY_D2H), "memcpy d2h")
 
 
 _metrics_scratch = {}      # device -> float64 scratch of t2v_image_metrics_u8 (grown on demand; uses are stream-ordered)

@@ -142,8 +142,16 @@ class TestOptions(BaseOptions):
           "warping error under the real flow's forward-backward mask, tOF, and the flow-free flicker term, under "
           "\"temporal\" in metrics.json and --timing_json")
 
+        g("--gpu_jpeg", action="store_true", help="encode fake_B_*.jpg / real_A_*.jpg on the GPU (ops.jpeg_encode_u8: the "
+          "bytes Pillow writes) instead of copying every frame to the host and encoding it on threads there")
+        g("--jpeg_quality", type=int, default=None, help="with --gpu_jpeg: the JPEG quality, 1..100 (default 75, Pillow's)")
+
     def parse(self, argv=None, save=False):
         opt = super().parse(argv, save)
+        if opt.jpeg_quality is not None and not opt.gpu_jpeg:
+            self.parser.error("--jpeg_quality %d: the quality of --gpu_jpeg, which is not given" % opt.jpeg_quality)
+        if opt.jpeg_quality is not None and not 1 <= opt.jpeg_quality <= 100:
+            self.parser.error("--jpeg_quality %d is not in 1..100" % opt.jpeg_quality)
         if opt.metrics_temporal:
             opt.metrics = True
         if opt.metrics and opt.shard_chunks:

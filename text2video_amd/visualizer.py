@@ -1,7 +1,8 @@
 """Result writer with the reference's output layout (SURVEY.md App. F `Visualizer.save_images`):
     <results_dir>/<name>/<phase>_<which_epoch>/<seq>/<label>_<basename of the test_img file>.jpg
 which is what text2video_audio.sh:39-40 cleans and image2video*.py globs (`fake_B_*.jpg`).
-JPEG encoding runs on a small thread pool so it overlaps the GPU work of the next frames."""
+JPEG encoding runs on a small thread pool so it overlaps the GPU work of the next frames; files that arrive encoded
+(test.py --gpu_jpeg: ops.jpeg_encode_u8) are only written by it."""
 import os
 from concurrent.futures import ThreadPoolExecutor
 
@@ -16,18 +17,34 @@ def tensor2im_np(x_chw):
 
 
 class Visualizer:
-    def __init__(self, opt, workers=4):
+    def __init__(self, opt, workers=4, quality=None):
+        """quality: the JPEG quality of save_images (None: Pillow's default, 75)"""
+        self.quality = quality
         self.save_dir = os.path.join(opt.results_dir, opt.name, "%s_%s" % (opt.phase, opt.which_epoch))
         self.pool = ThreadPoolExecutor(max_workers=workers)
         self.pending = []
         self._made = set()
 
+    def _write(self, path, arr):
+        if self.quality is None:
+            Image.fromarray(arr).save(path)
+        else:
+            Image.fromarray(arr).save(path, quality=self.quality)
+
     @staticmethod
-    def _write(path, arr):
-        Image.fromarray(arr).save(path)
+    def _write_bytes(path, blob):
+        with open(path, "wb") as fh:
+            fh.write(blob)
+
+    def save_bytes(self, files, a_path):
+        """files: {label: the finished JPEG file as bytes}.  Same names as save_images; returns the written paths."""
+        return self._save(files, a_path, self._write_bytes, lambda blob: blob)
 
     def save_images(self, visuals, a_path):
         """visuals: {label: uint8 HWC array}.  Returns the written paths."""
+        return self._save(visuals, a_path, self._write, np.ascontiguousarray)
+
+    def _save(self, items, a_path, write, prepare):
         sub = os.path.basename(os.path.dirname(a_path))
         name = os.path.splitext(os.path.basename(a_path))[0]
         d = os.path.join(self.save_dir, sub)
@@ -35,9 +52,9 @@ class Visualizer:
             os.makedirs(d, exist_ok=True)
             self._made.add(d)
         out = []
-        for label, arr in visuals.items():
+        for label, item in items.items():
             path = os.path.join(d, "%s_%s.jpg" % (label, name))
-            self.pending.append(self.pool.submit(self._write, path, np.ascontiguousarray(arr)))
+            self.pending.append(self.pool.submit(write, path, prepare(item)))
             out.append(path)
         return out
 
