@@ -282,6 +282,27 @@ int t2v_batch_norm_finalize_scratch(t2v_ctx* ctx, void* stream, const t2v_conv_d
 int t2v_instance_norm_apply(t2v_ctx* ctx, void* stream, const float* x, const float* mean_rstd,
                             const float* gamma, const float* beta, const float* res1,
                             const float* res2, float* y, long npix, int C, int relu);
+/* Three more entries to the norm-apply kernels (additive to ABI 22): the launches a generator frame makes, on their own.
+ * Each refuses on the host, before anything is launched (T2V_ERR_INVALID): a NULL required pointer, C % 4 != 0 (n % 4 != 0),
+ * npix < 1, nimg < 1, gamma without beta or beta without gamma.
+ *
+ * t2v_instance_norm_apply_batch: t2v_instance_norm_apply on nimg images in one launch.  x, res1, res2 (nullable) and y hold
+ * the images back to back, npix*C floats apart; mean_rstd holds nimg tables [C][2], 2*C floats apart; gamma and beta [C]
+ * are shared by the images.  y == x is allowed.  Image i carries the bits of t2v_instance_norm_apply on its own operands.
+ *
+ * t2v_instance_norm_join: y = (norm_a(a_y) + a_res) + (norm_b(b_y) + b_res) in one pass, the encoder join: the bits of
+ * two t2v_instance_norm_apply calls (relu 0, res1 = the side's res) followed by t2v_add.  Per side: y and res (both
+ * required) nimg maps of npix*C floats, mean_rstd nimg tables of 2*C floats, gamma / beta [C] (both or neither).
+ *
+ * t2v_add: y[i] = a[i] + b[i], n floats, n % 4 == 0, 16-byte aligned pointers. */
+int t2v_instance_norm_apply_batch(t2v_ctx* ctx, void* stream, const float* x, const float* mean_rstd,
+                                  const float* gamma, const float* beta, const float* res1,
+                                  const float* res2, float* y, long npix, int C, int relu, int nimg);
+int t2v_instance_norm_join(t2v_ctx* ctx, void* stream, const float* a_y, const float* a_mean_rstd, const float* a_gamma,
+                           const float* a_beta, const float* a_res, const float* b_y, const float* b_mean_rstd,
+                           const float* b_gamma, const float* b_beta, const float* b_res, float* y, long npix, int C,
+                           int nimg);
+int t2v_add(t2v_ctx* ctx, void* stream, const float* a, const float* b, float* y, long n);
 
 /* ------------------------------------------------------------------------------------------
  * Flow-warp compositor.  Replaces SpatialGridSamplerBilinear_updateOutput (THCUNN.h:1048; F.

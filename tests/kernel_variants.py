@@ -301,6 +301,9 @@ def gamma(n):
     return n * U / (1 - n * U)
 
 
+LEAKY32 = float(torch.tensor(0.2, dtype=torch.float32))    # the LeakyReLU slope as the kernels hold it: float32(0.2), not 0.2
+
+
 def read_consts(path):
     """{name: float64 tensor} of the `constexpr double kX[r][c] = {...};` tables of a generated header"""
     src = open(path).read()
@@ -384,23 +387,35 @@ def input_bound(Aabs, n, e_d=None):
     return b if e_d is None else b + (1 + gamma(2 * n)) * e_d
 
 
-def lazy_d64(x, mean_rstd, gamma_=None, beta=None, relu=False, res=None):
-    """d = [relu]((x - mean) * rstd [* gamma + beta]) [+ res] in float64 from the fp32 operands, and its elementwise error
-    bound in fp32: x - mean (1 rounding), * rstd (2), * gamma (3), + beta (4), + res (5); each rounding is relative to the
-    value it rounds, all of which are <= |x - mean| rstd |gamma| + |beta| (+ |res|); ReLU is 1-Lipschitz: e_d <= gamma(5) (that
-    sum).  x [.., C], mean_rstd [C, 2]."""
+def lazy_d64(x, mean_rstd, gamma_=None, beta=None, relu=False, res=None, res2=None):
+    """d = [act]((x - mean) * rstd [* gamma + beta]) [+ res] [+ res2] in float64 from the fp32 operands, and its elementwise
+    error bound in fp32: x - mean (1 rounding), * rstd (2), * gamma (3), + beta (4), + res (5); each rounding is relative to
+    the value it rounds, all of which are <= |x - mean| rstd |gamma| + |beta| (+ |res|); ReLU is 1-Lipschitz: e_d <= gamma(5)
+    (that sum).  relu: 0 / False none, 1 / True ReLU, 2 LeakyReLU with the slope float32(0.2) the kernels multiply by (norm_act,
+    transform_common.h) -- v > 0 ? v : slope v is 1-Lipschitz too, so a v and v64 on two sides of 0 differ after it by no more
+    than before; the product by the slope is one more rounding, and the reference may as well take the slope as 0.2: the two
+    differ by 7.5e-9 relative, inside one more u (gamma(7)).  A second residual is one more addition (+1).
+    x [.., C], mean_rstd [C, 2]."""
     m, r = mean_rstd[:, 0].double(), mean_rstd[:, 1].double()
     t = (x.double() - m) * r
     mag = (x.double() - m).abs() * r
+    n = 5
     if gamma_ is not None:
         t = t * gamma_.double() + beta.double()
         mag = mag * gamma_.double().abs() + beta.double().abs()
-    if relu:
+    if int(relu) == 1:
         t = t.clamp(min=0)
+    elif int(relu) == 2:
+        t = torch.where(t > 0, t, t * LEAKY32)
+        n += 2
     if res is not None:
         t = t + res.double()
         mag = mag + res.double().abs()
-    return t, gamma(5) * mag + 5 * TINY
+    if res2 is not None:
+        t = t + res2.double()
+        mag = mag + res2.double().abs()
+        n += 1
+    return t, gamma(n) * mag + n * TINY
 
 
 def weight64(w, G, transposed_layout=False, flip=False):
@@ -490,20 +505,28 @@ def dy_front64(dy, x, mean_rstd, gamma_, beta, relu, sums, npix):
     fp32 pre, which is within gamma(4) (|gamma xhat| + |beta|) of that (two roundings for xhat, one each for the product and
     the sum); where |pre| is no larger than that the two may disagree, and the bound there also admits the other branch:
     + |r gamma dy| |act'(+) - act'(-)|."""
+    xh, pre, act, lo, near, r, ga = norm_pre64(x, mean_rstd, gamma_, beta, relu)
+    g = dy.double() * act
+    k0, k1 = sums[:, 0].double() / npix, sums[:, 1].double() / npix
+    front = r * ga * (g - k0 - xh * k1)
+    err = gamma(9) * (r * ga).abs() * (g.abs() + k0.abs() + xh.abs() * k1.abs()) + 9 * TINY
+    err = err + near.double() * (r * ga * dy.double()).abs() * (1.0 - lo)
+    return front, err
+
+
+def norm_pre64(x, mean_rstd, gamma_, beta, relu):
+    """what dy_front64 and the norm backward's sums share: xhat, pre = gamma xhat + beta and act'(pre) in float64 (the
+    convention at exactly zero is the kernels' `pre > 0`: ReLU' gives 0 and Leaky gives 0.2 at pre == 0), the lower slope
+    `lo`, and the `near` mask inside which the kernel's own fp32 pre may fall on the other side of zero.  Also r, gamma."""
     m, r = mean_rstd[:, 0].double(), mean_rstd[:, 1].double()
     ga = gamma_.double() if gamma_ is not None else torch.ones_like(m)
     be = beta.double() if beta is not None else torch.zeros_like(m)
     xh = (x.double() - m) * r
     pre = ga * xh + be
-    lo = 0.0 if relu == 1 else 0.2 if relu == 2 else 1.0
-    act = torch.where(pre > 0, 1.0, lo).double()
-    g = dy.double() * act
-    k0, k1 = sums[:, 0].double() / npix, sums[:, 1].double() / npix
-    front = r * ga * (g - k0 - xh * k1)
-    err = gamma(9) * (r * ga).abs() * (g.abs() + k0.abs() + xh.abs() * k1.abs()) + 9 * TINY
-    near = pre.abs() <= gamma(4) * ((ga * xh).abs() + be.abs()) + TINY
-    err = err + near.double() * (r * ga * dy.double()).abs() * (1.0 - lo)
-    return front, err
+    lo = 0.0 if relu == 1 else LEAKY32 if relu == 2 else 1.0      # float32(0.2), the kernels' constant; 7.5e-9 from 0.2: inside u
+    act = torch.where(pre > 0, torch.ones_like(pre), torch.full_like(pre, lo))
+    near =pre.abs() <= gamma(4) * ((ga * xh).abs() + be.abs()) + TINY
+    return xh, pre, act, lo, near, r, ga
 
 
 def dgrad_output64(dV, TH, TW):
@@ -812,17 +835,17 @@ TABLE = {
     "t2v::accumulate_kernel":
         Existing(("tests/test_gpu_kernel_variants.py::test_layout_and_reduction_forms_against_float64",)),
     "t2v::act_backward_kernel":
-        Existing(("tests/test_gpu_backward.py::test_pointwise_and_pooling_backward", "tests/test_gpu_backward.py::test_masked_l1_and_flow_head_activation_backward",)),
+        Existing(("tests/test_gpu_elementwise_float64.py::test_act_backward_against_float64", "tests/test_gpu_backward.py::test_pointwise_and_pooling_backward", "tests/test_gpu_backward.py::test_masked_l1_and_flow_head_activation_backward",)),
     "t2v::adam_kernel":
         Existing(("tests/test_gpu_train_pieces.py::test_fused_adam_matches_torch041_semantics",)),
     "t2v::adam_multi_kernel":
         Existing(("tests/test_gpu_train_pieces.py::test_multi_tensor_adam_against_float64_on_both_paths",)),
     "t2v::add_kernel":
-        Uncovered('no Python entry point; reached only inside generator frames compared end to end with the oracle'),
+        Existing(("tests/test_gpu_elementwise_float64.py::test_norm_join_is_two_applies_and_an_add", "tests/test_gpu_elementwise_float64.py::test_add_strides_past_the_grid_cap",)),
     "t2v::avgpool3s2_backward_kernel":
-        Existing(("tests/test_gpu_backward.py::test_pointwise_and_pooling_backward",)),
+        Existing(("tests/test_gpu_elementwise_float64.py::test_avgpool_forward_and_backward_against_float64", "tests/test_gpu_backward.py::test_pointwise_and_pooling_backward",)),
     "t2v::avgpool3s2_kernel":
-        Existing(("tests/test_gpu_ops.py::test_avgpool_count_include_pad_false",)),
+        Existing(("tests/test_gpu_elementwise_float64.py::test_avgpool_forward_and_backward_against_float64", "tests/test_gpu_ops.py::test_avgpool_count_include_pad_false",)),
     "t2v::bn_running_update_kernel":
         Existing(("tests/test_gpu_kernel_variants.py::test_scalar_channel_forms_against_float64",)),
     "t2v::channel_sum_final_kernel":
@@ -974,26 +997,26 @@ TABLE = {
     "t2v::dispatch_order_kernel":
         Uncovered('the fixed-grid dispatch-order self-test run by t2v_create: it writes tickets, no numerical output'),
     "t2v::inorm_apply_kernel":
-        Existing(("tests/test_gpu_ops.py::test_instance_norm_affine_residual_matches_trainmode_batchnorm", "tests/test_gpu_ops.py::test_instance_norm_large_mean_is_stable",)),
+        Existing(("tests/test_gpu_elementwise_float64.py::test_norm_apply_against_float64", "tests/test_gpu_elementwise_float64.py::test_norm_join_is_two_applies_and_an_add", "tests/test_gpu_ops.py::test_instance_norm_affine_residual_matches_trainmode_batchnorm", "tests/test_gpu_ops.py::test_instance_norm_large_mean_is_stable",)),
     "t2v::inorm_bwd_apply_kernel":
-        Existing(("tests/test_gpu_backward.py::test_norm_backward_with_fused_activation",)),
+        Existing(("tests/test_gpu_elementwise_float64.py::test_norm_backward_against_float64", "tests/test_gpu_backward.py::test_norm_backward_with_fused_activation",)),
     "t2v::inorm_bwd_final_kernel":
-        Existing(("tests/test_gpu_backward.py::test_norm_backward_with_fused_activation",)),
+        Existing(("tests/test_gpu_elementwise_float64.py::test_norm_backward_against_float64", "tests/test_gpu_backward.py::test_norm_backward_with_fused_activation",)),
     "t2v::inorm_bwd_reduce_kernel":
-        Existing(("tests/test_gpu_backward.py::test_norm_backward_with_fused_activation",)),
+        Existing(("tests/test_gpu_elementwise_float64.py::test_norm_backward_against_float64", "tests/test_gpu_backward.py::test_norm_backward_with_fused_activation",)),
     "t2v::inorm_finalize_kernel":
         Existing(("tests/test_gpu_ops.py::test_instance_norm_affine_residual_matches_trainmode_batchnorm", "tests/test_gpu_ops.py::test_instance_norm_large_mean_is_stable",
                   "tests/test_gpu_norm_finalize_grouped.py::test_grouped_tables_against_float64_and_the_single_kernel_form",)),
     "t2v::inorm_finalize_merge_kernel":
         Existing(("tests/test_gpu_norm_finalize_grouped.py::test_grouped_tables_against_float64_and_the_single_kernel_form",)),
     "t2v::loss_backward_kernel":
-        Existing(("tests/test_gpu_backward.py::test_pointwise_and_pooling_backward",)),
+        Existing(("tests/test_gpu_elementwise_float64.py::test_loss_backward_past_the_grid_cap", "tests/test_gpu_backward.py::test_pointwise_and_pooling_backward",)),
     "t2v::loss_terms_final_kernel":
         Existing(("tests/test_gpu_loss_terms.py::test_values_against_float64_and_seeds_bit_for_bit_in_one_run",)),
     "t2v::loss_terms_kernel":
         Existing(("tests/test_gpu_loss_terms.py::test_values_against_float64_and_seeds_bit_for_bit_in_one_run",)),
     "t2v::masked_l1_backward_kernel":
-        Existing(("tests/test_gpu_backward.py::test_masked_l1_and_flow_head_activation_backward",)),
+        Existing(("tests/test_gpu_elementwise_float64.py::test_masked_l1_and_its_backward_against_float64", "tests/test_gpu_backward.py::test_masked_l1_and_flow_head_activation_backward",)),
     "t2v::maxpool2x2_backward_kernel":
         Existing(("tests/test_gpu_train_pieces.py::test_maxpool2x2_forward_backward_matches_torch",)),
     "t2v::maxpool2x2_kernel":
@@ -1027,7 +1050,7 @@ TABLE = {
     "t2v::reduce_final_kernel":
         Existing(("tests/test_gpu_kernel_variants.py::test_layout_and_reduction_forms_against_float64",)),
     "t2v::reduce_masked_l1_kernel":
-        Existing(("tests/test_gpu_backward.py::test_masked_l1_and_flow_head_activation_backward",)),
+        Existing(("tests/test_gpu_elementwise_float64.py::test_masked_l1_and_its_backward_against_float64", "tests/test_gpu_backward.py::test_masked_l1_and_flow_head_activation_backward",)),
     "t2v::reduce_partial_kernel<0>":
         Existing(("tests/test_gpu_kernel_variants.py::test_layout_and_reduction_forms_against_float64",)),
     "t2v::reduce_partial_kernel<1>":
@@ -1049,9 +1072,9 @@ TABLE = {
     "t2v::unzip2_kernel":
         Existing(("tests/test_gpu_kernel_variants.py::test_layout_and_reduction_forms_against_float64",)),
     "t2v::warp_composite_backward_kernel":
-        Existing(("tests/test_gpu_backward.py::test_flow_warp_composite_backward_matches_oracle_autograd",)),
+        Existing(("tests/test_gpu_elementwise_float64.py::test_flow_warp_forward_and_backward_against_float64", "tests/test_gpu_backward.py::test_flow_warp_composite_backward_matches_oracle_autograd",)),
     "t2v::warp_composite_kernel":
-        Existing(("tests/test_gpu_ops.py::test_flow_warp_composite_vs_grid_sample",)),
+        Existing(("tests/test_gpu_elementwise_float64.py::test_flow_warp_forward_and_backward_against_float64", "tests/test_gpu_ops.py::test_flow_warp_composite_vs_grid_sample",)),
     "t2v::wgrad_reduce_kernel":
         Existing(("tests/test_gpu_backward.py::test_conv_weight_and_bias_gradient",)),
     "t2v::wino_gemm_sk_kernel<t2v::TileCfg<32,1,4,5,1>,3,false>":

@@ -155,6 +155,12 @@ SIGNATURES = {
                                               c_float]),
     "t2v_instance_norm_apply": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                         c_void_p, c_void_p, c_long, c_int, c_int]),
+    # the batch form, the encoder join and the plain sum of the norm-apply kernels (additive to ABI 22)
+    "t2v_instance_norm_apply_batch": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                              c_void_p, c_void_p, c_long, c_int, c_int, c_int]),
+    "t2v_instance_norm_join": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                       c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_long, c_int, c_int]),
+    "t2v_add": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_long]),
     "t2v_flow_warp_composite": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p,
                                         c_void_p, c_int, c_int]),
     "t2v_flow_warp_composite_backward": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,

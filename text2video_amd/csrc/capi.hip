@@ -1458,6 +1458,37 @@ int t2v_instance_norm_apply(t2v_ctx* ctx, void* stream, const float* x, const fl
     T2V_REQUIRE((gamma == nullptr) == (beta == nullptr), "inorm_apply: gamma and beta must both be given or both NULL");
     return launch_inorm_apply((hipStream_t)stream, x, mean_rstd, gamma, beta, res1, res2, y, npix, C, relu);
 }
+// the batch form, the encoder join and the plain sum of the norm-apply kernels (additive to the ABI): the launches the
+// generator's frames make, callable on their own
+int t2v_instance_norm_apply_batch(t2v_ctx* ctx, void* stream, const float* x, const float* mean_rstd, const float* gamma,
+                                  const float* beta, const float* res1, const float* res2, float* y, long npix, int C,
+                                  int relu, int nimg) {
+    T2V_REQUIRE(ctx && x && mean_rstd && y, "inorm_apply_batch: null pointer");
+    T2V_REQUIRE((gamma == nullptr) == (beta == nullptr), "inorm_apply_batch: gamma and beta must both be given or both NULL");
+    T2V_REQUIRE(C > 0 && C % 4 == 0, "inorm_apply_batch: C=%d must be a positive multiple of 4", C);
+    T2V_REQUIRE(npix >= 1 && nimg >= 1 && nimg <= 65535, "inorm_apply_batch: npix=%ld nimg=%d", npix, nimg);
+    T2V_REQUIRE(relu >= 0 && relu <= 2, "inorm_apply_batch: relu=%d", relu);
+    return launch_inorm_apply((hipStream_t)stream, x, mean_rstd, gamma, beta, res1, res2, y, npix, C, relu, nimg);
+}
+int t2v_instance_norm_join(t2v_ctx* ctx, void* stream, const float* a_y, const float* a_mean_rstd, const float* a_gamma,
+                           const float* a_beta, const float* a_res, const float* b_y, const float* b_mean_rstd,
+                           const float* b_gamma, const float* b_beta, const float* b_res, float* y, long npix, int C,
+                           int nimg) {
+    T2V_REQUIRE(ctx && a_y && a_mean_rstd && a_res && b_y && b_mean_rstd && b_res && y, "inorm_join: null pointer");
+    T2V_REQUIRE((a_gamma == nullptr) == (a_beta == nullptr) && (b_gamma == nullptr) == (b_beta == nullptr),
+                "inorm_join: gamma and beta must both be given or both NULL");
+    T2V_REQUIRE(C > 0 && C % 4 == 0, "inorm_join: C=%d must be a positive multiple of 4", C);
+    T2V_REQUIRE(npix >= 1 && nimg >= 1 && nimg <= 65535, "inorm_join: npix=%ld nimg=%d", npix, nimg);
+    NormJoinSide a, b;
+    a.y = a_y; a.mean_rstd = a_mean_rstd; a.gamma = a_gamma; a.beta = a_beta; a.res = a_res;
+    b.y = b_y; b.mean_rstd = b_mean_rstd; b.gamma = b_gamma; b.beta = b_beta; b.res = b_res;
+    return launch_inorm_join((hipStream_t)stream, a, b, y, npix, C, nimg);
+}
+int t2v_add(t2v_ctx* ctx, void* stream, const float* a, const float* b, float* y, long n) {
+    T2V_REQUIRE(ctx && a && b && y, "add: null pointer");
+    T2V_REQUIRE(n >= 4 && n % 4 == 0, "add: n=%ld must be a positive multiple of 4", n);
+    return launch_add((hipStream_t)stream, a, b, y, n);
+}
 
 int t2v_flow_warp_composite(t2v_ctx* ctx, void* stream, const float* raw, const float* fw, const float* prev,
                             int prev_cs, int prev_c0, float* out, float* warp_out, int H, int W) {

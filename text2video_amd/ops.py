@@ -336,14 +336,96 @@ def instance_norm_finalize(stats, desc, eps=1e-5, out=None, running=None, scratc
     return mr
 
 
-def instance_norm_apply(x, mean_rstd, gamma=None, beta=None, res1=None, res2=None, relu=False, out=None):
+def _numel(t, n, name):
+    """the size contract of an elementwise entry, checked before the library sees a pointer"""
+    if t is not None and t.numel() != n:
+        raise ValueError("%s holds %d values, the call needs %d" % (name, t.numel(), n))
+
+
+def instance_norm_apply(x, mean_rstd, gamma=None, beta=None, res1=None, res2=None, relu=False, out=None, nimg=None):
+    """nimg: x, res1, res2 and the result are nimg images [nimg, ..., C] back to back, mean_rstd their nimg tables [nimg, C, 2]
+    (t2v_instance_norm_apply_batch: one launch); gamma / beta are shared"""
     c = context()
     _chk(x, "x")
     C = x.shape[-1]
+    if nimg is not None:
+        nimg = int(nimg)
+        if nimg < 1 or x.numel() % (nimg * C) != 0 or x.numel() == 0:
+            raise ValueError("x does not hold nimg = %d images of C = %d channels" % (nimg, C))
+        if C % 4 != 0:
+            raise ValueError("C = %d must be a multiple of 4" % C)
+        if (gamma is None) != (beta is None):
+            raise ValueError("gamma and beta must both be given or both None")
+        npix = x.numel() // (nimg * C)
+        y = out if out is not None else torch.empty_like(x)
+        for t, name in ((mean_rstd, "mean_rstd"), (gamma, "gamma"), (beta, "beta"), (res1, "res1"), (res2, "res2"), (y, "out")):
+            if t is not None:
+                _chk(t, name)
+        _numel(mean_rstd, nimg * 2 * C, "mean_rstd")
+        _numel(gamma, C, "gamma")
+        _numel(beta, C, "beta")
+        _numel(res1, x.numel(), "res1")
+        _numel(res2, x.numel(), "res2")
+        _numel(y, x.numel(), "out")
+        check(c.lib.t2v_instance_norm_apply_batch(c.handle, _stream(), _p(x), _p(mean_rstd), _p(gamma), _p(beta), _p(res1),
+                                                  _p(res2), _p(y), npix, C, int(relu), nimg), "instance_norm_apply_batch")
+        return y
     npix = x.numel() // C
     y = out if out is not None else torch.empty_like(x)
     check(c.lib.t2v_instance_norm_apply(c.handle, _stream(), _p(x), _p(mean_rstd), _p(gamma), _p(beta), _p(res1),
                                         _p(res2), _p(y), npix, C, int(relu)), "instance_norm_apply")
+    return y
+
+
+def instance_norm_join(a, b, nimg=1, out=None):
+    """The encoder join (t2v_instance_norm_join): (norm_a(a_y) + a_res) + (norm_b(b_y) + b_res) in one launch.  a, b: tuples
+    (y, mean_rstd, gamma | None, beta | None, res); y and res [nimg, ..., C], mean_rstd [nimg, C, 2]."""
+    c = context()
+    ya = a[0]
+    _chk(ya, "a.y")
+    C = ya.shape[-1]
+    nimg = int(nimg)
+    if C % 4 != 0:
+        raise ValueError("C = %d must be a multiple of 4" % C)
+    if nimg < 1 or ya.numel() == 0 or ya.numel() % (nimg * C) != 0:
+        raise ValueError("a.y does not hold nimg = %d images of C = %d channels" % (nimg, C))
+    n = ya.numel()
+    y = out if out is not None else torch.empty_like(ya)
+    _chk(y, "out")
+    _numel(y, n, "out")
+    for side, tag in ((a, "a"), (b, "b")):
+        sy, mr, ga, be, res = side
+        if sy is None or mr is None or res is None:
+            raise ValueError("%s: y, mean_rstd and res are required" % tag)
+        if (ga is None) != (be is None):
+            raise ValueError("%s: gamma and beta must both be given or both None" % tag)
+        for t, name in ((sy, "y"), (mr, "mean_rstd"), (ga, "gamma"), (be, "beta"), (res, "res")):
+            if t is not None:
+                _chk(t, tag + "." + name)
+        _numel(sy, n, tag + ".y")
+        _numel(res, n, tag + ".res")
+        _numel(mr, nimg * 2 * C, tag + ".mean_rstd")
+        _numel(ga, C, tag + ".gamma")
+        _numel(be, C, tag + ".beta")
+    check(c.lib.t2v_instance_norm_join(c.handle, _stream(), _p(a[0]), _p(a[1]), _p(a[2]), _p(a[3]), _p(a[4]), _p(b[0]),
+                                       _p(b[1]), _p(b[2]), _p(b[3]), _p(b[4]), _p(y), n // (nimg * C), C, nimg),
+          "instance_norm_join")
+    return y
+
+
+def add(a, b, out=None):
+    """a + b (t2v_add); numel a multiple of 4"""
+    c = context()
+    _chk(a, "a")
+    _chk(b, "b")
+    n = a.numel()
+    if n == 0 or n % 4 != 0:
+        raise ValueError("n = %d must be a positive multiple of 4" % n)
+    y = out if out is not None else torch.empty_like(a)
+    _chk(y, "out")
+    _numel(b, n, "b")
+    _numel(y, n, "out")
+    check(c.lib.t2v_add(c.handle, _stream(), _p(a), _p(b), _p(y), n), "add")
     return y
 
 
