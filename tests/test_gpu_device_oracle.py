@@ -319,6 +319,8 @@ def _df_on_hip_frames(mods, clip, boxes, f_hip, g_hip, seed):
     # of the stems' k order 1e-6 on nine tensors and 4e-4 .. 2e-3 on exactly those four -- the step's gradient being, bit for
     # bit, what D_f alone computes on the returned frames.  The fp32 oracle is subject to the same event on other elements
     # (~8 % per pass and implementation).  So: the median against the fp32 oracle's own, and a cap on what one flip can do.
+    # (D_f's geometry with the kink masks SHARED between the HIP module and float64 -- no flip left, every tensor held to 4 x the
+    # fp32 oracle's own error on the weights of all three seeds -- is tests/test_gpu_module_gradients.py, cases face128_seed5 .. 7.)
     import copy
     from oracle.generator_ref import MultiscaleDiscriminator      # noqa: F401
     mse = torch.nn.MSELoss()

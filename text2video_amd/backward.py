@@ -24,6 +24,7 @@ class ConvDataGrad:
     def __init__(self, fwd_desc):
         d = self.fwd = fwd_desc
         self.fold = 0
+        self.crop = None
         if d.transposed:
             # forward: [H,W] -> [2H,2W]; gradient: conv k3 s2 p1 on dY
             self.desc = ops.conv_desc(2 * d.H, 2 * d.W, d.Cout, d.Cin, 3, 2, 1, ops.PAD_ZERO)
@@ -34,10 +35,15 @@ class ConvDataGrad:
             # output_padding so that the transposed conv reproduces the forward input size
             op_h = d.H - ((ho - 1) * 2 - 2 * d.pad + d.kH)
             op_w = d.W - ((wo - 1) * 2 - 2 * d.pad + d.kW)
-            assert op_h == op_w and op_h in (0, 1), "unsupported stride-2 geometry"
-            self.desc = ops.conv_desc(ho, wo, d.Cout, d.Cin, d.kH, 2, d.pad, ops.PAD_ZERO, True, output_padding=op_h)
+            assert op_h in (0, 1) and op_w in (0, 1), "unsupported stride-2 geometry"
+            self.desc = ops.conv_desc(ho, wo, d.Cout, d.Cin, d.kH, 2, d.pad, ops.PAD_ZERO, True, output_padding=max(op_h, op_w))
             self.kind = "same"
-            self._polyphase()
+            if op_h != op_w:
+                # H and W of different parity (a 7 x 6 map): the transposed conv has ONE output_padding, so the dimension that
+                # needs none gets a last row / column the forward conv never read -- computed by the direct kernel, dropped here
+                self.crop = (d.H, d.W)
+            else:
+                self._polyphase()
         else:
             ho, wo = ops.conv_out_dims(d)
             if d.pad_mode == ops.PAD_REFLECT and d.pad > 0:
@@ -71,6 +77,9 @@ class ConvDataGrad:
 
     def batch(self, dy, out):
         """dy: [B, Hout, Wout, cs] -> out [B, H, W, round_up4(Cin)]: one launch for a direct-algorithm gradient conv"""
+        if self.crop:
+            out.copy_(ops.conv2d_auto_batch(dy, self.packed, None, self.desc)[:, :self.crop[0], :self.crop[1]])
+            return out
         if not self.fold:
             return ops.conv2d_auto_batch(dy, self.packed, None, self.desc, out=out)
         dxp = ops.conv2d_auto_batch(dy, self.packed, None, self.desc)
@@ -80,6 +89,9 @@ class ConvDataGrad:
 
     def __call__(self, dy, out=None):
         """dy: [Hout, Wout, cs>=Cout] -> dX [H, W, round_up4(Cin)] (written into `out` if given)."""
+        if self.crop:
+            dx = ops.conv2d_auto(dy, self.packed, None, self.desc)[:self.crop[0], :self.crop[1]]
+            return dx.contiguous() if out is None else out.copy_(dx)
         if not self.fold:
             return ops.conv2d_auto(dy, self.packed, None, self.desc, out=out)
         dxp = ops.conv2d_auto(dy, self.packed, None, self.desc)

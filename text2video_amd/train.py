@@ -258,6 +258,10 @@ class _ConvBlock(torch.autograd.Function):
         # loss reaches the fake / raw passes only) -- that backward runs on the images [pt_skip:] alone.
         B = x.shape[0]
         assert B % groups == 0, "conv_block: batch %d is not %d equal passes" % (B, groups)
+        if pt_skip and norm == "batch" and groups == 1:
+            # (the statistics of ONE pass cover the skipped images too: the norm's adjoint on x[pt_skip:] alone would be wrong)
+            raise ValueError("conv_block: pt_skip=%d with norm='batch' needs the skipped images in passes of their own "
+                             "(groups > 1): one pass's batch statistics couple every image's gradient" % pt_skip)
         dev = x.device
         xcs = x.shape[-1]
         ho, wo = ops.conv_out_dims(desc)
