@@ -1,10 +1,14 @@
-"""python -m text2video_amd.evaluate DIR_A DIR_B [--pattern 'fake_B_*'] [--temporal] [--json OUT]
+"""python -m text2video_amd.evaluate DIR_A DIR_B [--pattern 'fake_B_*'] [--temporal] [--gpu_decode] [--json OUT]
 
 PSNR / SSIM / MAE between the image files of two result trees, paired by relative path: the picture-level answer to "what
 does --arith bf16x2 do to my model" (the same test.py command run twice) and "epoch 20 against epoch 40".  The files are
 decoded with Pillow and compared on the GPU by the kernel of `test.py --metrics` (ops.image_metrics, whole frame only).
 Prints and (--json) writes one summary per sequence (= directory) and one overall.  Unpaired files and pairs of different
 sizes are listed and make the exit status 1.
+
+--gpu_decode reads the files as bytes and decodes the JPEG ones on the GPU, in batches (jpeg_decode.decode_files: Pillow's
+bytes, so the report is the same value for value); files the decoder does not take -- other formats, progressive or grey
+JPEGs, code streams that do not synchronise -- go through Pillow as without the flag.
 
 --temporal adds the temporal-consistency figures of `test.py --metrics_temporal` (ops.optical_flow_u8 + ops.temporal_metrics):
 within each directory, files that are consecutive in the sorted paired list form the pairs (t-1, t); A = DIR_A is read against
@@ -37,36 +41,59 @@ def pair_files(dir_a, dir_b, pattern="fake_B_*"):
 
 
 MIN_FLOW_SIDE = 8        # ops.optical_flow_u8 refuses smaller frames
+DECODE_BATCH = 32        # pairs per jpeg_decode.decode_files call under --gpu_decode
 
 
-def compare_trees(dir_a, dir_b, pattern="fake_B_*", device="cuda:0", temporal=False):
+def _decoded_pairs(pairs, dir_a, dir_b, device, gpu_decode, fallback):
+    """yield (relative path, a, b): the two RGB images uint8 [H,W,3] of every pair -- host arrays from Pillow, or device
+    tensors from the GPU decoder (`fallback` collects the files Pillow decoded for it)"""
+    import numpy as np
+    if not gpu_decode:
+        from PIL import Image
+        for rel in pairs:
+            with Image.open(os.path.join(dir_a, rel)) as im:
+                a = np.array(im.convert("RGB"))
+            with Image.open(os.path.join(dir_b, rel)) as im:
+                b = np.array(im.convert("RGB"))
+            yield rel, a, b
+        return
+    from . import jpeg_decode
+    for at in range(0, len(pairs), DECODE_BATCH):
+        batch = pairs[at:at + DECODE_BATCH]
+        files = [os.path.join(d, rel) for d in (dir_a, dir_b) for rel in batch]
+        blobs = []
+        for f in files:
+            with open(f, "rb") as fh:
+                blobs.append(fh.read())
+        tensors, fell = jpeg_decode.decode_files(blobs, device)
+        fallback.extend((files[i], reason) for i, reason in fell)
+        for j, rel in enumerate(batch):
+            yield rel, tensors[j], tensors[len(batch) + j]
+
+
+def compare_trees(dir_a, dir_b, pattern="fake_B_*", device="cuda:0", temporal=False, gpu_decode=False, fallback=None):
     """-> the report: {"definition", "overall", "sequences": {dir: summary}, "unpaired_a", "unpaired_b", "size_mismatch"};
     temporal: every summary gains "temporal" (metrics.pool_temporal over the directory's consecutive pairs), the report
-    "temporal_definition" and "temporal_skipped" (second files of pairs that changed size or are narrower than 8 pixels)"""
-    import numpy as np
-    from PIL import Image
+    "temporal_definition" and "temporal_skipped" (second files of pairs that changed size or are narrower than 8 pixels).
+    gpu_decode: decode on the GPU (the same report); `fallback`, a list, receives (file, reason) of what Pillow decoded then"""
     from ._xp import torch
     from . import metrics as M
     from . import ops
     pairs, only_a, only_b = pair_files(dir_a, dir_b, pattern)
     per_seq, mismatch, pending = {}, [], []
     t_pending, t_skipped, last = [], [], None      # last: (directory, device a, device b) of the previous paired file
-    for rel in pairs:
-        with Image.open(os.path.join(dir_a, rel)) as im:
-            a = np.array(im.convert("RGB"))
-        with Image.open(os.path.join(dir_b, rel)) as im:
-            b = np.array(im.convert("RGB"))
-        if a.shape != b.shape:
+    for rel, a, b in _decoded_pairs(pairs, dir_a, dir_b, device, gpu_decode, [] if fallback is None else fallback):
+        if tuple(a.shape) != tuple(b.shape):
             mismatch.append({"file": rel, "a": [a.shape[1], a.shape[0]], "b": [b.shape[1], b.shape[0]]})
             last = None
             continue
-        da, db = torch.from_numpy(a).to(device), torch.from_numpy(b).to(device)
+        da, db = (a, b) if gpu_decode else (torch.from_numpy(a).to(device), torch.from_numpy(b).to(device))
         row = ops.image_metrics(da, db)
         pending.append((rel, 3 * a.shape[0] * a.shape[1], row))
         if temporal:
             seq = os.path.dirname(rel) or "."
             if last is not None and last[0] == seq:
-                if tuple(last[1].shape) != a.shape or min(a.shape[:2]) < MIN_FLOW_SIDE:
+                if tuple(last[1].shape) != tuple(a.shape) or min(a.shape[:2]) < MIN_FLOW_SIDE:
                     t_skipped.append(rel)
                 else:
                     pa, pb = last[1], last[2]
@@ -102,6 +129,7 @@ def main(argv=None):
     ap.add_argument("dir_b")
     ap.add_argument("--pattern", default="fake_B_*", help="shell pattern the files' base names must match")
     ap.add_argument("--temporal", action="store_true", help="add warping error, tOF and the flicker term of consecutive files")
+    ap.add_argument("--gpu_decode", action="store_true", help="decode the JPEG files on the GPU, in batches (the same report)")
     ap.add_argument("--json", default=None, metavar="OUT", help="write the report to this file")
     ap.add_argument("--gpu_ids", default="0")
     args = ap.parse_args(argv)
@@ -111,7 +139,11 @@ def main(argv=None):
     if os.environ.get("T2V_LEAN", "1") != "0":
         from . import _xp
         _xp.use_lean()          # no torch needed for an allocator and a stream (honoured when torch is not loaded yet)
-    rep = compare_trees(args.dir_a, args.dir_b, args.pattern, "cuda:%d" % int(str(args.gpu_ids).split(",")[0]), args.temporal)
+    fallback = []
+    rep = compare_trees(args.dir_a, args.dir_b, args.pattern, "cuda:%d" % int(str(args.gpu_ids).split(",")[0]), args.temporal,
+                        args.gpu_decode, fallback)
+    if fallback:
+        print("--gpu_decode: Pillow decoded %d file(s), the first: %s (%s)" % ((len(fallback),) + fallback[0]), file=sys.stderr)
     for seq, s in list(rep["sequences"].items()) + [("overall", rep["overall"])]:
         print("%-24s %4d frames  psnr %s dB  ssim %s  mae %s" % (seq, s["frames"], _fmt(s["psnr"], ".3f"), _fmt(s["ssim"], ".6f"),
                                                                _fmt(s["mae"], ".4f")))

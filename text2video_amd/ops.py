@@ -782,6 +782,79 @@ def jpeg_encode_u8(images, quality=75, out=None, lengths=None, workspace=None):
     return out, lengths
 
 
+# ----------------------------------------------------------------------------------------------------------------------
+# JPEG decoding (libt2v_jpegdec.so, include/t2v_jpeg_decode.h; the host part: text2video_amd/jpeg.py parse())
+# ----------------------------------------------------------------------------------------------------------------------
+_jpegdec_workspace = {}      # device -> uint8 workspace of t2v_jpegdec_decode_u8 (grown on demand; uses are stream-ordered)
+
+
+def _jpegdec():
+    from . import _jpegdeclib
+    return _jpegdeclib
+
+
+def jpeg_decode_supported(H, W, sampling):
+    """whether jpeg_decode_u8 takes H x W images of this sampling (t2v_jpegdec_supported)"""
+    return bool(_jpegdec().load().t2v_jpegdec_supported(int(H), int(W), int(sampling)))
+
+
+def jpeg_decode_workspace_bytes(H, W, sampling, nimg, scan_capacity):
+    """bytes of workspace jpeg_decode_u8 needs (0: a call it refuses)"""
+    return int(_jpegdec().load().t2v_jpegdec_workspace_bytes(int(H), int(W), int(sampling), int(nimg), int(scan_capacity)))
+
+
+def jpeg_decode_u8(scans, scan_capacity, lengths, tables, H, W, sampling, nimg, dst=None, dst_cs=3, status=None, workspace=None):
+    """Decode nimg JPEG scans of one geometry on the current stream (t2v_jpegdec_decode_u8, include/t2v_jpeg_decode.h).
+    scans, lengths, tables: contiguous device tensors of nimg * scan_capacity, nimg * 4 and nimg * jpeg.TABLE_BYTES bytes
+    (any dtype: byte views of one uploaded buffer are fine): the entropy-coded bytes of every file, their uint32 lengths and
+    the table blobs jpeg.parse() made; sampling is Pillow's `subsampling` number.
+    -> (dst, status): dst a uint8 device tensor [nimg,H,W,dst_cs] (channel 3, if any, 0) holding what Pillow's
+    Image.open(...).convert("RGB") gives, status an int32 device tensor [nimg]: 0, or bits _jpegdeclib.NOT_CONVERGED /
+    CORRUPT for an image whose dst slot is then unspecified.  One memset and eight launches, no host synchronisation; an
+    unsupported geometry or an argument that does not fit raises with nothing launched."""
+    D = _jpegdec()
+    context()
+    H, W, sampling, nimg, cap, dst_cs = int(H), int(W), int(sampling), int(nimg), int(scan_capacity), int(dst_cs)
+    if not jpeg_decode_supported(H, W, sampling):
+        raise ValueError("jpeg_decode_u8: %dx%d, sampling %d is outside %d..%d per dimension, sampling 0..2"
+                         % (H, W, sampling, D.MIN_DIM, D.MAX_DIM))
+    if not 1 <= nimg <= D.MAX_IMAGES:
+        raise ValueError("jpeg_decode_u8: %d images (1..%d per call)" % (nimg, D.MAX_IMAGES))
+    if dst_cs not in (3, 4):
+        raise ValueError("jpeg_decode_u8: dst_cs %d (3 or 4)" % dst_cs)
+
+    def size(t):      # (torch: a property; leantorch: a method)
+        n = t.nbytes
+        return n() if callable(n) else n
+    for t, name, need in ((scans, "scans", nimg * cap), (lengths, "lengths", nimg * 4), (tables, "tables", nimg * D.load().t2v_jpegdec_table_bytes())):
+        if not (t.is_cuda and t.is_contiguous() and size(t) == need):
+            raise ValueError("jpeg_decode_u8: %s must be a contiguous device tensor of %d bytes" % (name, need))
+    dev = scans.device
+    if dst is None:
+        dst = torch.empty(nimg, H, W, dst_cs, dtype=torch.uint8, device=dev)
+    if not (dst.is_cuda and dst.dtype == torch.uint8 and dst.is_contiguous() and tuple(dst.shape) == (nimg, H, W, dst_cs)):
+        raise ValueError("jpeg_decode_u8: dst must be a contiguous uint8 device tensor [%d,%d,%d,%d]" % (nimg, H, W, dst_cs))
+    if status is None:
+        status = torch.empty(nimg, dtype=torch.int32, device=dev)
+    if not (status.is_cuda and status.dtype == torch.int32 and status.is_contiguous() and status.numel() == nimg):
+        raise ValueError("jpeg_decode_u8: status must be a contiguous int32 device tensor [%d]" % nimg)
+    need = jpeg_decode_workspace_bytes(H, W, sampling, nimg, cap)
+    if need == 0:
+        raise ValueError("jpeg_decode_u8: scan_capacity %d (a multiple of 16, 16..2^28)" % cap)
+    if workspace is None:
+        workspace = _jpegdec_workspace.get(str(dev))
+        if workspace is None or workspace.numel() < need:
+            workspace = _jpegdec_workspace[str(dev)] = torch.empty(need, dtype=torch.uint8, device=dev)
+    elif not (workspace.is_cuda and workspace.dtype == torch.uint8 and workspace.is_contiguous()):
+        raise ValueError("jpeg_decode_u8: workspace must be a contiguous uint8 device tensor")
+    if workspace.numel() < need or workspace.data_ptr() % 256:
+        raise ValueError("jpeg_decode_u8: workspace holds %d bytes at an address that is %d mod 256; %d images of %dx%d need "
+                         "%d aligned bytes" % (workspace.numel(), workspace.data_ptr() % 256, nimg, H, W, need))
+    D.check(D.load().t2v_jpegdec_decode_u8(_stream(), _p(scans), cap, _p(lengths), _p(tables), H, W, sampling, nimg, _p(workspace),
+                                           _p(dst), dst_cs, _p(status)), "decode_u8")
+    return dst, status
+
+
 _side_streams = {}      # device -> a stream of the library's own beside the current one (created on first use)
 
 

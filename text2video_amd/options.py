@@ -168,6 +168,13 @@ class TestOptions(BaseOptions):
 class TrainOptions(BaseOptions):
     is_train = True
 
+    def parse(self, argv=None, save=False):
+        opt = super().parse(argv, save)
+        if opt.gpu_decode and not (opt.train_loader == "prefetch" and opt.gpu_resize):
+            self.parser.error("--gpu_decode: the decoder in front of --train_loader prefetch --gpu_resize, which %s not given"
+                              % ("are" if opt.train_loader != "prefetch" and not opt.gpu_resize else "is"))
+        return opt
+
     def extra(self):
         g = self.parser.add_argument
         g("--display_freq", type=int, default=100)
@@ -209,6 +216,9 @@ class TrainOptions(BaseOptions):
         g("--gpu_resize", action="store_true", help="with --train_loader prefetch: the frames' BICUBIC resize, crop and "
           "normalisation run on the GPU in one launch per clip (ops.resample_crop_normalize_u8, Pillow's bytes); a geometry "
           "over the kernel's tap limit is resized on the CPU")
+        g("--gpu_decode", action="store_true", help="with --train_loader prefetch --gpu_resize: the frames' JPEG files are "
+          "decoded on the GPU as well (ops.jpeg_decode_u8, Pillow's bytes): the loader threads read and parse, the compressed "
+          "bytes are uploaded; a file the decoder does not take is decoded by Pillow")
         g("--vgg_weights", type=str, default="", help="torchvision vgg19 state dict (.pth) for the perceptual loss; the "
           "reference lets torchvision download it, which this tree cannot")
         g("--vgg_random_init", action="store_true", help="run the VGG loss path on seeded random weights (timing / tests)")

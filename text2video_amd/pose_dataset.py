@@ -100,6 +100,31 @@ def _decode_frame(path, new_size, box, out):
     out[...] = b
 
 
+def _read_file(path):
+    with open(path, "rb") as fh:
+        return fh.read()
+
+
+def _assemble_jpeg_clip(reads, size, alloc):
+    """--gpu_decode, on a decoder thread behind the clip's reads: the files' bytes parsed and packed into ONE page-locked
+    buffer for the GPU decoder -> ("jpeg", jpeg_decode.Group, blobs).  A clip with a frame jpeg.parse refuses (or of another
+    size or sampling than the first) goes the "raw" way whole: -> ("raw", the frames decoded by Pillow uint8 [T,h,w,3])."""
+    import io
+    from . import jpeg_decode
+    blobs = [f.result() for _, f in reads]
+    groups, refused = jpeg_decode.pack(blobs, alloc)
+    if not refused and len(groups) == 1 and (groups[0].W, groups[0].H) == tuple(size):
+        return "jpeg", groups[0], blobs
+    B = alloc((len(blobs), size[1], size[0], 3))
+    for i, blob in enumerate(blobs):
+        with Image.open(io.BytesIO(blob)) as im:
+            b = np.asarray(im.convert("RGB"))
+        if b.shape != B[i].shape:
+            raise ValueError("%s: decoded to %s, the clip's other frames to %s" % (reads[i][0], b.shape, B[i].shape))
+        B[i] = b
+    return "raw", B, None
+
+
 class PoseDataset:
     def __init__(self, opt):
         self.opt = opt
@@ -450,7 +475,7 @@ class TrainPoseDataset:
             B.append(np.asarray(b.crop(box)))
         return {"A": np.stack(A), "B": np.stack(B), "seq": seq, "start": start, "t_step": step, "params": prm}
 
-    def iter_clips(self, indices, ahead=2, workers=None, gpu_resize=False, alloc=None):
+    def iter_clips(self, indices, ahead=2, workers=None, gpu_resize=False, alloc=None, gpu_decode=False):
         """The clips sample() would return for `indices`, in that order and from the same generator, prepared ahead of
         the consumer.  An entry of `indices` is an index, or (index, n_frames_total) for a clip drawn ahead of an epoch
         boundary at which update_training_batch changes the clip length: it gets the length it would have had.
@@ -463,7 +488,10 @@ class TrainPoseDataset:
 
         Yields sample()'s dict.  gpu_resize: instead of "B" the clip carries "raw", the decoded frames uint8 [T,h,w,3] in
         ONE buffer, and "size" = (w, h); ops.resample_crop_normalize_u8(raw, **params) finishes them on the device.
-        alloc(shape) -> uint8 array: where "A" and "B" / "raw" are assembled (pinned host memory in train.py).
+        gpu_decode (with gpu_resize): the decoder threads read and parse the files instead of decoding them, and the clip
+        carries "jpeg" = (jpeg_decode.Group, the files' bytes) in place of "raw": one page-locked buffer of scans, tables
+        and lengths for ops.jpeg_decode_u8.  A clip with a frame the GPU decoder does not take carries "raw" as before.
+        alloc(shape) -> uint8 array: where "A" and "B" / "raw" / the JPEG buffer are assembled (pinned host memory in train.py).
         workers: rasteriser processes and decoder threads, default --nThreads; 0 rasterises in the pump thread.
         An unreadable file or a dead worker ends the iteration with the file's name; nothing is retried here."""
         import queue
@@ -500,7 +528,9 @@ class TrainPoseDataset:
             prm = get_train_img_params(opt, size, rng)
             (nw, nh), (cw, ch), (cx, cy) = prm["new_size"], prm["crop_size"], prm["crop_pos"]
             box = (cx, cy, cx + cw, cy + ch)
-            B = alloc((n, size[1], size[0], 3)) if gpu_resize else alloc((n, ch, cw, 3))
+            if gpu_decode and not gpu_resize:
+                raise ValueError("iter_clips: gpu_decode needs gpu_resize")
+            B = None if gpu_decode else (alloc((n, size[1], size[0], 3)) if gpu_resize else alloc((n, ch, cw, 3)))
             drop = opt.random_drop_prob
             poses, frames = [], []
             for i in range(n):
@@ -521,7 +551,12 @@ class TrainPoseDataset:
                     poses.append((src, pool.submit(("train", src, size, (nw, nh), box, drop, opt.remove_face_labels,
                                                     opt.basic_point_only, not opt.fast_pose, not opt.no_hand_discs, state))))
                 img = self.img[seq][t]
-                frames.append((img, decoders.submit(_decode_frame, img, None if gpu_resize else (nw, nh), box, B[i])))
+                if gpu_decode:
+                    frames.append((img, decoders.submit(_read_file, img)))
+                else:
+                    frames.append((img, decoders.submit(_decode_frame, img, None if gpu_resize else (nw, nh), box, B[i])))
+            if gpu_decode:      # (queued behind the reads it waits for: the pool takes its jobs in order)
+                B = decoders.submit(_assemble_jpeg_clip, list(frames), size, alloc)
             meta = {"seq": seq, "start": start, "t_step": step, "params": prm}
             if gpu_resize:
                 meta["size"] = size
@@ -559,7 +594,14 @@ class TrainPoseDataset:
                     except Exception as e:      # noqa: BLE001
                         raise RuntimeError("train loader: frame %s: %s: %s" % (path, type(e).__name__, e)) from e
                 meta["A"] = A
-                meta["raw" if gpu_resize else "B"] = B
+                if gpu_decode:
+                    try:
+                        kind, B, blobs = B.result()
+                    except Exception as e:      # noqa: BLE001
+                        raise RuntimeError("train loader: frames of %s: %s: %s" % (frames[0][0], type(e).__name__, e)) from e
+                    meta[kind] = (B, blobs) if kind == "jpeg" else B
+                else:
+                    meta["raw" if gpu_resize else "B"] = B
                 yield meta
         finally:
             stop.set()

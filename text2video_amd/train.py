@@ -1636,6 +1636,10 @@ class _ClipFeeder:
         import threading
         self.opt, self.dev = opt, dev
         self.gpu_resize = bool(getattr(opt, "gpu_resize", False))
+        self.gpu_decode = self.gpu_resize and bool(getattr(opt, "gpu_decode", False))
+        self._jpeg_ws = None                              # the decode calls' workspace (used on the copy stream only)
+        self._jpeg_status = [None, None]                  # slot -> (device int32, pinned int32) of its clip's statuses
+        self.jpeg_clips = self.jpeg_fallback_frames = self.h2d_bytes = 0
         self.copy_stream = torch.cuda.Stream(device=dev)
         self._free = collections.defaultdict(list)      # shape -> pinned tensors not in use
         self._pinned = {}                                 # address of a handed-out array -> its pinned tensor
@@ -1646,7 +1650,7 @@ class _ClipFeeder:
         self._staged = None
         self._held = []                                   # pinned tensors of the clip being consumed
         self._lock = threading.Lock()
-        self._it = ds.iter_clips(schedule, ahead=2, gpu_resize=self.gpu_resize, alloc=self._alloc)
+        self._it = ds.iter_clips(schedule, ahead=2, gpu_resize=self.gpu_resize, alloc=self._alloc, gpu_decode=self.gpu_decode)
 
     def _alloc(self, shape):      # called from the loader's threads
         shape = tuple(int(v) for v in shape)
@@ -1667,7 +1671,30 @@ class _ClipFeeder:
         if d is None:
             d = self._slots[key] = torch.empty(t.shape, dtype=torch.uint8, device=self.dev)
         d.copy_(t, non_blocking=True)
+        self.h2d_bytes += t.numel()
         return t, d
+
+    def _decode(self, clip, slot):
+        """--gpu_decode, on the copy stream: upload the clip's compressed bytes and enqueue the decode call into the slot's
+        raw-frame buffer; the statuses travel back to pinned memory behind it.  -> (pinned buffer, raw frames on the device)"""
+        from . import jpeg_decode, ops as _ops
+        g, _ = clip["jpeg"]
+        pj, dj = self._upload(g.buf, slot, "J")
+        key = (slot, "B", (g.n, g.H, g.W, 3))
+        Bu = self._slots.get(key)
+        if Bu is None:
+            Bu = self._slots[key] = torch.empty(g.n, g.H, g.W, 3, dtype=torch.uint8, device=self.dev)
+        st = self._jpeg_status[slot]
+        if st is None or st[0].numel() != g.n:
+            st = self._jpeg_status[slot] = (torch.empty(g.n, dtype=torch.int32, device=self.dev),
+                                            torch.empty(g.n, dtype=torch.int32, pin_memory=True))
+        need = _ops.jpeg_decode_workspace_bytes(g.H, g.W, g.sampling, g.n, g.capacity)
+        if self._jpeg_ws is None or self._jpeg_ws.numel() < need:
+            self._jpeg_ws = torch.empty(need, dtype=torch.uint8, device=self.dev)
+        jpeg_decode.decode_uploaded(g, dj, 3, dst=Bu, status=st[0], workspace=self._jpeg_ws)
+        st[1].copy_(st[0], non_blocking=True)
+        self.jpeg_clips += 1
+        return pj, Bu
 
     def stage(self):
         """take the next clip from the loader (waits for it if the loader is behind) and start its upload"""
@@ -1682,7 +1709,10 @@ class _ClipFeeder:
             self.copy_stream.wait_event(self._slot_done[slot])
         with torch.cuda.stream(self.copy_stream):
             pa, A = self._upload(clip["A"], slot, "A")
-            pb, Bu = self._upload(clip["raw"] if self.gpu_resize else clip["B"], slot, "B")
+            if "jpeg" in clip:
+                pb, Bu = self._decode(clip, slot)
+            else:
+                pb, Bu = self._upload(clip["raw"] if self.gpu_resize else clip["B"], slot, "B")
             ev = torch.cuda.Event()
             ev.record(self.copy_stream)
         self._staged = (clip, slot, A, Bu, ev, [pa, pb])
@@ -1705,6 +1735,14 @@ class _ClipFeeder:
         if real_all is None:
             real_all = self._real_all[(T_, H, W)] = torch.zeros(T_, H, W, 4, device=self.dev)
         prm = clip["params"]
+        if "jpeg" in clip:
+            # the statuses came with the event the step waits on anyway (the clip was staged a step ago); a frame the
+            # decoder gave up on is decoded by Pillow from the bytes the loader read, before the resample launch
+            from . import jpeg_decode
+            ev.synchronize()
+            for i in self._jpeg_status[slot][1].numpy().nonzero()[0].tolist():
+                Bu[i].copy_(torch.from_numpy(jpeg_decode.pillow_rgb(clip["jpeg"][1][i])))
+                self.jpeg_fallback_frames += 1
         if self.gpu_resize:
             (w, h), (nw, nh) = clip["size"], prm["new_size"]
             if max(_ops.pillow_bicubic_taps(w, nw), _ops.pillow_bicubic_taps(h, nh)) <= _ops.RESAMPLE_MAX_TAPS:
@@ -1715,7 +1753,8 @@ class _ClipFeeder:
                 ev.synchronize()
                 (cx, cy), (cw, ch) = prm["crop_pos"], prm["crop_size"]
                 B = np.stack([np.asarray(Image.fromarray(f).resize((nw, nh), Image.BICUBIC).crop((cx, cy, cx + cw, cy + ch)))
-                              for f in clip["raw"]])
+                              for f in (clip["raw"] if "raw" in clip else
+                                        [jpeg_decode.pillow_rgb(b) for b in clip["jpeg"][1]])])
                 real_all[..., :3] = (torch.from_numpy(B).to(self.dev).float() / 255.0 - 0.5) / 0.5
         else:
             real_all[..., :3] = (Bu.float() / 255.0 - 0.5) / 0.5
