@@ -626,7 +626,7 @@ def pillow_bicubic_taps(in_size, out_size):
     return 1 if in_size == out_size else 2 * math.ceil(2.0 * max(in_size / out_size, 1.0)) + 1
 
 
-RESAMPLE_MAX_TAPS = 33      # T2V_RESAMPLE_MAX_TAPS
+RESAMPLE_MAX_TAPS = _lib.RESAMPLE_MAX_TAPS      # T2V_RESAMPLE_MAX_TAPS (include/t2v.h)
 _resample_tables = {}       # (device, in, out) -> (first, count, coef) on the device
 
 
@@ -894,6 +894,7 @@ def copy_bytes_to_host(dst_pinned, dst_offset, src, src_offset, nbytes, stream=N
                                ctypes.c_void_p(src.data_ptr() + src_offset), nbytes, _lib.COPY_D2H), "memcpy d2h")
 
 
+METRICS_MAX_BOXES, METRICS_MAX_SIDE = _lib.METRICS_MAX_BOXES, _lib.METRICS_MAX_SIDE      # the library's limits (include/t2v.h)
 _metrics_scratch = {}      # device -> float64 scratch of t2v_image_metrics_u8 (grown on demand; uses are stream-ordered)
 METRICS_DEFINITION = ("psnr = 10 log10(255^2 / mse) and mae over the pixels' 3 channels; ssim = mean SSIM index (Wang et al. "
                       "2004: 11x11 Gaussian window, sigma 1.5, K1 0.01, K2 0.03, L 255, per channel on the 8-bit values, "
