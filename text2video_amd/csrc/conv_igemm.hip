@@ -38,7 +38,6 @@ namespace t2v {
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef unsigned int v4u __attribute__((__vector_size__(16)));
 
 template <int MF> struct Mfma;
 template <> struct Mfma<32> {
@@ -80,17 +79,6 @@ using CfgW = TileCfg<32, 2, 2, 3, 1>;  // 192 x 64: all tile rows of a 512x320 f
 using CfgT = TileCfg<32, 1, 4, 5, 1>;  // 160 x 128: the same rows without the padding, 80 accumulator registers: one block per CU
 using CfgT8 = TileCfg<32, 1, 4, 8, 1>; // 256 x 128: a 512x512 frame's 256 tile rows in one tile per position and column, 128
                                        // accumulator registers, 48 KiB stages: one block per CU as well
-
-// One LDS-DMA instruction through buffer addressing: 64 lanes x 16 B -> 1 KiB at the wave-uniform LDS
-// address `lds_dst`; source = base + voff (per lane, bytes) + soff (scalar, bytes).  Lanes with
-// voff >= nbytes are out of range and write zeros.  (Device-only builtins: the host pass of hipcc
-// must not see them, or it silently drops the kernel stubs.)
-__device__ __forceinline__ void dma16(const float* base, int nbytes, char* lds_dst, int voff, int soff) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    const __amdgpu_buffer_rsrc_t srd = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(base), 0, nbytes, 0x00020000);
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(srd, (__attribute__((address_space(3))) void*)lds_dst, 16, voff, soff, 0, 0);
-#endif
-}
 
 // ---- the MFMA waves' K loop, shared by conv_igemm_kernel and wino_gemm_sk_kernel -------------------------------------------
 // One K stage = RQ groups of 4*TM*TN MFMAs, software-pipelined by hand (one wave per SIMD has nobody else to hide its
@@ -497,21 +485,17 @@ __global__ __launch_bounds__(512) void conv_igemm_kernel(const ConvKParams p) {
 // (36 positions x 2 x 8) are 1.125 rounds of the 512 resident blocks (two per CU), and the 2304 64x64 tiles used instead
 // pay twice the LDS-DMA traffic per FLOP.  Here the grid IS the 512 resident blocks: the (tile, K stage) units are laid
 // out tile-major and every block takes an equal run of them -- 36 of 18432 stages for that frame, i.e. the tail of one
-// tile, (whole tiles,) and the head of the next.  The head goes FIRST: its accumulators are written (write-through) to
-// the block's slot of `partial` and a per-wave tag is raised; the block that owns the rest of that tile gets to it LAST
-// and starts its K loop from those accumulators instead of zeros.  Every output is therefore the same K-ordered chain
-// of MFMAs as in conv_igemm_kernel (bit-identical), nobody waits on a block that started after it (the producer of a
-// block's hand-over is block b - 8, dispatched earlier), and whole tiles never touch the scratch.
+// tile, (whole tiles,) and the head of the next.  The head goes FIRST and its accumulators are handed over; the block that
+// owns the rest of that tile gets to it LAST and starts its K loop from them instead of zeros (the hand-over: k_loops.h).
+// Every output is therefore the same K-ordered chain of MFMAs as in conv_igemm_kernel (bit-identical), and whole tiles
+// never touch the scratch.
 // Blocks b, b + 8, ... (one XCD under round-robin dispatch) share a run of whole tiles, m tile fastest: the two blocks
 // on one U column tile run side by side in one L2.
 struct SkKParams {
     const float* a;
     const float* b;
     float* c;
-    float* partial;               // [grid][4 waves][64 regs][64 lanes]
-    unsigned long long* flags;    // [grid][4 waves]
-    unsigned long long tag;       // unique per launch: stale flags of earlier launches never match
-    unsigned* err;                // sticky error word raised by a hand-over that timed out
+    SkHandover h;
     long a_group_stride;
     int T, K, N, c_cs;
     int mtiles_g, ntiles, nk, tiles, tiles_per_xcd, blocks_per_xcd;
@@ -648,31 +632,8 @@ __global__ __launch_bounds__(512) void wino_gemm_sk_kernel(const SkKParams p) {
         // ---- MFMA waves ----
         acc_t acc[Cfg::TM][Cfg::TN];
         if (init) {
-            // the accumulators an earlier block of this XCD left for this tile (block j-1 = blockIdx - 8; block j - half in
-            // the second schedule); its wave `wid` wrote what this wave reads
-            const int src = blockIdx.x - 8 * (hybrid ? half : 1);
-            const unsigned long long* fl = p.flags + src * 4 + wid;
-            // (bounded: 1 s.  The producer ran before this block was even dispatched; if its tag is still missing something
-            // is broken: the tile is then poisoned with NaNs and the host is told through p.err -- no hung GPU, no silent frame)
-            const bool timed_out = handover_wait(fl, p.tag, p.err, lane);
-            // taken: clear it, so that a replay of this very launch (a captured graph re-issues the same tag) starts clean
-            if (lane == 0) __hip_atomic_store(const_cast<unsigned long long*>(fl), 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            // write-through (sc1) stores on the producer's side, sc1 loads here: the pair that is coherent across the
-            // XCDs' L2s inside one launch; 16 x 16 bytes per lane at scalar offsets off one SRD
-            const __amdgpu_buffer_rsrc_t srd = __builtin_amdgcn_make_buffer_rsrc(
-                const_cast<float*>(p.partial) + (size_t)(src * 4 + wid) * PW, 0, PW * 4, 0x00020000);
-#pragma unroll
-            for (int i = 0; i < Cfg::TM; ++i)
-#pragma unroll
-                for (int jj = 0; jj < Cfg::TN; ++jj)
-#pragma unroll
-                    for (int q = 0; q < 4; ++q) {
-                        auto raw = __builtin_amdgcn_raw_buffer_load_b128(srd, lane * 16, ((i * Cfg::TN + jj) * 4 + q) * 1024, 16);
-                        float v[4];
-                        __builtin_memcpy(v, &raw, 16);
-#pragma unroll
-                        for (int e = 0; e < 4; ++e) acc[i][jj][q * 4 + e] = timed_out ? __builtin_nanf("") : v[e];
-                    }
+            // the producer: block j - 1 of this XCD (blockIdx - 8); block j - half in the second schedule
+            handover_fetch<PW>(p.h, blockIdx.x - 8 * (hybrid ? half : 1), wid, lane, acc);
         } else {
 #pragma unroll
             for (int i = 0; i < Cfg::TM; ++i)
@@ -682,31 +643,14 @@ __global__ __launch_bounds__(512) void wino_gemm_sk_kernel(const SkKParams p) {
                     for (int r = 0; r < MM::NREG; ++r) acc[i][jj][r] = 0.f;
         }
         if (flag_due) {
-            // (the head went first: its stores drain while the loaders fetch this tile's first stage)
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the write-through stores have left for memory
-            if (lane == 0)
-                __hip_atomic_store(p.flags + blockIdx.x * 4 + wid, p.tag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            handover_raise(p.h, wid, lane);
             flag_due = false;
         }
         mfma_k_loop<Cfg, RING, BKN>(smem, ke - kb, a_row0, b_row0, g, fsw, acc);
         __syncthreads();   // pairs with the loaders' closing barrier
 
         if (publish) {
-            const __amdgpu_buffer_rsrc_t srd = __builtin_amdgcn_make_buffer_rsrc(
-                p.partial + (size_t)(blockIdx.x * 4 + wid) * PW, 0, PW * 4, 0x00020000);
-#pragma unroll
-            for (int i = 0; i < Cfg::TM; ++i)
-#pragma unroll
-                for (int jj = 0; jj < Cfg::TN; ++jj)
-#pragma unroll
-                    for (int q = 0; q < 4; ++q) {
-                        float v[4];
-#pragma unroll
-                        for (int e = 0; e < 4; ++e) v[e] = acc[i][jj][q * 4 + e];
-                        v4u raw;
-                        __builtin_memcpy(&raw, v, 16);
-                        __builtin_amdgcn_raw_buffer_store_b128(raw, srd, lane * 16, ((i * Cfg::TN + jj) * 4 + q) * 1024, 16);
-                    }
+            handover_publish<PW>(p.h, wid, lane, acc);
             flag_due = true;
         } else {
             // one SRD on the tile's first output row, one per-lane offset (its row group and column), the rest scalar
@@ -727,10 +671,7 @@ __global__ __launch_bounds__(512) void wino_gemm_sk_kernel(const SkKParams p) {
                 }
         }
     }
-    if (flag_due) {   // a run that was nothing but a head
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        if (lane == 0) __hip_atomic_store(p.flags + blockIdx.x * 4 + wid, p.tag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
+    if (flag_due) handover_raise(p.h, wid, lane);   // a run that was nothing but a head
 }
 
 // ---- the same GEMM for tile rows that are no whole 128s: ragged M tiles --------------------------------------------------
@@ -741,17 +682,14 @@ __global__ __launch_bounds__(512) void wino_gemm_sk_kernel(const SkKParams p) {
 // 64 x 64), the ragged one as 1 x 4 waves of (32 r) x 32 -- every wave busy on every k step, no zero rows.  A unit is one K
 // stage of one fragment row; the unit list (group-major, M tile fastest, as above) is cut into equal WEIGHT runs per block, a
 // run boundary rounded to the nearest stage of the tile it falls into (both neighbours compute the same boundary).  A run is
-// at least one full tile long, so a tile is cut at most once: head first / tail last, the accumulator hand-over and its
-// guards are those of wino_gemm_sk_kernel, and every output is still the same K-ordered MFMA chain (bit-identical to the
+// at least one full tile long, so a tile is cut at most once: head first / tail last, the accumulator hand-over is the same
+// (k_loops.h; the producer is block b - 8), and every output is still the same K-ordered MFMA chain (bit-identical to the
 // other forms of the stage: which wave owns an element changes, its sum does not).
 struct SkrKParams {
     const float* a;
     const float* b;
     float* c;
-    float* partial;
-    unsigned long long* flags;
-    unsigned long long tag;
-    unsigned* err;
+    SkHandover h;
     long a_group_stride;
     int Tp;                       // rows per position of a / c (the padded pitch)
     int K, N, c_cs;
@@ -813,24 +751,7 @@ __device__ __forceinline__ void skr_piece(const SkrKParams& p, char* smem, int w
     const int b_row0 = wn * (Cfg::TN * MF) + fr;
     acc_t acc[Cfg::TM][Cfg::TN];
     if (init) {
-        const int src = blockIdx.x - 8;
-        const unsigned long long* fl = p.flags + src * 4 + wid;
-        const bool timed_out = handover_wait(fl, p.tag, p.err, lane);
-        if (lane == 0) __hip_atomic_store(const_cast<unsigned long long*>(fl), 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        const __amdgpu_buffer_rsrc_t srd = __builtin_amdgcn_make_buffer_rsrc(
-            const_cast<float*>(p.partial) + (size_t)(src * 4 + wid) * PW, 0, PW * 4, 0x00020000);
-#pragma unroll
-        for (int i = 0; i < Cfg::TM; ++i)
-#pragma unroll
-            for (int jj = 0; jj < Cfg::TN; ++jj)
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    auto raw = __builtin_amdgcn_raw_buffer_load_b128(srd, lane * 16, ((i * Cfg::TN + jj) * 4 + q) * 1024, 16);
-                    float v[4];
-                    __builtin_memcpy(v, &raw, 16);
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) acc[i][jj][q * 4 + e] = timed_out ? __builtin_nanf("") : v[e];
-                }
+        handover_fetch<PW>(p.h, blockIdx.x - 8, wid, lane, acc);
     } else {
 #pragma unroll
         for (int i = 0; i < Cfg::TM; ++i)
@@ -840,29 +761,13 @@ __device__ __forceinline__ void skr_piece(const SkrKParams& p, char* smem, int w
                 for (int r = 0; r < MM::NREG; ++r) acc[i][jj][r] = 0.f;
     }
     if (flag_due) {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        if (lane == 0) __hip_atomic_store(p.flags + blockIdx.x * 4 + wid, p.tag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        handover_raise(p.h, wid, lane);
         flag_due = false;
     }
     mfma_k_loop<Cfg, RING>(smem, ke - kb, a_row0, b_row0, g, fsw, acc);
     __syncthreads();   // pairs with the loaders' closing barrier
     if (publish) {
-        // (the wave -> element mapping of the hand-over is the tile's own: producer and consumer run the same Cfg)
-        const __amdgpu_buffer_rsrc_t srd =
-            __builtin_amdgcn_make_buffer_rsrc(p.partial + (size_t)(blockIdx.x * 4 + wid) * PW, 0, PW * 4, 0x00020000);
-#pragma unroll
-        for (int i = 0; i < Cfg::TM; ++i)
-#pragma unroll
-            for (int jj = 0; jj < Cfg::TN; ++jj)
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    float v[4];
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) v[e] = acc[i][jj][q * 4 + e];
-                    v4u raw;
-                    __builtin_memcpy(&raw, v, 16);
-                    __builtin_amdgcn_raw_buffer_store_b128(raw, srd, lane * 16, ((i * Cfg::TN + jj) * 4 + q) * 1024, 16);
-                }
+        handover_publish<PW>(p.h, wid, lane, acc);
         flag_due = true;
     } else {
         const __amdgpu_buffer_rsrc_t srd = __builtin_amdgcn_make_buffer_rsrc(
@@ -942,10 +847,7 @@ __global__ __launch_bounds__(512, 4) void wino_gemm_skr_kernel(const SkrKParams 
         else if (frs == 2) skr_piece<CfgR2, RING>(p, smem, wid, lane, is_loader, pg, nt, row0, kb, ke, flag_due);
         else skr_piece<CfgR1, RING>(p, smem, wid, lane, is_loader, pg, nt, row0, kb, ke, flag_due);
     }
-    if (flag_due && !is_loader) {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        if (lane == 0) __hip_atomic_store(p.flags + blockIdx.x * 4 + wid, p.tag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
+    if (flag_due && !is_loader) handover_raise(p.h, wid, lane);
 }
 
 // ---- the ragged form with ONE block per CU: balanced tall tiles ---------------------------------------------------------
@@ -1022,10 +924,7 @@ __global__ __launch_bounds__(512) void wino_gemm_skt_kernel(const SkrKParams p) 
         else if (frs == 4) skr_piece<CfgR4, RING, kSktPW>(p, smem, wid, lane, is_loader, pg, nt, row0, kb, ke, flag_due);
         else skr_piece<CfgR3, RING, kSktPW>(p, smem, wid, lane, is_loader, pg, nt, row0, kb, ke, flag_due);
     }
-    if (flag_due && !is_loader) {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        if (lane == 0) __hip_atomic_store(p.flags + blockIdx.x * 4 + wid, p.tag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
+    if (flag_due && !is_loader) handover_raise(p.h, wid, lane);
 }
 
 int wino_gemm_sk_grid_blocks() {
@@ -1052,7 +951,13 @@ static int lds_optin_bytes() {
 }
 int sk_exclusive_lds(int own_bytes) { return std::max(own_bytes, std::min(kSkExclusiveLds, lds_optin_bytes())); }
 constexpr int kSkMaxGrid = 1024;
-size_t wino_gemm_sk_scratch_floats() { return (size_t)kSkMaxGrid * (4 * 64 * 64 + 4 * 2); }
+// The hand-over scratch: kSkMaxGrid blocks x 4 waves x a 4096-float slot (the one-block-per-CU forms' larger slots, on at most
+// half as many blocks, fit the same area), then the flags, one unsigned long long per block and wave.
+constexpr size_t kSkPartialFloats = (size_t)kSkMaxGrid * 4 * 64 * 64;
+size_t wino_gemm_sk_scratch_floats() { return kSkPartialFloats + (size_t)kSkMaxGrid * 4 * 2; }
+SkHandover sk_handover(float* scratch, unsigned* err) {
+    return {scratch, reinterpret_cast<unsigned long long*>(scratch + kSkPartialFloats), wino_gemm_sk_next_tag(), err};
+}
 
 // tile of the fixed-grid launch: 128 x 128 where the tile rows are whole 128s; 192 x 64 where they are whole 192s (a 512x320
 // frame: 160 tiles padded to 192 -- all rows of a transform position in one tile); 0: no fixed-grid form
@@ -1142,10 +1047,7 @@ int launch_wino_gemm_sk(hipStream_t s, const SkGemm& g) {
     T2V_REQUIRE(wino_gemm_sk_ok(g.groups, g.T, g.K, g.N, g.c_cs, g.rows), "stream-K gemm: shape not supported");
     SkKParams k;
     k.a = g.a; k.b = g.b; k.c = g.c;
-    k.partial = g.scratch;
-    k.flags = reinterpret_cast<unsigned long long*>(g.scratch + (size_t)kSkMaxGrid * 4 * 64 * 64);
-    k.tag = wino_gemm_sk_next_tag();
-    k.err = g.err;
+    k.h = sk_handover(g.scratch, g.err);
     k.a_group_stride = g.a_group_stride;
     k.T = g.T; k.K = g.K; k.N = g.N; k.c_cs = g.c_cs;
     if (g.b_kn) {
@@ -1238,10 +1140,7 @@ int launch_wino_gemm_skt(hipStream_t s, const SkGemm& g, int rows) {
     T2V_REQUIRE(wino_gemm_skt_ok(g.groups, rows, g.T, g.K, g.N, g.c_cs), "tall ragged fixed-grid gemm: shape not supported");
     SkrKParams k;
     k.a = g.a; k.b = g.b; k.c = g.c;
-    k.partial = g.scratch;
-    k.flags = reinterpret_cast<unsigned long long*>(g.scratch + (size_t)kSkMaxGrid * 4 * 64 * 64);
-    k.tag = wino_gemm_sk_next_tag();
-    k.err = g.err;
+    k.h = sk_handover(g.scratch, g.err);
     k.a_group_stride = g.a_group_stride;
     k.Tp = g.T; k.K = g.K; k.N = g.N; k.c_cs = g.c_cs;
     k.F = (rows + 31) / 32;
@@ -1268,10 +1167,7 @@ int launch_wino_gemm_skr(hipStream_t s, const SkGemm& g, int rows) {
     T2V_REQUIRE(wino_gemm_skr_ok(g.groups, rows, g.T, g.K, g.N, g.c_cs), "ragged fixed-grid gemm: shape not supported");
     SkrKParams k;
     k.a = g.a; k.b = g.b; k.c = g.c;
-    k.partial = g.scratch;
-    k.flags = reinterpret_cast<unsigned long long*>(g.scratch + (size_t)kSkMaxGrid * 4 * 64 * 64);
-    k.tag = wino_gemm_sk_next_tag();
-    k.err = g.err;
+    k.h = sk_handover(g.scratch, g.err);
     k.a_group_stride = g.a_group_stride;
     k.Tp = g.T; k.K = g.K; k.N = g.N; k.c_cs = g.c_cs;
     k.F = (rows + 31) / 32;

@@ -29,13 +29,6 @@ namespace t2v {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
-__device__ __forceinline__ void wg_dma16(const float* base, int nbytes, char* lds_dst, int voff, int soff) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    const __amdgpu_buffer_rsrc_t srd = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(base), 0, nbytes, 0x00020000);
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(srd, (__attribute__((address_space(3))) void*)lds_dst, 16, voff, soff, 0, 0);
-#endif
-}
-
 // ---- the MFMA waves' pixel loop, shared by conv_wgrad_kernel and wino_wgrad_sk_kernel ---------------------------------------
 // 2 x 2 waves, each 64 (n) x 64 (c) = 2 x 2 tiles of 32x32.  Software pipeline (one MFMA wave per SIMD has nobody to hide
 // its LDS latency): a stage's PIX/2 pixel pairs run as PIX/8 groups of 4 pairs = 16 MFMAs; the operands of group q+1 are
@@ -194,7 +187,7 @@ __global__ __launch_bounds__(512) void conv_wgrad_kernel(const WgradParams p) {
                     opix = (b * p.Hout + oy) * p.Wout + ox;
                 }
                 const int vy = oky ? (opix * p.Cout_s + (fold_n ? ln : n0 + chunk * 4)) * 4 : kOOB;
-                wg_dma16(p.dy, dy_bytes, sY + (wid * RW + i * 2) * 512, vy, 0);
+                dma16(p.dy, dy_bytes, sY + (wid * RW + i * 2) * 512, vy, 0);
                 // X: gathered through the tap
                 int iy = my * p.stride + ldy, ix = mx * p.stride + ldx;
                 bool okx = ok && c_ok;
@@ -207,7 +200,7 @@ __global__ __launch_bounds__(512) void conv_wgrad_kernel(const WgradParams p) {
                     okx = okx && (unsigned)iy < (unsigned)p.Hin && (unsigned)ix < (unsigned)p.Win;
                 }
                 const int vx = okx ? (((b * p.Hin + iy) * p.Win + ix) * p.Cin_s + lc) * 4 : kOOB;
-                wg_dma16(p.x, x_bytes, sX + (wid * RW + i * 2) * 512, vx, 0);
+                dma16(p.x, x_bytes, sX + (wid * RW + i * 2) * 512, vx, 0);
             }
         };
         // Fast path (every layer of the generator but the folded stems / heads): the GEMM rows are whole stages long, so the
@@ -267,10 +260,10 @@ __global__ __launch_bounds__(512) void conv_wgrad_kernel(const WgradParams p) {
                 const int ix0 = sx * p.stride;
 #pragma unroll
                 for (int i = 0; i < NI; ++i) {
-                    wg_dma16(yb, dy_img_bytes, sY + (wid * RW + i * 2) * 512, inb ? vy_c[i] : kOOB, inb ? soff_y : 0);
+                    dma16(yb, dy_img_bytes, sY + (wid * RW + i * 2) * 512, inb ? vy_c[i] : kOOB, inb ? soff_y : 0);
                     const int ix = ix0 + lx0[i];
                     const int vx = (rowok && c_ok && (unsigned)ix < (unsigned)p.Win) ? (ix * p.Cin_s + lc) * 4 : kOOB;
-                    wg_dma16(xb, x_img_bytes, sX + (wid * RW + i * 2) * 512, vx, soff_x);
+                    dma16(xb, x_img_bytes, sX + (wid * RW + i * 2) * 512, vx, soff_x);
                 }
             };
             loader_k_loop<kWgRing, 2 * NI>(0, nk, issue_fast);
@@ -382,16 +375,12 @@ struct WinoWgradSkParams {
     const float* v;               // [36][Tt][Cin]
     const float* m;               // [36][Tt][Cout]
     float* du;                    // [36][Cout_p][Kp]
-    float* partial;               // [grid][4 waves][64 regs][64 lanes]
-    unsigned long long* flags;    // [grid][4 waves]
-    unsigned long long tag;
-    unsigned* err;                // sticky error word raised by a hand-over that timed out
+    SkHandover h;                 // a cut tile's accumulators, from the block that begins it to the one that finishes it
     int Tt, Cin, Cout, Cout_p, Kp;
     int ntiles, ctiles, nk, tiles, tiles_per_xcd, blocks_per_xcd;
     int rounds;   // > 0: whole rounds of one tile per block + half a round cut in two (wino_gemm_sk_kernel's second schedule)
     int half_round;   // ... 0: whole rounds only (tiles a multiple of the grid: 2304 tiles on one block per CU = 9 rounds)
 };
-typedef unsigned int wg_v4u __attribute__((__vector_size__(16)));
 
 template <int PIX, int RING>
 __global__ __launch_bounds__(512) void wino_wgrad_sk_kernel(const WinoWgradSkParams p) {
@@ -487,8 +476,8 @@ __global__ __launch_bounds__(512) void wino_wgrad_sk_kernel(const WinoWgradSkPar
                 const int so_m = (kt - kb) * PIX * p.Cout * 4, so_x = (kt - kb) * PIX * p.Cin * 4;
 #pragma unroll
                 for (int i = 0; i < NI; ++i) {
-                    wg_dma16(mbase, kOOB, sY + i * 2 * 512, n_ok ? vm[i] : kOOB, so_m);
-                    wg_dma16(xbase, kOOB, sX + i * 2 * 512, c_ok ? vx[i] : kOOB, so_x);
+                    dma16(mbase, kOOB, sY + i * 2 * 512, n_ok ? vm[i] : kOOB, so_m);
+                    dma16(xbase, kOOB, sX + i * 2 * 512, c_ok ? vx[i] : kOOB, so_x);
                 }
             };
             loader_k_loop<RING, LD>(kb, ke, issue_stage);
@@ -500,25 +489,7 @@ __global__ __launch_bounds__(512) void wino_wgrad_sk_kernel(const WinoWgradSkPar
         f32x16 acc[2][2];
         if (init) {
             const int src = blockIdx.x - 8 * (hybrid ? half : 1);
-            const unsigned long long* fl = p.flags + src * 4 + wid;
-            // (bounded, 1 s; on a time-out the tile is poisoned with NaNs and p.err is raised: see wino_gemm_sk_kernel)
-            const bool timed_out = handover_wait(fl, p.tag, p.err, lane);
-            // taken: clear it, so that a replay of this very launch (a captured graph re-issues the same tag) starts clean
-            if (lane == 0) __hip_atomic_store(const_cast<unsigned long long*>(fl), 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            const __amdgpu_buffer_rsrc_t srd = __builtin_amdgcn_make_buffer_rsrc(
-                const_cast<float*>(p.partial) + (size_t)(src * 4 + wid) * 4096, 0, 16384, 0x00020000);
-#pragma unroll
-            for (int i = 0; i < 2; ++i)
-#pragma unroll
-                for (int j = 0; j < 2; ++j)
-#pragma unroll
-                    for (int q = 0; q < 4; ++q) {
-                        auto raw = __builtin_amdgcn_raw_buffer_load_b128(srd, lane * 16, ((i * 2 + j) * 4 + q) * 1024, /*sc1*/ 16);
-                        float v[4];
-                        __builtin_memcpy(v, &raw, 16);
-#pragma unroll
-                        for (int e = 0; e < 4; ++e) acc[i][j][q * 4 + e] = timed_out ? __builtin_nanf("") : v[e];
-                    }
+            handover_fetch<4096>(p.h, src, wid, lane, acc);
         } else {
 #pragma unroll
             for (int i = 0; i < 2; ++i)
@@ -528,30 +499,14 @@ __global__ __launch_bounds__(512) void wino_wgrad_sk_kernel(const WinoWgradSkPar
                     for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
         }
         if (flag_due) {
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            if (lane == 0)
-                __hip_atomic_store(p.flags + blockIdx.x * 4 + wid, p.tag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            handover_raise(p.h, wid, lane);
             flag_due = false;
         }
         wgrad_mfma_loop<PIX, RING>(smem, ke - kb, wn, wc, fi, kk, acc);
         __syncthreads();   // pairs with the loaders' closing barrier
 
         if (publish) {
-            const __amdgpu_buffer_rsrc_t srd = __builtin_amdgcn_make_buffer_rsrc(
-                p.partial + (size_t)(blockIdx.x * 4 + wid) * 4096, 0, 16384, 0x00020000);
-#pragma unroll
-            for (int i = 0; i < 2; ++i)
-#pragma unroll
-                for (int j = 0; j < 2; ++j)
-#pragma unroll
-                    for (int q = 0; q < 4; ++q) {
-                        float v[4];
-#pragma unroll
-                        for (int e = 0; e < 4; ++e) v[e] = acc[i][j][q * 4 + e];
-                        wg_v4u raw;
-                        __builtin_memcpy(&raw, v, 16);
-                        __builtin_amdgcn_raw_buffer_store_b128(raw, srd, lane * 16, ((i * 2 + j) * 4 + q) * 1024, /*sc1*/ 16);
-                    }
+            handover_publish<4096>(p.h, wid, lane, acc);
             flag_due = true;
         } else {
             // D[row n][col c] -> dU[xi][n][c]: one SRD on the tile's first element, one per-lane offset, scalar row steps
@@ -573,10 +528,7 @@ __global__ __launch_bounds__(512) void wino_wgrad_sk_kernel(const WinoWgradSkPar
                 }
         }
     }
-    if (flag_due) {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        if (lane == 0) __hip_atomic_store(p.flags + blockIdx.x * 4 + wid, p.tag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
+    if (flag_due) handover_raise(p.h, wid, lane);
 }
 
 bool wino_wgrad_sk_ok(int Tt, int Cin, int Cout) {
@@ -592,10 +544,7 @@ int launch_wino_wgrad_sk(hipStream_t s, const float* V, const float* Md, float* 
     T2V_REQUIRE(wino_wgrad_sk_ok(Tt, Cin, Cout), "fixed-grid weight gradient: shape not supported");
     WinoWgradSkParams k;
     k.v = V; k.m = Md; k.du = dU;
-    k.partial = scratch;
-    k.flags = reinterpret_cast<unsigned long long*>(scratch + wino_gemm_sk_scratch_floats() - 1024 * 4 * 2);
-    k.tag = wino_gemm_sk_next_tag();
-    k.err = async_error_word();
+    k.h = sk_handover(scratch, async_error_word());
     k.Tt = Tt; k.Cin = Cin; k.Cout = Cout; k.Cout_p = Cout_p; k.Kp = Kp;
     k.ntiles = (Cout + 127) / 128; k.ctiles = (Cin + 127) / 128; k.nk = Tt / 16;
     k.tiles = 36 * k.ntiles * k.ctiles;

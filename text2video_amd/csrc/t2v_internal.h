@@ -321,6 +321,15 @@ struct SkGemm {
     bool b_kn = false;     // b is [groups][K][N] (wino_gemm_sk_bkn_ok): a data gradient reading the forward layer's U in place
 };
 size_t wino_gemm_sk_scratch_floats();
+// the operands of the accumulator hand-over between two blocks of a fixed-grid launch (k_loops.h), as the kernels get them
+struct SkHandover {
+    float* partial;               // [grid][4 waves][PW floats]: a wave's slot, PW = 4096 (64 registers x 64 lanes) or the kernel's own
+    unsigned long long* flags;    // [grid][4 waves]
+    unsigned long long tag;       // unique per launch: stale flags of earlier launches never match
+    unsigned* err;                // sticky error word raised by a hand-over that timed out
+};
+// ... for one launch on `scratch` (wino_gemm_sk_scratch_floats() floats): the buffer's layout, and a fresh tag
+SkHandover sk_handover(float* scratch, unsigned* err);
 bool wino_gemm_sk_ok(int groups, int T, int K, int N, int c_cs, int rows = 0);   // rows: real tile rows per position, if known
 bool wino_gemm_sk_bkn_ok(int groups, int T, int K, int N, int c_cs);
 int wino_gemm_sk_tall_rows(int groups, int rows, int T, int N);      // 160 | 256: the one-block-per-CU form of that kernel is taken; 0: not

@@ -12,6 +12,7 @@
 //                                   polyphase F(4,2) layers, whose split-emitting transforms are in polyphase_split.hip
 // One block per 128 x 128 output tile, nothing shared between blocks: every output is one block's fixed-order chain.
 #include "t2v_internal.h"
+#include "k_loops.h"
 #include "transform_common.h"
 
 namespace t2v {
@@ -103,13 +104,6 @@ constexpr int kBM = 128, kBN = 128, kSBK = 32, kRing = 3;
 constexpr int kStageBytes = 2 * 2 * 64 * 128;      // [plane][A|B][64 LDS rows][128 B] = 32 KiB
 constexpr int kLd = 8;                             // DMA instructions per loader wave and stage
 constexpr int kSplitGemmLds = kRing * kStageBytes; // 96 KiB
-
-__device__ __forceinline__ void dma16(const void* base, unsigned nbytes, char* lds_dst, int voff, int soff) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    const __amdgpu_buffer_rsrc_t srd = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0, nbytes, 0x00020000);
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(srd, (__attribute__((address_space(3))) void*)lds_dst, 16, voff, soff, 0, 0);
-#endif
-}
 
 __global__ __launch_bounds__(512) void wino_split_gemm_kernel(const u16* __restrict__ A, const u16* __restrict__ B,
                                                               float* __restrict__ C, int npos, int Tt, int N, int K,
