@@ -32,7 +32,8 @@ extern "C" {
 #endif
 
 /* (T2V_ALGO_POLYPHASE_BF16X2, t2v_conv_polyphase_bf16x2_supported and t2v_gen_desc.conv_algo 4 came after 22 and left it
- * alone: they add a symbol and values, no existing entry, struct or value changed.) */
+ * alone: they add a symbol and values, no existing entry, struct or value changed.  So did T2V_ALGO_DIRECT_BF16X2 and
+ * t2v_gen_desc.conv_algo 5; the two entry points of that form are declared in t2v_bf16x2.h.) */
 #define T2V_ABI_VERSION 22
 
 typedef enum {
@@ -79,9 +80,16 @@ enum { T2V_ACT_NONE = 0, T2V_ACT_TANH = 1, T2V_ACT_FLOW_W = 2 /* ch0,1: x*20 ; c
  * are POLYPHASE's fp32 arithmetic; V and U hold two bf16 planes in the bytes of the fp32 tensors, so every size is POLYPHASE's.
  * The F(4,2) operands are milder than F(4x4,3x3)'s: the float64 emulation of the form gives 1.7e-5 of the output's rms per
  * conv.  Forward only, where t2v_conv_polyphase_bf16x2_supported() says so; never chosen by t2v_conv_best_algo -- a caller
- * opts in (t2v_gen_desc.conv_algo 4). */
+ * opts in (t2v_gen_desc.conv_algo 4).
+ * DIRECT_BF16X2 = DIRECT for the 3x3 stride-2 conv and the transposed conv, its contraction in the same split-bf16 arithmetic
+ * (SpatialConvolutionMM / SpatialFullDilatedConvolution, THCUNN.h:664,794, as THCUNN's half instantiations ran them).  The input
+ * map and the packed weight hold, in place of every fp32 channel pair, the dwords {hi.x, hi.y | lo.x, lo.y}: every size is
+ * DIRECT's.  Bias and statistics partials are DIRECT's fp32 epilogue on 128 x 128 tiles.  It runs through the
+ * t2v_conv2d_forward_winograd* entries, whose workspace (t2v_conv_winograd_workspace_floats: H*W*Cin floats) receives the split
+ * of x.  Forward only, where t2v_conv_direct_bf16x2_supported of t2v_bf16x2.h says so; never chosen by t2v_conv_best_algo -- a caller opts
+ * in (t2v_gen_desc.conv_algo 5). */
 enum { T2V_ALGO_DIRECT = 0, T2V_ALGO_WINOGRAD = 1, T2V_ALGO_WINOGRAD_F4 = 2, T2V_ALGO_POLYPHASE = 3,
-       T2V_ALGO_WINOGRAD_F4_BF16X2 = 4, T2V_ALGO_POLYPHASE_BF16X2 = 5 };
+       T2V_ALGO_WINOGRAD_F4_BF16X2 = 4, T2V_ALGO_POLYPHASE_BF16X2 = 5, T2V_ALGO_DIRECT_BF16X2 = 6 };
 
 typedef struct t2v_ctx t2v_ctx;
 
@@ -556,7 +564,11 @@ typedef struct {
                          * runs as F(4x4,3x3) and t2v_conv_winograd_bf16x2_supported() accepts as
                          * T2V_ALGO_WINOGRAD_F4_BF16X2 (the reduced-precision mode; workspace sizes are those of 0);
                          * 4 = as 3, and every stride-2 / transposed layer that 0 runs as T2V_ALGO_POLYPHASE and
-                         * t2v_conv_polyphase_bf16x2_supported() accepts as T2V_ALGO_POLYPHASE_BF16X2 (same sizes) */
+                         * t2v_conv_polyphase_bf16x2_supported() accepts as T2V_ALGO_POLYPHASE_BF16X2 (same sizes);
+                         * 5 = as 4, and the stride-2 / transposed layers that 4 leaves T2V_ALGO_DIRECT, where
+                         * t2v_conv_direct_bf16x2_supported of t2v_bf16x2.h accepts them and the class measured faster (both
+                         * channel counts >= 128: the 128 <-> 256 layers), as
+                         * T2V_ALGO_DIRECT_BF16X2 (no size grows; such a layer leaves one statistics partial per 128 pixels) */
 } t2v_gen_desc;
 
 typedef struct {

@@ -17,7 +17,8 @@ Usage: frame_digest.py [--root TREE] [--cases a,b,...] [--sizes_only]
   e: a's generator called directly with want=(out, img_feat, flow_feat)
   f: ngf 16, 2 down layers, 2 blocks, 64x64: no polyphase layer, no lazy chain, implicit-GEMM heads -- nothing is ever pending
   g: c at 192x192: the staggered batch of 3 through a's F(4x4) lazy chains, polyphase layers and one-pass join
-Case a also runs with each frame-path switch set to its other value, and once with arith="bf16x2"."""
+Case a also runs with each frame-path switch set to its other value, once with arith="bf16x2" and once with
+arith_layers="trunk+stride2" on top of it."""
 import argparse
 import ctypes
 import hashlib
@@ -53,7 +54,7 @@ CASES = {
     "f": ([(GeneratorSpec(ngf=16, n_downsample=2, n_blocks=2, no_flow=False, norm="batch"), 6, 1)], 64, 64, 1, "frames"),
 }
 SWITCHES = [{}, {"T2V_CHAIN_LAZY": "0"}, {"T2V_STREAMS": "1"}, {"T2V_STREAMS": "2"}, {"T2V_FINALIZE_DIRECT": "0"},
-            {"T2V_CONV_ALGO": "1"}, {"T2V_CONV_ALGO": "2"}, {"arith": "bf16x2"}]
+            {"T2V_CONV_ALGO": "1"}, {"T2V_CONV_ALGO": "2"}, {"arith": "bf16x2"}, {"arith": "bf16x2", "arith_layers": "trunk+stride2"}]
 
 
 def plan(nets, H, W, nseq, conv_algo):
@@ -87,13 +88,14 @@ _gens = {}      # (spec, seed, T2V_CONV_ALGO, arith) -> HipGenerator: the cases 
 
 
 def generator(spec, seed, arith, dev):
-    pack = (os.environ.get("T2V_CONV_ALGO", "0"), arith)
+    arith, layers = arith      # (arith, arith_layers)
+    pack = (os.environ.get("T2V_CONV_ALGO", "0"), arith, layers)
     if any(k[2:] != pack for k in _gens):      # another algorithm selection: those weights are not needed again
         _gens.clear()
         torch.cuda.empty_cache()
     key = (repr(spec), seed) + pack
     if key not in _gens:
-        _gens[key] = HipGenerator(spec, dev, arith=arith).load_state_dict(synthetic_state_dict(spec, seed, flow_gain=0.1))
+        _gens[key] = HipGenerator(spec, dev, arith=arith, arith_layers=layers).load_state_dict(synthetic_state_dict(spec, seed, flow_gain=0.1))
     return _gens[key]
 
 
@@ -127,16 +129,18 @@ def outputs(nets, H, W, nseq, kind, arith):
 def run(name, switches):
     nets, H, W, nseq, kind = CASES[name]
     env = {k: v for k, v in switches.items() if k.startswith("T2V_")}
-    arith = switches.get("arith", "fp32")
+    arith, layers = switches.get("arith", "fp32"), switches.get("arith_layers", "trunk")
     saved = {k: os.environ.get(k) for k in env}
     os.environ.update(env)
     ops.reload_env()
     try:
-        conv_algo = _lib.CONV_ALGO_BF16X2 if arith == "bf16x2" else int(os.environ.get("T2V_CONV_ALGO", "0"))
+        conv_algo = int(os.environ.get("T2V_CONV_ALGO", "0"))
+        if arith == "bf16x2":
+            conv_algo = _lib.CONV_ALGO_BF16X2_STRIDE2 if layers == "trunk+stride2" else _lib.CONV_ALGO_BF16X2
         line = "%s %s ws=%s layers=%s algos=%s" % ((name, ",".join("%s=%s" % kv for kv in sorted(switches.items())) or "default")
                                                   + plan(nets, H, W, nseq, conv_algo))
         if not args.sizes_only:
-            line += " out=%s" % outputs(nets, H, W, nseq, kind, arith)
+            line += " out=%s" % outputs(nets, H, W, nseq, kind, (arith, layers))
         print(line, flush=True)
     finally:
         for k, v in saved.items():

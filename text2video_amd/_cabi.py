@@ -3,7 +3,8 @@ the one loader of the shared libraries.  Standard library only (the torch-free f
 
 The reader knows a closed vocabulary and raises HeaderError, naming the header and the declaration, on anything else:
   declarations   prototypes, `typedef struct { ... } name;`, `typedef struct name name;` (opaque), `enum { ... };` /
-                 `typedef enum { ... } name;`, `#define NAME <integer>`; include guards, #include and extern "C"
+                 `typedef enum { ... } name;`, `#define NAME <integer>`; include guards, #include and extern "C";
+                 `#include "x.h"` only in a companion header read with base = the Header of x.h, whose types it then uses
   scalars        int, long, float, double, size_t (and void as a return type)
   pointers       `const char*` returned -> c_char_p; a pointer to a struct of the header -> POINTER(that struct);
                  `int*` -> POINTER(c_int); `T**` (a pointer the callee writes a pointer through) -> POINTER(c_void_p);
@@ -33,8 +34,8 @@ class Header:
     (restype, argtypes); fields: struct name -> [(type, field)]; structs: struct name -> ctypes.Structure; constants:
     name -> int.  All in the header's order."""
 
-    def __init__(self, text, name):
-        self.name = name
+    def __init__(self, text, name, base=None):
+        self.name, self.base = name, base
         self.functions, self.signatures, self.fields, self.structs, self.constants, self.opaque = {}, {}, {}, {}, {}, set()
         text = re.sub(r"//[^\n]*", " ", re.sub(r"/\*.*?\*/", " ", text, flags=re.S))
         code = []
@@ -46,6 +47,8 @@ class Header:
             m = re.fullmatch(r"#\s*define\s+(\w+)\s*(.*)", s)
             if m and m.group(2):        # (without a value: an include guard)
                 self.constants[m.group(1)] = self._integer(m.group(2), s)
+            elif base is not None and re.fullmatch(r'#\s*include\s*"%s"' % re.escape(base.name), s):
+                continue
             elif not (m or _DIRECTIVE.fullmatch(s)):
                 self._bad("a preprocessor line outside the vocabulary", s)
         text = "\n".join(code).rstrip()
@@ -123,7 +126,9 @@ class Header:
         tok = re.findall(r"\w+|\S", t)
         core = [x for x in tok if x != "const"]
         base, stars = (core[0] if core else ""), core[1:]
-        if any(x != "*" for x in stars) or not (base in _SCALARS or base in _POINTEES or base in self.structs or base in self.opaque):
+        structs = dict(self.base.structs, **self.structs) if self.base else self.structs
+        opaque = self.opaque | self.base.opaque if self.base else self.opaque
+        if any(x != "*" for x in stars) or not (base in _SCALARS or base in _POINTEES or base in structs or base in opaque):
             self._bad("type `%s` is outside the vocabulary" % t, decl)
         if not stars:
             if base == "void" and returned:
@@ -135,20 +140,21 @@ class Header:
             return POINTER(c_void_p)
         if len(stars) == 1 and base == "char" and returned:
             return c_char_p
-        if len(stars) == 1 and base in self.structs:
-            return POINTER(self.structs[base])
+        if len(stars) == 1 and base in structs:
+            return POINTER(structs[base])
         if len(stars) == 1 and base == "int":
             return POINTER(c_int)
         return c_void_p
 
 
-def read_header(name):
-    """include/<name> of this tree (also for another build of the same ABI, T2V_LIBRARY)"""
+def read_header(name, base=None):
+    """include/<name> of this tree (also for another build of the same ABI, T2V_LIBRARY); base: the Header a companion
+    header includes"""
     path = os.path.join(INCLUDE_DIR, name)
     if not os.path.exists(path):
         raise RuntimeError("header %s not found: the binding reads the C ABI from it" % path)
     with open(path) as f:
-        return Header(f.read(), name)
+        return Header(f.read(), name, base)
 
 
 class Binding:
@@ -159,11 +165,19 @@ class Binding:
         self.header = read_header(header)
         self.signatures, self.abi_version = self.header.signatures, self.header.constants[abi_macro]
         self.prefix = abi_symbol[:-len("_abi_version")]
+        self.companions = []      # headers that declare further entry points of the same library (companion())
         self._lib, self._lock = None, threading.RLock()
 
     def constants(self, prefix):
         """the header's constants that start with `prefix`, without it"""
         return {k[len(prefix):]: v for k, v in self.header.constants.items() if k.startswith(prefix)}
+
+    def companion(self, header):
+        """A header that includes this binding's and declares more entry points of the same library, with its types: they are
+        bound by load() like the main header's; `signatures` stays the main header's."""
+        h = read_header(header, self.header)
+        self.companions.append(h)
+        return h
 
     def load(self):
         """Load the library and bind every declared symbol.  Raises if anything is missing."""
@@ -181,7 +195,8 @@ class Binding:
         if self.first:
             self.first()
         lib = ctypes.CDLL(self.lib_path)
-        for name, (res, args) in self.signatures.items():
+        declared = list(self.signatures.items()) + [kv for h in self.companions for kv in h.signatures.items()]
+        for name, (res, args) in declared:
             fn = getattr(lib, name)  # AttributeError if the symbol is not exported
             fn.restype = res
             fn.argtypes = args

@@ -41,6 +41,8 @@ def _hip_runtime_first():
 _binding = _cabi.bind(LIB_PATH, "t2v.h", "t2v_abi_version", "T2V_ABI_VERSION",
                       "the HIP extension is required (no CPU fallback)", first=_hip_runtime_first)
 SIGNATURES = _binding.signatures      # name -> (restype, argtypes); every symbol include/t2v.h declares, in its order
+# include/t2v_bf16x2.h: the entry points of the split-bf16 direct convolution (T2V_ALGO_DIRECT_BF16X2), same library
+BF16X2_SIGNATURES = _binding.companion("t2v_bf16x2.h").signatures
 load, check = _binding.load, _binding.check
 ConvDesc, GenDesc, Layer, GenIO = (_binding.header.structs[s] for s in ("t2v_conv_desc", "t2v_gen_desc", "t2v_layer", "t2v_gen_io"))
 # every T2V_* constant of the header without the prefix: ABI_VERSION, PAD_*, ACT_*, ALGO_*, MAX_BATCH, COPY_*, VISUALS_*,
@@ -50,6 +52,7 @@ T2V_OK = _binding.header.constants["T2V_OK"]
 # values of t2v_gen_desc.conv_algo, which the header describes in a comment and does not name
 CONV_ALGO_BF16X2 = 3            # the selection of 0 with its F(4x4,3x3) trunk in split-bf16 arithmetic
 CONV_ALGO_BF16X2_STRIDE2 = 4    # 3, and the polyphase stride-2 / transposed layers in split-bf16 as well
+CONV_ALGO_BF16X2_OUTER = 5      # 4, and the stride-2 / transposed layers that stay direct (128 <-> 256) in split-bf16 as well
 
 
 class Context:

@@ -256,7 +256,8 @@ int build_conv_plan(const t2v_conv_desc* d, int x_cs, bool need_stats, ConvPlan*
         const double fillq = (double)nbq / (double)(((nbq + 255) / 256) * 256);
         // (rule against forced tiles, per layer, at 512x320 / 512x680 / 512x512: within 1.3 / 2.8 / 1.0 % of the best forced
         // choice -- profiles/r04_ab_s2_tiles.txt; the forcing switch is gone)
-        const int force = options().conv_tile;
+        // (T2V_ALGO_DIRECT_BF16X2 has the one 128x128 form: conv_igemm_split.hip)
+        const int force = is_direct_split(d->algo) ? 1 : options().conv_tile;
         if (force == 2 || (force != 1 && ((fill < 0.8 && nb < 1024) || (k.nphases > 1 && nb <= 512) || (fillq - fill >= 0.1 && nb < 2048)))) {
             pl.tile = kTileQ;
             conv_tile_dims(pl.tile, &pl.BM, &pl.BN);
@@ -297,6 +298,11 @@ bool winograd_supported(const t2v_conv_desc* d, int x_cs, int algo) {
 }
 // Training is fp32: every backward, weight-gradient and data-gradient entry turns a split-bf16 descriptor away by name
 static bool refuses_split(const t2v_conv_desc* d, const char* entry) {
+    if (d && is_direct_split(d->algo)) {
+        set_error("%s: T2V_ALGO_DIRECT_BF16X2 (algo 6) is a forward-only form; gradients run in fp32 (algo %d)", entry,
+                  T2V_ALGO_DIRECT);
+        return true;
+    }
     if (d && is_poly_split(d->algo)) {
         set_error("%s: T2V_ALGO_POLYPHASE_BF16X2 (algo 5) is a forward-only form; gradients run in fp32 (algo %d)", entry,
                   T2V_ALGO_POLYPHASE);
@@ -564,6 +570,54 @@ static bool poly_form_supported(const t2v_conv_desc* d, int x_cs) {
     return is_poly_split(d->algo) ? polyphase_split_supported(d, x_cs) : polyphase_supported(d, x_cs);
 }
 
+// ---- T2V_ALGO_DIRECT_BF16X2 (conv_igemm_split.hip): the 3x3 stride-2 conv (even map) and the transposed conv
+// (output_padding 1) with zero padding 1 and no activation, whole 32-deep K stages per tap and whole 128-wide N tiles, every
+// operand and the output below the out-of-range marker of the 32-bit buffer offsets
+bool direct_split_supported(const t2v_conv_desc* d, int x_cs) {
+    if (!d || d->kH != 3 || d->kW != 3 || d->stride != 2 || d->pad != 1 || d->pad_mode != T2V_PAD_ZERO || d->act != T2V_ACT_NONE)
+        return false;
+    if (x_cs != d->Cin || d->Cin < 32 || d->Cin % 32 != 0 || d->Cout < 128 || d->Cout % 128 != 0 || d->H < 1 || d->W < 1) return false;
+    if (d->transposed ? d->output_padding != 1 : (d->H % 2 != 0 || d->W % 2 != 0)) return false;
+    const long out_px = d->transposed ? 4L * d->H * d->W : (long)(d->H / 2) * (d->W / 2);
+    // (the largest weight block a phase addresses: 9 taps, 4 for a transposed conv)
+    return (long)d->H * d->W * d->Cin * 4 < 0x7fff0000L && (long)d->Cout * (d->transposed ? 4 : 9) * d->Cin * 4 < 0x7fff0000L &&
+           out_px * d->Cout * 4 < 0x7fff0000L;
+}
+int check_split_library() {
+    const int got = t2v_split_interface();
+    T2V_REQUIRE(got == kSplitInterface, "libt2v_split.so speaks interface 0x%x, libt2v_hip.so 0x%x: the two libraries are not of one build",
+                got, kSplitInterface);
+    return T2V_OK;
+}
+// n floats (n % 4 == 0) into the pair layout; y == x: in place
+int launch_split_pairs(hipStream_t s, const float* x, float* y, long n) {
+    T2V_TRY(check_split_library());
+    T2V_REQUIRE(n > 0 && n % 4 == 0, "split pass: %ld floats (a positive multiple of 4)", n);
+    T2V_HIP_CHECK((hipError_t)t2v_split_launch_pairs(s, x, y, n / 4, capped_grid(n / 4, 256, 4096)));
+    return T2V_OK;
+}
+// p: a kTileL plan of a supported layer (direct_split_supported), x and w in the pair layout
+int launch_conv_igemm_split(hipStream_t s, const ConvKParams& p) {
+    T2V_REQUIRE(p.Cin_s % kBK == 0 && p.Cout % 128 == 0 && p.Cout_s == p.Cout && p.pad_mode == T2V_PAD_ZERO &&
+                    p.act == T2V_ACT_NONE && p.batch <= 1 && p.mtiles == (p.M + 127) / 128 && p.ntiles == p.Cout / 128,
+                "split-bf16 direct conv: plan outside the form (Cin %% 32, Cout %% 128, zero padding, no activation, 128x128 tiles)");
+    T2V_TRY(check_split_library());
+    T2V_HIP_CHECK((hipError_t)t2v_split_launch_conv(s, &p));
+    return T2V_OK;
+}
+int direct_split_forward(hipStream_t s, const t2v_conv_desc* d, const float* x_pairs, const float* w_packed, const float* bias,
+                         float* y, float* stats_partial) {
+    T2V_REQUIRE(d && is_direct_split(d->algo) && direct_split_supported(d, d->Cin),
+                "split-bf16 direct forward: shape not supported (t2v_conv_direct_bf16x2_supported)");
+    ConvPlan pl;
+    T2V_TRY(build_conv_plan(d, d->Cin, stats_partial != nullptr, &pl));
+    T2V_REQUIRE(pl.tile == kTileL, "internal: the split-bf16 direct conv plans 128x128 tiles");
+    ConvKParams k = pl.kp;
+    k.x = x_pairs; k.w = w_packed; k.bias = bias; k.y = y; k.Cout_s = d->Cout; k.stats = stats_partial;
+    k.batch = 1;
+    return launch_conv_igemm_split(s, k);
+}
+
 // stages bit 1 = input transform, 2 = the 81 batched GEMMs, 4 = output transform (bias, statistics partials)
 int polyphase_forward(t2v_ctx* ctx, hipStream_t s, const t2v_conv_desc* d, const float* x, const float* w_packed,
                       const float* bias, float* y, float* stats_partial, float* workspace, int stages,
@@ -707,8 +761,10 @@ size_t t2v_conv_packed_weight_floats(const t2v_conv_desc* d, int x_cs) {
     if (build_conv_plan(d, x_cs, false, &pl) != T2V_OK) return 0;
     if (is_winograd(d->algo)) return winograd_supported(d, x_cs, d->algo) ? (size_t)wino_pos(d->algo) * pl.Cout_p * x_cs : 0;
     if (is_poly(d->algo)) return poly_form_supported(d, x_cs) ? (size_t)81 * pl.Cout_p * x_cs : 0;
+    if (is_direct_split(d->algo) && !direct_split_supported(d, x_cs)) return 0;      // (the bytes of the fp32 packing)
     return pl.wfloats;
 }
+int t2v_conv_direct_bf16x2_supported(const t2v_conv_desc* d, int x_cs) { return direct_split_supported(d, x_cs) ? 1 : 0; }
 int t2v_conv_polyphase_bf16x2_supported(const t2v_conv_desc* d, int x_cs) { return polyphase_split_supported(d, x_cs) ? 1 : 0; }
 int t2v_conv_polyphase_supported(const t2v_conv_desc* d, int x_cs) {
     return (polyphase_supported(d, x_cs) ? 1 : 0) | (polyphase_pays(d, x_cs) ? 2 : 0);
@@ -724,6 +780,8 @@ int t2v_conv_winograd_bf16x2_supported(const t2v_conv_desc* d, int x_cs) {
 int t2v_conv_best_algo(const t2v_conv_desc* d, int x_cs, int cap) { return d ? best_conv_algo(d, x_cs, cap) : T2V_ALGO_DIRECT; }
 
 size_t t2v_conv_winograd_workspace_floats(const t2v_conv_desc* d, int x_cs) {
+    // T2V_ALGO_DIRECT_BF16X2: the input in the pair layout, the bytes of x
+    if (d && is_direct_split(d->algo)) return direct_split_supported(d, x_cs) ? (size_t)d->H * d->W * d->Cin : 0;
     if (d && is_poly(d->algo)) return poly_form_supported(d, x_cs) ? polyphase_workspace_floats(d) : 0;
     if (!d || !winograd_supported(d, x_cs, d->algo)) return 0;
     return winograd_workspace_floats(d);
@@ -731,6 +789,7 @@ size_t t2v_conv_winograd_workspace_floats(const t2v_conv_desc* d, int x_cs) {
 
 size_t t2v_conv_winograd_batch_workspace_floats(const t2v_conv_desc* d, int x_cs, int nimg) {
     if (!d || nimg < 1) return 0;
+    if (is_direct_split(d->algo)) return nimg == 1 ? t2v_conv_winograd_workspace_floats(d, x_cs) : 0;
     if (is_poly(d->algo)) return nimg == 1 && poly_form_supported(d, x_cs) ? polyphase_workspace_floats(d) : 0;
     if (!winograd_supported(d, x_cs, d->algo) || (nimg > 1 && !is_f4(d->algo))) return 0;
     return winograd_workspace_floats(d, nimg);
@@ -742,6 +801,14 @@ size_t t2v_conv_winograd_batch_workspace_floats(const t2v_conv_desc* d, int x_cs
 static int winograd_stages(t2v_ctx* ctx, hipStream_t s, const t2v_conv_desc* d, int nimg, const float* x, int x_cs, long img_stride,
                            const float* w_packed, const float* bias, float* y, int y_cs, float* stats_partial, float* workspace,
                            int stages, const LazyNorm* lazy) {
+    if (is_direct_split(d->algo)) {
+        // stages bit 1 = the split pass of x into the workspace, 2 | 4 (either) = the conv with its epilogue
+        T2V_REQUIRE(direct_split_supported(d, x_cs), "split-bf16 direct forward: shape not supported (t2v_conv_direct_bf16x2_supported)");
+        T2V_REQUIRE(y_cs == d->Cout, "split-bf16 direct forward: output channel storage must equal Cout");
+        T2V_REQUIRE(nimg == 1 && !lazy, "split-bf16 direct forward: one image with an applied norm");
+        if (stages & 1) T2V_TRY(launch_split_pairs(s, x, workspace, (long)d->H * d->W * d->Cin));
+        return (stages & 6) ? direct_split_forward(s, d, workspace, w_packed, bias, y, stats_partial) : T2V_OK;
+    }
     if (is_poly(d->algo)) {
         T2V_REQUIRE(poly_form_supported(d, x_cs), "polyphase forward: shape not supported (t2v_conv_polyphase_supported, "
                                                   "t2v_conv_polyphase_bf16x2_supported)");
@@ -833,11 +900,17 @@ static int pack_weight(t2v_ctx* ctx, void* stream, const t2v_conv_desc* d, int x
         return (d->algo == T2V_ALGO_WINOGRAD_F4 ? launch_winograd4_weight : launch_winograd_weight)(
             s, w_torch_dev, packed_dev, d->Cout, d->Cin, pl.Cout_p, x_cs, adjoint);
     }
+    if (is_direct_split(d->algo))
+        T2V_REQUIRE(direct_split_supported(d, x_cs) && !adjoint, "pack_weight: split-bf16 direct form not supported for this shape");
     if (!d->transposed)
-        return launch_pack_conv_weight(s, w_torch_dev, packed_dev, d->Cout, d->Cin, d->kH, d->kW, x_cs, pl.kp.ph[0].Kp,
-                                       pl.Cout_p, adjoint);
-    T2V_REQUIRE(!adjoint, "pack_weight_adjoint: stride-1 convolutions only (a transposed conv's data gradient reuses its weight)");
-    return launch_pack_convT_weight(s, w_torch_dev, packed_dev, d->Cin, d->Cout, x_cs, pl.Cout_p, d->kH, d->pad);
+        T2V_TRY(launch_pack_conv_weight(s, w_torch_dev, packed_dev, d->Cout, d->Cin, d->kH, d->kW, x_cs, pl.kp.ph[0].Kp,
+                                        pl.Cout_p, adjoint));
+    else {
+        T2V_REQUIRE(!adjoint, "pack_weight_adjoint: stride-1 convolutions only (a transposed conv's data gradient reuses its weight)");
+        T2V_TRY(launch_pack_convT_weight(s, w_torch_dev, packed_dev, d->Cin, d->Cout, x_cs, pl.Cout_p, d->kH, d->pad));
+    }
+    // T2V_ALGO_DIRECT_BF16X2: the fp32 packing, every K pair replaced in place by its two bf16 terms
+    return is_direct_split(d->algo) ? launch_split_pairs(s, packed_dev, packed_dev, (long)pl.wfloats) : T2V_OK;
 }
 int t2v_conv_pack_weight(t2v_ctx* ctx, void* stream, const t2v_conv_desc* d, int x_cs, const float* w_torch_dev,
                          float* packed_dev) {
@@ -1460,6 +1533,13 @@ int t2v_instance_norm_apply(t2v_ctx* ctx, void* stream, const float* x, const fl
 }
 // the batch form, the encoder join and the plain sum of the norm-apply kernels (additive to the ABI): the launches the
 // generator's frames make, callable on their own
+int t2v_instance_norm_apply_bf16x2(t2v_ctx* ctx, void* stream, const float* x, const float* mean_rstd, const float* gamma,
+                                   const float* beta, float* y, long npix, int C, int relu) {
+    T2V_REQUIRE(ctx && x && mean_rstd && y, "instance_norm_apply_bf16x2: null pointer");
+    T2V_REQUIRE(C > 0 && C % 4 == 0 && npix >= 1, "instance_norm_apply_bf16x2: C=%d (a multiple of 4), npix=%ld", C, npix);
+    T2V_REQUIRE((gamma == nullptr) == (beta == nullptr), "instance_norm_apply_bf16x2: gamma and beta must both be given or both NULL");
+    return launch_inorm_apply_split((hipStream_t)stream, x, mean_rstd, gamma, beta, nullptr, y, npix, C, relu);
+}
 int t2v_instance_norm_apply_batch(t2v_ctx* ctx, void* stream, const float* x, const float* mean_rstd, const float* gamma,
                                   const float* beta, const float* res1, const float* res2, float* y, long npix, int C,
                                   int relu, int nimg) {

@@ -50,7 +50,14 @@ bool polyphase_pays(const t2v_conv_desc* d, int x_cs);      // ... and is the fa
 // either arithmetic: the split-bf16 form shares every geometry, layout size and the output transforms
 inline bool is_poly_split(int algo) { return algo == T2V_ALGO_POLYPHASE_BF16X2; }
 inline bool is_poly(int algo) { return algo == T2V_ALGO_POLYPHASE || is_poly_split(algo); }
-inline bool is_bf16x2(int algo) { return is_split(algo) || is_poly_split(algo); }      // the forward-only forms
+// the direct stride-2 / transposed conv in split-bf16 arithmetic (conv_igemm_split.hip): the plan, the packed-weight size and
+// the statistics partials are those of the direct form on 128 x 128 tiles
+inline bool is_direct_split(int algo) { return algo == T2V_ALGO_DIRECT_BF16X2; }
+bool direct_split_supported(const t2v_conv_desc* d, int x_cs);
+// x: the input in the pair layout (an inorm_apply_split pass or launch_split_pairs made it), w_packed: pack_weight's
+int direct_split_forward(hipStream_t s, const t2v_conv_desc* d, const float* x_pairs, const float* w_packed, const float* bias,
+                         float* y, float* stats_partial);
+inline bool is_bf16x2(int algo) { return is_split(algo) || is_poly_split(algo) || is_direct_split(algo); }      // the forward-only forms
 // ... the split-bf16 form (81 GEMMs on wino_split_gemm_kernel) takes the layer
 bool polyphase_split_supported(const t2v_conv_desc* d, int x_cs);
 inline TileGrid poly_tile_grid(const t2v_conv_desc* d) {

@@ -11,6 +11,7 @@
 #include "t2v_internal.h"
 #include "norm_pool.h"
 #include "transform_common.h"
+#include "norm_apply.h"
 
 namespace t2v {
 
@@ -278,31 +279,7 @@ int launch_bn_running_update(hipStream_t s, const float* mean_rstd, float* runni
     return T2V_OK;
 }
 
-// One side of the encoder join, norm(y) + res per float4 (the arithmetic of an inorm_apply pass with relu 0 and one residual)
-__device__ __forceinline__ float4 join_side(const NormJoinSide& s, long im, long n4, int C4, long i, int c4) {
-    const float4* mr = reinterpret_cast<const float4*>(s.mean_rstd) + im * 2 * C4;
-    const float4 a = mr[2 * c4], b = mr[2 * c4 + 1];
-    float4 v = reinterpret_cast<const float4*>(s.y)[im * n4 + i];
-    v.x = norm_scale(v.x, a.x, a.y);
-    v.y = norm_scale(v.y, a.z, a.w);
-    v.z = norm_scale(v.z, b.x, b.y);
-    v.w = norm_scale(v.w, b.z, b.w);
-    if (s.gamma) {
-        const float4 gm = reinterpret_cast<const float4*>(s.gamma)[c4], bt = reinterpret_cast<const float4*>(s.beta)[c4];
-        v.x = norm_affine(v.x, gm.x, bt.x);
-        v.y = norm_affine(v.y, gm.y, bt.y);
-        v.z = norm_affine(v.z, gm.z, bt.z);
-        v.w = norm_affine(v.w, gm.w, bt.w);
-    }
-    const float4 r = reinterpret_cast<const float4*>(s.res)[im * n4 + i];
-    v.x += r.x; v.y += r.y; v.z += r.z; v.w += r.w;
-    return v;
-}
-
-// y = [relu]((x-mean)*rstd*gamma+beta) + res1 + res2 ; float4 over NHWC, C % 4 == 0
-// join.y != null: ... + (norm_j(join.y) + join.res), the second sum formed by itself and added last -- the encoder join
-// d = (norm_b(yb) + rb) + (norm_a(ya) + ra) in ONE pass: what two apply passes (relu 0, one residual each) and add_kernel
-// compute, value by value through the same functions in the same order, without writing and re-reading the two sums
+// (join_side and inorm_apply_body, the pass itself: norm_apply.h)
 __global__ __launch_bounds__(256) void inorm_apply_kernel(const float4* __restrict__ x,
                                                           const float4* __restrict__ mean_rstd,
                                                           const float4* __restrict__ gamma,
@@ -310,57 +287,9 @@ __global__ __launch_bounds__(256) void inorm_apply_kernel(const float4* __restri
                                                           const float4* __restrict__ res1,
                                                           const float4* __restrict__ res2, float4* __restrict__ y,
                                                           long n4, int C4, int relu, const NormJoinSide join) {
-    {   // blockIdx.y = image of a batch: maps n4 float4 apart, (mean, rstd) tables 2*C4 float4 apart
-        const long im = blockIdx.y;
-        x += im * n4;
-        y += im * n4;
-        mean_rstd += im * 2 * C4;
-        if (res1) res1 += im * n4;
-        if (res2) res2 += im * n4;
-    }
-    const long stride = (long)gridDim.x * blockDim.x;
-    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
-        const int c4 = (int)(i % C4);
-        const float4 a = mean_rstd[2 * c4], b = mean_rstd[2 * c4 + 1];  // (m0,r0,m1,r1) (m2,r2,m3,r3)
-        float4 v = x[i];
-        v.x = norm_scale(v.x, a.x, a.y);
-        v.y = norm_scale(v.y, a.z, a.w);
-        v.z = norm_scale(v.z, b.x, b.y);
-        v.w = norm_scale(v.w, b.z, b.w);
-        if (gamma) {
-            const float4 gm = gamma[c4], bt = beta[c4];
-            v.x = norm_affine(v.x, gm.x, bt.x);
-            v.y = norm_affine(v.y, gm.y, bt.y);
-            v.z = norm_affine(v.z, gm.z, bt.z);
-            v.w = norm_affine(v.w, gm.w, bt.w);
-        }
-        if (relu == 1) {          // (one uniform branch per float4, the activation a constant inside it)
-            v.x = norm_act(v.x, 1);
-            v.y = norm_act(v.y, 1);
-            v.z = norm_act(v.z, 1);
-            v.w = norm_act(v.w, 1);
-        } else if (relu == 2) {
-            v.x = norm_act(v.x, 2);
-            v.y = norm_act(v.y, 2);
-            v.z = norm_act(v.z, 2);
-            v.w = norm_act(v.w, 2);
-        }
-        if (res1) {
-            const float4 r = res1[i];
-            v.x += r.x; v.y += r.y; v.z += r.z; v.w += r.w;
-        }
-        if (res2) {
-            const float4 r = res2[i];
-            v.x += r.x; v.y += r.y; v.z += r.z; v.w += r.w;
-        }
-        if (join.y) {
-            const float4 r = join_side(join, blockIdx.y, n4, C4, i, c4);
-            v.x += r.x; v.y += r.y; v.z += r.z; v.w += r.w;
-        }
-        y[i] = v;
-    }
+    y += (long)blockIdx.y * n4;
+    inorm_apply_body(x, mean_rstd, gamma, beta, res1, res2, n4, C4, relu, join, [&](long i, float4 v) { y[i] = v; });
 }
-
 // nimg > 1: a batch of images back to back (x, res1, res2, y npix*C floats apart, mean_rstd 2*C apart), one launch
 int launch_inorm_apply(hipStream_t s, const float* x, const float* mean_rstd, const float* gamma,
                        const float* beta, const float* res1, const float* res2, float* y, long npix, int C,
@@ -372,6 +301,16 @@ int launch_inorm_apply(hipStream_t s, const float* x, const float* mean_rstd, co
                        reinterpret_cast<const float4*>(gamma), reinterpret_cast<const float4*>(beta),
                        reinterpret_cast<const float4*>(res1), reinterpret_cast<const float4*>(res2),
                        reinterpret_cast<float4*>(y), n4, C / 4, relu, NormJoinSide{});
+    T2V_HIP_CHECK(hipGetLastError());
+    return T2V_OK;
+}
+int launch_inorm_apply_split(hipStream_t s, const float* x, const float* mean_rstd, const float* gamma, const float* beta,
+                             const float* res1, float* y, long npix, int C, int relu, int nimg) {
+    T2V_REQUIRE(C % 4 == 0, "inorm_apply (split store): C=%d must be a multiple of 4", C);
+    const long n4 = npix * (C / 4);
+    // (the kernel is libt2v_split.so's: conv_igemm_split.hip)
+    T2V_TRY(check_split_library());
+    T2V_HIP_CHECK((hipError_t)t2v_split_launch_norm_apply(s, x, mean_rstd, gamma, beta, res1, y, n4, C / 4, relu, grid_for(n4, 256), nimg));
     T2V_HIP_CHECK(hipGetLastError());
     return T2V_OK;
 }

@@ -53,17 +53,32 @@ struct LayerSpec {
     }
 };
 
-// conv_algo 3 | 4: the selection of 0 in the opt-in split-bf16 arithmetic, 3 on the trunk, 4 on the stride-2 layers as well
-inline bool split_mode(const t2v_gen_desc& g) { return g.conv_algo == 3 || g.conv_algo == 4; }
+// conv_algo 3 | 4 | 5: the selection of 0 in the opt-in split-bf16 arithmetic, 3 on the trunk, 4 on the polyphase stride-2 layers
+// as well, 5 also on the stride-2 layers that stay direct
+inline bool split_mode(const t2v_gen_desc& g) { return g.conv_algo >= 3 && g.conv_algo <= 5; }
 // a stride-2 / transposed 3x3 layer: polyphase F(4,2) where that is the faster form, with conv_algo 4 in split-bf16 arithmetic
 // where that form takes the layer.  Every class polyphase_pays selects measured faster split than fp32 as a whole conv, ranges
 // apart (scripts/measure_split_bf16_stride2.py, MI355X, profiles/split_bf16_stride2_times.txt): 256->512 @256x256 251.6 -> 192.8 us
 // (the shortest ring run, K = 256), 512->1024 @128x128 221.0 -> 136.9, 1024->512 (transposed) @64x64 214.4 -> 133.2, 512->256
 // (transposed) @128x128 250.2 -> 198.1; 512<->1024 at 512x320 148.9 -> 115.2 / 141.3 -> 111.8, at 512x680 290.1 -> 177.1 /
 // 292.3 -> 185.5: no class is excluded
-int stride2_algo(const t2v_gen_desc& g, const t2v_conv_desc& cd, int x_cs) {
-    if (!(g.conv_algo == 0 || split_mode(g)) || !polyphase_pays(&cd, x_cs)) return T2V_ALGO_DIRECT;
-    return g.conv_algo == 4 && polyphase_split_supported(&cd, x_cs) ? T2V_ALGO_POLYPHASE_BF16X2 : T2V_ALGO_POLYPHASE;
+// conv_algo 5: a layer that stays direct (polyphase_pays says no) runs as T2V_ALGO_DIRECT_BF16X2 where that form takes it AND
+// its class was measured: both channel counts >= 128, i.e. the 128 <-> 256 layers of the ngf-128 generators (and the same
+// class reached from ngf 64 one level down).  Narrower layers that the predicate accepts (64 -> 128: 288 one-per-CU tiles with
+// K = 576 at 384x384, where the fp32 plan takes 64x64 tiles) were not measured and stay fp32.  Every measured class is faster as apply pass + whole conv, ranges apart (scripts/measure_split_bf16_outer.py, MI355X,
+// profiles/split_bf16_outer_times.txt; fp32 -> split, us): 128->256 @512x512 330.5 -> 168.6, 256->128 (transposed) @256x256
+// 317.3 -> 176.8; at 512x320 212.1 -> 113.3 / 211.3 -> 109.2, at 512x680 482.7 -> 240.4 / 438.5 -> 230.9, at 1024x1024
+// 1339.7 -> 693.5 / 1255.0 -> 706.8 (the same layers forced to T2V_ALGO_POLYPHASE_BF16X2: 307.1 / 317.4 @512x512): no measured
+// class is excluded.
+// pairs_ok: the layer's input is a map only this layer reads, so the norm apply pass in front of it may store the pair layout
+// of T2V_ALGO_DIRECT_BF16X2 in place (encoder maps and decoder maps between two layers; a decoder's first layer only behind a
+// ResnetBlock chain, whose output is the branch's own -- without one it reads the encoder sum both branches share)
+int stride2_algo(const t2v_gen_desc& g, const t2v_conv_desc& cd, int x_cs, bool pairs_ok) {
+    if (!(g.conv_algo == 0 || split_mode(g))) return T2V_ALGO_DIRECT;
+    if (!polyphase_pays(&cd, x_cs))
+        return g.conv_algo == 5 && pairs_ok && cd.Cin >= 128 && cd.Cout >= 128 && direct_split_supported(&cd, x_cs) ? T2V_ALGO_DIRECT_BF16X2
+                                                                                                                 : T2V_ALGO_DIRECT;
+    return g.conv_algo >= 4 && polyphase_split_supported(&cd, x_cs) ? T2V_ALGO_POLYPHASE_BF16X2 : T2V_ALGO_POLYPHASE;
 }
 
 // canonical layer list (the order documented in t2v.h)
@@ -75,7 +90,7 @@ void enumerate_layers(const t2v_gen_desc& g, std::vector<LayerSpec>& out) {
         for (int i = 0; i < n; ++i) {
             t2v_conv_desc cd = mk_conv(H >> i, W >> i, G << i, G << (i + 1), 3, 2, 1, T2V_PAD_ZERO, 0);
             // the deep stride-2 layers as polyphase Winograd F(4,2) (polyphase.hip) where that is the faster form
-            cd.algo = stride2_algo(g, cd, G << i);
+            cd.algo = stride2_algo(g, cd, G << i, true);
             out.push_back({cd, G << i, true});
         }
     };
@@ -89,16 +104,16 @@ void enumerate_layers(const t2v_gen_desc& g, std::vector<LayerSpec>& out) {
             cd.algo = T2V_ALGO_WINOGRAD_F4_BF16X2;
         for (int i = 0; i < 2 * count; ++i) out.push_back({cd, C, true});
     };
+    const int nb_enc = g.is_local ? 0 : g.n_blocks - g.n_blocks / 2;
+    const int nb_res = g.is_local ? g.n_blocks : g.n_blocks / 2;
     auto ups = [&]() {
         for (int i = 0; i < n; ++i) {
             const int l = n - i;
             t2v_conv_desc cd = mk_conv(H >> l, W >> l, G << l, G << (l - 1), 3, 2, 1, T2V_PAD_ZERO, 1);
-            cd.algo = stride2_algo(g, cd, G << l);
+            cd.algo = stride2_algo(g, cd, G << l, i > 0 || nb_res > 0);
             out.push_back({cd, G << l, true});
         }
     };
-    const int nb_enc = g.is_local ? 0 : g.n_blocks - g.n_blocks / 2;
-    const int nb_res = g.is_local ? g.n_blocks : g.n_blocks / 2;
     enc(g.input_nc); rbs(nb_enc);
     enc(g.prev_nc);  rbs(nb_enc);
     rbs(nb_res); ups();
@@ -278,23 +293,30 @@ struct Runner {
         return T2V_OK;
     }
     // the apply pass that nobody took over: dst = [relu](norm(src)) + res for `count` images from image `im` on
-    int discharge(const Pending& p, int im, int count, const float* src, float* dst) const {
+    // pairs: dst receives the pair layout a T2V_ALGO_DIRECT_BF16X2 layer reads (the split store of the same pass)
+    int discharge(const Pending& p, int im, int count, const float* src, float* dst, bool pairs = false) const {
         const LayerSpec& L = specs[p.layer];
         T2V_REQUIRE(count == 1 || b.mr_stride == (size_t)2 * L.cd.Cout, "internal: chain scratch layout");
         const NormJoinSide n = join_side(p, im, src);
+        if (pairs) return launch_inorm_apply_split(s, n.y, n.mean_rstd, n.gamma, n.beta, n.res, dst, L.out_px(), L.cd.Cout, p.relu, count);
         return launch_inorm_apply(s, n.y, n.mean_rstd, n.gamma, n.beta, n.res, nullptr, dst, L.out_px(), L.cd.Cout, p.relu, count);
     }
+    // layer l runs as T2V_ALGO_DIRECT_BF16X2: the pass that writes its input stores the pair layout
+    bool reads_pairs(int l) const { return l < (int)specs.size() && is_direct_split(specs[l].cd.algo); }
 
     // conv (+ fused stats) -> finalize of layer `own.layer` for ONE image; y receives the conv output.  `in`: the norm x still
     // owes -- this (polyphase) layer's input transform applies it.  defer: leave y raw and `own` to the next layer (no apply
     // pass: a read and a write of the map less), else y is normalised in place.  Same arithmetic in the same order: the frames
     // are bit-identical to the apply form (T2V_CHAIN_LAZY=0).
-    int conv_norm_one(int im, const float* x, const Pending& in, float* y, const Pending& own, bool defer) {
+    // x_pairs: x is in the pair layout (this layer is T2V_ALGO_DIRECT_BF16X2); y_pairs: the apply pass stores y in it
+    int conv_norm_one(int im, const float* x, const Pending& in, float* y, const Pending& own, bool defer, bool x_pairs, bool y_pairs) {
         const LayerSpec& L = specs[own.layer];
         const t2v_layer& w = layers[own.layer];
         float* stats = stats_of(im);
         if (g.norm_affine) T2V_REQUIRE(w.gamma && w.beta, "layer %d: norm_affine=1 but gamma/beta missing", own.layer);
         const bool poly = is_poly(L.cd.algo);
+        T2V_REQUIRE(x_pairs == is_direct_split(L.cd.algo) && !(defer && y_pairs),
+                    "internal: layer %d: the pair layout goes to the split-bf16 direct layers, from an apply pass", own.layer);
         LazyNorm ln;
         if (in) T2V_TRY(lazy_norm(in, im, poly ? Takes::Polyphase : Takes::Applied, nullptr, &ln));
         ConvPlan pl;
@@ -304,13 +326,15 @@ struct Runner {
             T2V_TRY(winograd_forward(ctx, s, &L.cd, x, w.w, w.bias, y, stats, b.wino[sc], 7));
         } else if (poly) {
             T2V_TRY(polyphase_forward(ctx, s, &L.cd, x, w.w, w.bias, y, stats, b.wino[sc], 7, in ? &ln : nullptr));
+        } else if (is_direct_split(L.cd.algo)) {
+            T2V_TRY(direct_split_forward(s, &L.cd, x, w.w, w.bias, y, stats));
         } else {
             T2V_TRY(build_conv_plan(&L.cd, L.x_cs, true, &pl));
             T2V_TRY(run_conv(ctx, s, pl, x, w.w, w.bias, y, L.cd.Cout, stats));
             plan = &pl;
         }
         T2V_TRY(finalize_norm(s, &L.cd, L.x_cs, stats, 1, g.eps, mr_of(im), fin_of(im), nullptr, plan));
-        return defer ? T2V_OK : discharge(own, im, 1, y, y);
+        return defer ? T2V_OK : discharge(own, im, 1, y, y, y_pairs);
     }
     // the next layer for every image of the batch (one launch sequence per image): y = [relu](norm(conv(x))) + res, or with
     // `defer` the raw conv output and that norm in *owed.  (The images of a lock-step batch as
@@ -319,9 +343,9 @@ struct Runner {
     // 66.8 / 66.7 at 512x680, 92.0 / 92.0 vs 91.8 / 91.7 at 512x512, alternating runs: inside two-stream frames the other
     // stream already fills what a 2.5-blocks-per-CU launch leaves idle.)
     int conv_norm(const Ptrs& x, Pending in, const MutPtrs& y, int relu, const float* res, bool defer = false,
-                  Pending* owed = nullptr) {
+                  Pending* owed = nullptr, bool x_pairs = false, bool y_pairs = false) {
         const Pending own{li, sc, relu, res};
-        for (int im = 0; im < nimg; ++im) T2V_TRY(conv_norm_one(im, x.p[im], in, y.p[im], own, defer));
+        for (int im = 0; im < nimg; ++im) T2V_TRY(conv_norm_one(im, x.p[im], in, y.p[im], own, defer, x_pairs, y_pairs));
         ++li;
         if (owed) *owed = defer ? own : Pending{};
         return T2V_OK;
@@ -369,9 +393,9 @@ struct Runner {
     }
 
     // x + [pad1,conv3,N,ReLU,pad1,conv3,N](x), image by image
-    int resblock(const float* x, float* t, float* y) {
+    int resblock(const float* x, float* t, float* y, bool y_pairs) {
         T2V_TRY(conv_norm(at(x, b.bott), Pending{}, at(t, b.bott), 1, nullptr));
-        return conv_norm(at(t, b.bott), Pending{}, at(y, b.bott), 0, x);
+        return conv_norm(at(t, b.bott), Pending{}, at(y, b.bott), 0, x, false, nullptr, false, y_pairs);
     }
 
     // One F(4x4) Winograd conv of a chain over the whole batch (maps `bott` floats apart), up to and including the
@@ -408,7 +432,8 @@ struct Runner {
     // per conv.  tmp: raw conv1 / conv2 outputs, block outputs (alternating); all hold the batch back to back.
     // defer: the last norm is left to the caller as well (the encoder join applies both encoders' in one pass);
     // v0: V of x, made by share_v()
-    int res_chain_lazy(const float* x, int count, float* tmp[4], const float** out, bool defer, Pending* owed, const float* v0) {
+    int res_chain_lazy(const float* x, int count, float* tmp[4], const float** out, bool defer, Pending* owed, const float* v0,
+                       bool out_pairs) {
         const float* cur = x;
         Pending end;      // what the conv output waiting in tmp[1] owes: its norm + the block input `cur`
         for (int i = 0; i < count; ++i) {
@@ -420,7 +445,7 @@ struct Runner {
         }
         *out = tmp[1];
         *owed = defer ? end : Pending{};
-        return defer ? T2V_OK : discharge(end, 0, nimg, tmp[1], tmp[1]);
+        return defer ? T2V_OK : discharge(end, 0, nimg, tmp[1], tmp[1], out_pairs);
     }
 
     // a chain of `count` blocks starting at layer l takes the lazy form
@@ -435,13 +460,16 @@ struct Runner {
     }
     // chain of `count` resblocks starting from x (never written; the batch back to back, `bott` floats apart); result
     // pointer in *out, the norm it still owes (with `defer`, the lazy chain only) in *owed.  tmp: 4 distinct buffers != x.
-    int res_chain(const float* x, int count, float* tmp[4], const float** out, bool defer, Pending* owed, const float* v0 = nullptr) {
-        if (chain_is_lazy(li, count)) return res_chain_lazy(x, count, tmp, out, defer, owed, v0);
+    // out_pairs: the chain's output (count > 0: a buffer of tmp, read by the decoder's first layer alone) in the pair layout
+    int res_chain(const float* x, int count, float* tmp[4], const float** out, bool defer, Pending* owed, const float* v0 = nullptr,
+                  bool out_pairs = false) {
+        T2V_REQUIRE(!out_pairs || (count > 0 && !defer), "internal: the pair layout is stored by a chain's own closing apply pass");
+        if (chain_is_lazy(li, count)) return res_chain_lazy(x, count, tmp, out, defer, owed, v0, out_pairs);
         T2V_REQUIRE(!defer && !v0, "internal: only the lazy chain leaves its last norm pending / borrows a V");
         const float* cur = x;
         for (int i = 0; i < count; ++i) {
             float* y = (cur == tmp[1]) ? tmp[2] : tmp[1];
-            T2V_TRY(resblock(cur, tmp[0], y));
+            T2V_TRY(resblock(cur, tmp[0], y, out_pairs && i + 1 == count));
             cur = y;
         }
         *out = cur;
@@ -452,11 +480,16 @@ struct Runner {
     // c7,N,R, (d,N,R) x n, RB x nb; defer: as res_chain
     int encoder(const Ptrs& x, float** act, int nb, float* tmp[4], const float** out, bool defer, Pending* owed) {
         const int n = g.is_local ? 1 : g.n_downsample;
-        // (the stem's output feeds the first stride-2 layer only)
-        T2V_TRY(conv_norm(x, Pending{}, at(act[0], b.lvl[0]), 1, nullptr, n > 0 && next_takes_raw(), owed));
-        for (int i = 0; i < n; ++i)
+        // (the stem's output feeds the first stride-2 layer only, act[i] the layer after it only: where that layer is
+        // T2V_ALGO_DIRECT_BF16X2 the apply pass stores the pair layout in place; act[n] goes on in fp32)
+        bool pairs = n > 0 && reads_pairs(li + 1);
+        T2V_TRY(conv_norm(x, Pending{}, at(act[0], b.lvl[0]), 1, nullptr, n > 0 && next_takes_raw(), owed, false, pairs));
+        for (int i = 0; i < n; ++i) {
+            const bool x_pairs = pairs;
+            pairs = i + 1 < n && reads_pairs(li + 1);
             T2V_TRY(conv_norm(at(act[i], b.lvl[i]), *owed, at(act[i + 1], b.lvl[i + 1]), 1, nullptr,
-                              i + 1 < n && next_takes_raw(), owed));
+                              i + 1 < n && next_takes_raw(), owed, x_pairs, pairs));
+        }
         if (nb == 0) {
             T2V_REQUIRE(!defer, "internal: an encoder without blocks ends in an applied norm");
             *out = act[n];
@@ -466,7 +499,9 @@ struct Runner {
     }
 
     // *owed: the norm the last layer left to the head
-    int decoder(const float* x, float** dec, const float** out, Pending* owed) {
+    // x_pairs: x is in the pair layout (decoder_reads_pairs(): the caller's chain stored it so); dec[l], l > 0, is read by the
+    // next layer alone and takes the layout where that layer asks for it; dec[0] goes to the head and export_feat in fp32
+    int decoder(const float* x, float** dec, const float** out, Pending* owed, bool x_pairs) {
         const int n = g.is_local ? 1 : g.n_downsample;
         const float* cur = x;
         size_t cur_stride = b.bott;
@@ -476,7 +511,9 @@ struct Runner {
             float* y = dec[l];
             // (the direct 128 <-> 256 layers load by LDS-DMA with hardware zero padding and take no pending norm: has_norm
             // layers other than polyphase never answer next_takes_raw)
-            T2V_TRY(conv_norm(at(cur, cur_stride), *owed, at(y, b.lvl[l]), 1, nullptr, next_takes_raw(), owed));
+            const bool y_pairs = i + 1 < n && reads_pairs(li + 1);
+            T2V_TRY(conv_norm(at(cur, cur_stride), *owed, at(y, b.lvl[l]), 1, nullptr, next_takes_raw(), owed, x_pairs, y_pairs));
+            x_pairs = y_pairs;
             cur = y;
             cur_stride = b.lvl[l];
         }
@@ -648,14 +685,16 @@ int t2v_generator_forward_batch(t2v_ctx* ctx, void* stream, const t2v_gen_desc* 
         T2V_TRY(fork());
         r2.li = 2 * enc_layers + branch_layers;
         const float *res_flow, *flow_feat;
-        T2V_TRY(r2.res_chain(flow_in, nb_res, tmpB, &res_flow, false, &owed_flow, v0));
-        T2V_TRY(r2.decoder(res_flow, b.decF, &flow_feat, &owed_flow));
+        const bool pairs = r2.reads_pairs(r2.li + 2 * nb_res);      // the decoder's first layer (enumerate_layers: nb_res > 0 then)
+        T2V_TRY(r2.res_chain(flow_in, nb_res, tmpB, &res_flow, false, &owed_flow, v0, pairs));
+        T2V_TRY(r2.decoder(res_flow, b.decF, &flow_feat, &owed_flow, pairs));
         T2V_TRY(r2.head(r2.at(flow_feat, feat), owed_flow, fw));
         T2V_TRY(r2.export_feat(flow_feat, feat, owed_flow, want_flow_feat));
     }
     const float *res_img, *img_feat;
-    T2V_TRY(r.res_chain(img_in, nb_res, tmpA, &res_img, false, &owed_img, v0));
-    T2V_TRY(r.decoder(res_img, b.decI, &img_feat, &owed_img));
+    const bool img_pairs = r.reads_pairs(r.li + 2 * nb_res);
+    T2V_TRY(r.res_chain(img_in, nb_res, tmpA, &res_img, false, &owed_img, v0, img_pairs));
+    T2V_TRY(r.decoder(res_img, b.decI, &img_feat, &owed_img, img_pairs));
     T2V_TRY(r.head(r.at(img_feat, feat), owed_img, raw));
     T2V_TRY(r.export_feat(img_feat, feat, owed_img, want_img_feat));
     if (!d->no_flow) {

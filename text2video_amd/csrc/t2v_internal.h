@@ -4,6 +4,7 @@
 #include <stddef.h>
 #include <stdint.h>
 #include "../../include/t2v.h"
+#include "../../include/t2v_bf16x2.h"
 
 namespace t2v {
 
@@ -303,6 +304,25 @@ enum ConvTile { kTileL = 0 /*128x128, 32x32x2 MFMA*/, kTileS = 1 /*256x16, 16x16
 int conv_tile_for(int Cout);
 void conv_tile_dims(int tile, int* BM, int* BN);
 int launch_conv_igemm(hipStream_t s, const ConvKParams& p, int tile);
+// conv_igemm_split.hip (T2V_ALGO_DIRECT_BF16X2): x and w hold {hi.x, hi.y | lo.x, lo.y} per fp32 channel pair, in place of it;
+// p is a kTileL plan.  launch_split_pairs turns n floats (n % 4 == 0) into that layout, in place where y == x.
+int launch_conv_igemm_split(hipStream_t s, const ConvKParams& p);
+int launch_split_pairs(hipStream_t s, const float* x, float* y, long n);
+}  // namespace t2v
+// ... whose kernels are libt2v_split.so's (conv_igemm_split.hip): its three launches, each returning a hipError_t
+// The interface between the two objects is versioned: kSplitInterface changes with the three launches and with the size of
+// ConvKParams, which one of them takes; libt2v_hip.so compares its own value with the library's before every launch
+// (check_split_library, capi.hip) and refuses a libt2v_split.so of another build by name.
+extern "C" {
+int t2v_split_interface(void);
+int t2v_split_launch_pairs(hipStream_t s, const float* x, float* y, long n4, int grid);
+int t2v_split_launch_conv(hipStream_t s, const t2v::ConvKParams* p);
+int t2v_split_launch_norm_apply(hipStream_t s, const float* x, const float* mean_rstd, const float* gamma, const float* beta,
+                                const float* res1, float* y, long n4, int C4, int relu, int grid, int nimg);
+}
+namespace t2v {
+constexpr int kSplitInterface = (1 << 16) + (int)sizeof(ConvKParams);      // (revision 1)
+int check_split_library();
 
 // The batched Winograd GEMM (36 groups x [T x K] x [K x N]) on a fixed grid of two blocks per CU, each block taking an
 // equal run of K stages out of the tile-major list of (128x128 tile, stage) units: 576 tiles of a 512x512 frame are
@@ -377,6 +397,9 @@ int launch_inorm_finalize(hipStream_t s, const float* stats, int nparts, int mti
 int launch_inorm_apply(hipStream_t s, const float* x, const float* mean_rstd, const float* gamma,
                        const float* beta, const float* res1, const float* res2, float* y, long npix, int C,
                        int relu, int nimg = 1);
+// the same pass (one residual) storing the pair layout of T2V_ALGO_DIRECT_BF16X2 instead of the value; y == x is allowed
+int launch_inorm_apply_split(hipStream_t s, const float* x, const float* mean_rstd, const float* gamma, const float* beta,
+                             const float* res1, float* y, long npix, int C, int relu, int nimg = 1);
 // one side of the encoder join: norm(y) + res, the batch's maps back to back, the (mean, rstd) tables 2*C floats apart
 struct NormJoinSide {
     const float* y = nullptr;

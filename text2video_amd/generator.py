@@ -181,7 +181,7 @@ class HipGenerator:
     Weights are packed lazily per frame geometry: the ResnetBlock convs use Winograd-transformed
     weights wherever the geometry supports it (t2v_generator_layer_desc reports the algorithm)."""
 
-    def __init__(self, spec, device="cuda", conv_algo=None, arith="fp32", arith_layers="trunk"):
+    def __init__(self, spec, device="cuda", conv_algo=None, arith="fp32", arith_layers="trunk", arith_outer=False):
         """arith: "fp32" (default: every kernel in exact fp32) | "bf16x2": the ResnetBlock trunk's F(4x4,3x3) GEMMs in
         split-bf16 arithmetic (t2v_gen_desc.conv_algo 3; inference only).  Measured (DESIGN.md section 0,
         profiles/split_bf16_accuracy.txt): 2.2e-5 of the output's rms per conv against 1.8e-7 for the fp32 pipeline -- the
@@ -190,7 +190,10 @@ class HipGenerator:
         arith_layers (with arith="bf16x2"): "trunk" (default) | "trunk+stride2": also the polyphase stride-2 and transposed
         layers' 81 GEMMs in split-bf16 arithmetic (t2v_gen_desc.conv_algo 4); 1.7e-5 of the output's rms per such conv in the
         float64 emulation of the form.
-        The mode is chosen by these arguments only: conv_algo=3 | 4 without them, or T2V_CONV_ALGO=3 | 4, is refused."""
+        arith_outer (with arith="bf16x2", arith_layers="trunk+stride2"): also the stride-2 and transposed layers that stay direct
+        convolutions (128 <-> 256 channels), as T2V_ALGO_DIRECT_BF16X2 where that form takes the layer
+        (t2v_gen_desc.conv_algo 5); the norm apply pass in front of such a layer stores each value's two bf16 terms in its place.
+        The mode is chosen by these arguments only: conv_algo=3 | 4 | 5 without them, or T2V_CONV_ALGO=3 | 4 | 5, is refused."""
         import os
         if arith not in ARITHS:
             raise ValueError("arith=%r: one of %s" % (arith, ", ".join(ARITHS)))
@@ -198,8 +201,16 @@ class HipGenerator:
             raise ValueError("arith_layers=%r: one of %s" % (arith_layers, ", ".join(ARITH_LAYERS)))
         if arith == "fp32" and arith_layers != "trunk":
             raise ValueError("arith_layers=%r is the scope of arith='bf16x2' (arith='fp32' given)" % (arith_layers,))
+        if arith_outer and not (arith == "bf16x2" and arith_layers == "trunk+stride2"):
+            raise ValueError("arith_outer=True extends arith='bf16x2', arith_layers='trunk+stride2' (arith=%r, arith_layers=%r given)"
+                             % (arith, arith_layers))
         if arith == "bf16x2":
             mode = _lib.CONV_ALGO_BF16X2_STRIDE2 if arith_layers == "trunk+stride2" else _lib.CONV_ALGO_BF16X2
+            if arith_outer:
+                mode = _lib.CONV_ALGO_BF16X2_OUTER
+            elif conv_algo == _lib.CONV_ALGO_BF16X2_OUTER:
+                raise ValueError("conv_algo=5 is the split-bf16 trunk, stride-2 and outer layers: select it with arith='bf16x2', "
+                                 "arith_layers='trunk+stride2', arith_outer=True")
             if conv_algo not in (None, 0, mode):
                 raise ValueError("arith='bf16x2' selects the ResnetBlock algorithm itself (conv_algo=%r given)" % (conv_algo,))
             conv_algo = mode
@@ -208,6 +219,13 @@ class HipGenerator:
         elif conv_algo == _lib.CONV_ALGO_BF16X2_STRIDE2:
             raise ValueError("conv_algo=4 is the split-bf16 trunk and stride-2 layers: select it with arith='bf16x2', "
                              "arith_layers='trunk+stride2'")
+        elif conv_algo == _lib.CONV_ALGO_BF16X2_OUTER:
+            raise ValueError("conv_algo=5 is the split-bf16 trunk, stride-2 and outer layers: select it with arith='bf16x2', "
+                             "arith_layers='trunk+stride2', arith_outer=True")
+        elif conv_algo is None and int(os.environ.get("T2V_CONV_ALGO", "0")) == _lib.CONV_ALGO_BF16X2_OUTER:
+            raise ValueError("T2V_CONV_ALGO=5: the split-bf16 outer layers are selected with arith='bf16x2', "
+                             "arith_layers='trunk+stride2', arith_outer=True (--arith bf16x2 --arith_layers trunk+stride2 "
+                             "--arith_outer), not by the environment; T2V_CONV_ALGO takes 0, 1 or 2")
         elif conv_algo is None and int(os.environ.get("T2V_CONV_ALGO", "0")) == _lib.CONV_ALGO_BF16X2_STRIDE2:
             raise ValueError("T2V_CONV_ALGO=4: the split-bf16 trunk and stride-2 layers are selected with arith='bf16x2', "
                              "arith_layers='trunk+stride2' (--arith bf16x2 --arith_layers trunk+stride2), not by the "
@@ -217,6 +235,7 @@ class HipGenerator:
                              "environment; T2V_CONV_ALGO takes 0, 1 or 2")
         self.arith = arith
         self.arith_layers = arith_layers
+        self.arith_outer = bool(arith_outer)
         self.spec = spec
         self.device = torch.device(device)
         self.ctx = ops.context(self.device)

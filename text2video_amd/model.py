@@ -101,7 +101,8 @@ def create_model(opt, device="cuda:0", marks=None):
             raise FileNotFoundError("%s not found (pass --synthetic_weights SEED to run without a checkpoint)" % path)
         t0 = time.perf_counter()
         nets.append(HipGenerator(spec, device, arith=getattr(opt, "arith", "fp32"),
-                                 arith_layers=getattr(opt, "arith_layers", "trunk")).load_state_dict(sd))
+                                 arith_layers=getattr(opt, "arith_layers", "trunk"),
+                                 arith_outer=bool(getattr(opt, "arith_outer", False))).load_state_dict(sd))
         torch.cuda.synchronize(device)
         marks["weights_to_device_s"] = marks.get("weights_to_device_s", 0.0) + time.perf_counter() - t0
         if getattr(torch, "LAST_UPLOAD", None):

@@ -12,7 +12,7 @@ from ._xp import torch     # the real torch, or leantorch under vid2vid/test.py'
 
 from . import _lib
 from ._lib import (ACT_FLOW_W, ACT_LRELU, ACT_NONE, ACT_TANH, ALGO_DIRECT, ALGO_WINOGRAD,  # noqa: F401
-                   ALGO_POLYPHASE, ALGO_POLYPHASE_BF16X2, ALGO_WINOGRAD_F4, ALGO_WINOGRAD_F4_BF16X2, PAD_REFLECT, PAD_ZERO, VISUALS_FLOW, VISUALS_IMAGE, VISUALS_MAX_PANELS,
+                   ALGO_DIRECT_BF16X2, ALGO_POLYPHASE, ALGO_POLYPHASE_BF16X2, ALGO_WINOGRAD_F4, ALGO_WINOGRAD_F4_BF16X2, PAD_REFLECT, PAD_ZERO, VISUALS_FLOW, VISUALS_IMAGE, VISUALS_MAX_PANELS,
                    VISUALS_UNIT, ConvDesc, check)
 
 _contexts = {}
@@ -104,6 +104,14 @@ def polyphase_bf16x2_supported(desc, x_cs=None):
     return bool(_lib.load().t2v_conv_polyphase_bf16x2_supported(ctypes.byref(desc), x_cs))
 
 
+def direct_bf16x2_supported(desc, x_cs=None):
+    """True when `desc` (a 3x3 stride-2 conv or its transposed counterpart) can run as ALGO_DIRECT_BF16X2: the direct form with
+    its contraction in split-bf16 arithmetic (forward only; the input map and the packed weight then hold, in place of every
+    fp32 channel pair, its two bf16 terms)"""
+    x_cs = round_up(desc.Cin, 4) if x_cs is None else x_cs
+    return bool(_lib.load().t2v_conv_direct_bf16x2_supported(ctypes.byref(desc), x_cs))
+
+
 def polyphase_pays(desc, x_cs=None):
     """... and the library's own rule selects it for this shape (the faster form: both channel counts >= 256)"""
     x_cs = round_up(desc.Cin, 4) if x_cs is None else x_cs
@@ -118,7 +126,8 @@ def best_conv_algo(desc, x_cs=None, cap=0):
 
 def conv2d_auto(x, packed_w, bias, desc, y_cs=None, stats=None, out=None):
     """conv2d or conv2d_winograd, whichever desc.algo (and the weight packing that goes with it) says."""
-    if desc.algo in (ALGO_WINOGRAD, ALGO_WINOGRAD_F4, ALGO_WINOGRAD_F4_BF16X2, ALGO_POLYPHASE, ALGO_POLYPHASE_BF16X2):
+    if desc.algo in (ALGO_WINOGRAD, ALGO_WINOGRAD_F4, ALGO_WINOGRAD_F4_BF16X2, ALGO_POLYPHASE, ALGO_POLYPHASE_BF16X2,
+                     ALGO_DIRECT_BF16X2):
         assert y_cs is None or y_cs == desc.Cout
         return conv2d_winograd(x, packed_w, bias, desc, stats=stats, out=out)
     return conv2d(x, packed_w, bias, desc, y_cs=y_cs, stats=stats, out=out)
@@ -161,6 +170,7 @@ def conv2d_winograd(x, packed_u, bias, desc, stats=None, out=None, workspace=Non
     """3x3 stride-1 reflect-pad-1 conv through Winograd (desc.algo: ALGO_WINOGRAD F(2x2,3x3) | ALGO_WINOGRAD_F4 F(4x4,3x3) |
     ALGO_WINOGRAD_F4_BF16X2, F(4x4,3x3) with split-bf16 GEMMs: V and the packed weight then hold two bf16 planes).
     stages: bit mask 1 = input transform, 2 = batched GEMM, 4 = output transform (all by default).
+    ALGO_DIRECT_BF16X2 (a stride-2 / transposed layer) runs here as well: stage 1 splits x into the workspace, 2 | 4 is the conv.
     keep_v = (wgrad_ws, batch, slot): the input transform lands in that slot of the Winograd-domain weight gradient's workspace
     (backward_weight_winograd_workspace) and stays there for the backward pass (conv2d_backward_weight_winograd_dy)."""
     c = context()
@@ -374,6 +384,18 @@ def instance_norm_apply(x, mean_rstd, gamma=None, beta=None, res1=None, res2=Non
     y = out if out is not None else torch.empty_like(x)
     check(c.lib.t2v_instance_norm_apply(c.handle, _stream(), _p(x), _p(mean_rstd), _p(gamma), _p(beta), _p(res1),
                                         _p(res2), _p(y), npix, C, int(relu)), "instance_norm_apply")
+    return y
+
+
+def instance_norm_apply_bf16x2(x, mean_rstd, gamma=None, beta=None, relu=False, out=None):
+    """instance_norm_apply with the split store (t2v_instance_norm_apply_bf16x2): the result holds, in the 8 bytes of every
+    channel pair, the dwords {hi.x, hi.y | lo.x, lo.y} an ALGO_DIRECT_BF16X2 layer reads; out may be x."""
+    c = context()
+    _chk(x, "x")
+    C = x.shape[-1]
+    y = out if out is not None else torch.empty_like(x)
+    check(c.lib.t2v_instance_norm_apply_bf16x2(c.handle, _stream(), _p(x), _p(mean_rstd), _p(gamma), _p(beta), _p(y),
+                                               x.numel() // C, C, int(relu)), "instance_norm_apply_bf16x2")
     return y
 
 

@@ -26,6 +26,10 @@ def _common(p):
       "that run in split-bf16 arithmetic: trunk (what --arith bf16x2 alone selects): the ResnetBlock convs; trunk+stride2: "
       "also the polyphase stride-2 and transposed layers (the 81 GEMMs of each on the same kernel; the float64 emulation of "
       "one such conv is 1.7e-5 of its output's rms from the exact one)")
+    g("--arith_outer", action="store_true", help="with --arith bf16x2 --arith_layers trunk+stride2: also the stride-2 and "
+      "transposed layers that run as direct convolutions (128 <-> 256 channels), their contraction in the same split-bf16 "
+      "arithmetic where that measured faster; the norm apply pass in front of such a layer stores the two bf16 terms of each "
+      "value in place of it")
     g("--batchSize", type=int, default=1)
     g("--loadSize", type=int, default=512)
     g("--fineSize", type=int, default=512)
@@ -100,6 +104,11 @@ class BaseOptions:
         if opt.arith_layers is not None and opt.arith != "bf16x2":
             self.parser.error("--arith_layers %s: the scope of --arith bf16x2, which is not given" % opt.arith_layers)
         opt.arith_layers = opt.arith_layers or "trunk"
+        if opt.arith_outer and not (opt.arith == "bf16x2" and opt.arith_layers == "trunk+stride2"):
+            self.parser.error("--arith_outer: on top of --arith bf16x2 --arith_layers trunk+stride2, which %s not given"
+                              % ("are" if opt.arith != "bf16x2" else "is"))
+        if opt.arith_outer and self.is_train:
+            self.parser.error("--arith_outer: a forward-only form of --arith bf16x2; training computes in fp32")
         if unknown:
             print("warning: ignoring unknown options %s" % unknown, file=sys.stderr)
         opt.isTrain = self.is_train

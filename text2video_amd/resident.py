@@ -176,7 +176,7 @@ class _Pipe:
 
 def model_key(opt):
     """what decides whether a resident model can serve a request: the checkpoint files (path, size, mtime) or the synthetic
-    seed, the architecture flags and the arithmetic (--arith and its scope, --arith_layers)"""
+    seed, the architecture flags and the arithmetic (--arith and its scope, --arith_layers and --arith_outer)"""
     files = []
     for s in range(opt.n_scales_spatial):
         p = os.path.abspath(os.path.join(opt.checkpoints_dir, opt.name, "%s_net_G%d.pth" % (opt.which_epoch, s)))
@@ -188,7 +188,8 @@ def model_key(opt):
     return json.dumps([files, opt.synthetic_weights, opt.ngf, opt.n_blocks, opt.n_blocks_local, opt.n_downsample_G,
                        opt.n_frames_G, opt.input_nc, opt.label_nc, opt.output_nc, opt.norm, bool(opt.no_flow),
                        bool(getattr(opt, "no_flow_explicit", False)), opt.n_scales_spatial, bool(opt.no_first_img), str(opt.gpu_ids),
-                       getattr(opt, "arith", "fp32"), getattr(opt, "arith_layers", "trunk")])
+                       getattr(opt, "arith", "fp32"), getattr(opt, "arith_layers", "trunk"),
+                       bool(getattr(opt, "arith_outer", False))])
 
 
 def serve(path, idle_s):
