@@ -11,16 +11,10 @@
 #include <stdlib.h>
 
 #include "t2v_internal.h"
+#include "k_loops.h"
 #include "transform_common.h"
 
 namespace t2v {
-
-__device__ __forceinline__ void hd_dma16(const float* base, int nbytes, char* lds_dst, int voff, int soff) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    const __amdgpu_buffer_rsrc_t srd = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(base), 0, nbytes, 0x00020000);
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(srd, (__attribute__((address_space(3))) void*)lds_dst, 16, voff, soff, 0, 0);
-#endif
-}
 
 constexpr int kHdTile = 16;                 // 16 x 16 output pixels per block
 constexpr int kHdHalo = kHdTile + 6;        // 22
@@ -44,15 +38,10 @@ __global__ __launch_bounds__(256) void conv_head7x7_strip_kernel(const HeadParam
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int cin_s = CIN ? CIN : p.Cin_s;
-    int tile;
-    {   // block b runs on XCD b % 8: every XCD gets a contiguous band of tile rows, so that the halo overlap of neighbouring
-        // tiles (22x22 fetched per 16x16 outputs = 1.9x) is served by that XCD's own L2 (measured on the first form of this
-        // kernel: 457 vs 315 us without)
-        const int nb = gridDim.x, b = blockIdx.x;
-        const int xcd = b & 7, idx = b >> 3;
-        const int q = nb >> 3, r = nb & 7;
-        tile = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-    }
+    // block b runs on XCD b % 8: every XCD gets a contiguous band of tile rows, so that the halo overlap of neighbouring
+    // tiles (22x22 fetched per 16x16 outputs = 1.9x) is served by that XCD's own L2 (measured on the first form of this
+    // kernel: 457 vs 315 us without)
+    const int tile = xcd_band(blockIdx.x, gridDim.x);
     const int tiles_x = (p.W + kHdTile - 1) / kHdTile;
     const int x0 = (tile % tiles_x) * kHdTile, y0 = (tile / tiles_x) * kHdTile;
     int voff[8];
@@ -94,7 +83,7 @@ __global__ __launch_bounds__(256) void conv_head7x7_strip_kernel(const HeadParam
     // four waves' halo pieces are the four quarters of one 64-byte segment per pixel
     auto stage = [&](int c) {
 #pragma unroll
-        for (int i = 0; i < 8; ++i) hd_dma16(p.x, x_bytes, plane + i * 1024, voff[i], c * 4);
+        for (int i = 0; i < 8; ++i) dma16(p.x, x_bytes, plane + i * 1024, voff[i], c * 4);
     };
     for (int c0 = wave * 4; c0 < cin_s; c0 += 16) {
         // (issuing the next pass's DMA under the last two phases of this one -- the plane is dead once the last halo row is in

@@ -207,13 +207,7 @@ __global__ __launch_bounds__(512) void conv_igemm_kernel(const ConvKParams p) {
     // each XCD's L2 sees a contiguous run of tiles sharing A rows / all B columns.
     const int tiles_per_phase = p.mtiles * p.ntiles;
     const int phase = blockIdx.x / tiles_per_phase;
-    int rem;
-    {
-        const int nb = tiles_per_phase, b = blockIdx.x - phase * tiles_per_phase;
-        const int xcd = b & 7, idx = b >> 3;
-        const int q = nb >> 3, r = nb & 7;
-        rem = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-    }
+    const int rem = xcd_band(blockIdx.x - phase * tiles_per_phase, tiles_per_phase);
     const int mt = rem / p.ntiles;
     const int nt = rem - mt * p.ntiles;
     const int m0 = mt * BM, n0 = nt * BN;
@@ -1027,14 +1021,10 @@ unsigned long long wino_gemm_sk_next_tag() {
 
 template <class Cfg, int RING = 2, bool BKN = false>
 static int launch_sk(hipStream_t s, const SkKParams& k, int grid) {
-    auto kern = wino_gemm_sk_kernel<Cfg, RING, BKN>;
+    constexpr auto kern = wino_gemm_sk_kernel<Cfg, RING, BKN>;
     constexpr int LDS_BYTES = RING * Cfg::STAGE_BYTES;
     static const int LDS_MAX = sk_exclusive_lds(LDS_BYTES);
-    static bool attr_done = false;   // per instantiation
-    if (!attr_done) {
-        T2V_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_MAX));
-        attr_done = true;
-    }
+    T2V_HIP_CHECK(optin_dynamic_lds<kern>(LDS_MAX));
     // a two-per-CU form launched on ONE block per CU (sk_launch_blocks under overlap hint 2) keeps its CU's second GEMM slot
     // shut as well (conv_wgrad.hip: launch_wino_wgrad_sk)
     const bool exclusive = RING == 2 && grid < wino_gemm_sk_grid_blocks();
@@ -1151,13 +1141,9 @@ int launch_wino_gemm_skt(hipStream_t s, const SkGemm& g, int rows) {
     k.cg_per_xcd = (k.cgs + 7) / 8;
     const long Wx = (long)k.cg_per_xcd * k.F * k.nk;
     k.S = (int)std::max<long>((long)(k.mt_base + (k.mt_extra ? 1 : 0)) * k.nk, (Wx + k.blocks_per_xcd - 1) / k.blocks_per_xcd);
-    auto kern = wino_gemm_skt_kernel<3>;
+    constexpr auto kern = wino_gemm_skt_kernel<3>;
     constexpr int LDS_BYTES = 3 * CfgR6::STAGE_BYTES;
-    static bool attr_done = false;
-    if (!attr_done) {
-        T2V_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES));
-        attr_done = true;
-    }
+    T2V_HIP_CHECK(optin_dynamic_lds<kern>(LDS_BYTES));
     hipLaunchKernelGGL(kern, dim3(grid), dim3(512), LDS_BYTES, s, k);
     T2V_HIP_CHECK(hipGetLastError());
     return T2V_OK;
@@ -1175,13 +1161,9 @@ int launch_wino_gemm_skr(hipStream_t s, const SkGemm& g, int rows) {
     const int grid = wino_gemm_sk_grid_blocks();
     k.blocks_per_xcd = grid / 8;
     k.S = (int)skr_run_units(g.groups, rows, g.K, g.N, &k.cg_per_xcd);
-    auto kern = wino_gemm_skr_kernel<2>;
+    constexpr auto kern = wino_gemm_skr_kernel<2>;
     constexpr int LDS_BYTES = 2 * CfgL::STAGE_BYTES;
-    static bool attr_done = false;
-    if (!attr_done) {
-        T2V_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES));
-        attr_done = true;
-    }
+    T2V_HIP_CHECK(optin_dynamic_lds<kern>(LDS_BYTES));
     hipLaunchKernelGGL(kern, dim3(grid), dim3(512), LDS_BYTES, s, k);
     T2V_HIP_CHECK(hipGetLastError());
     return T2V_OK;
@@ -1203,14 +1185,9 @@ void conv_tile_dims(int tile, int* BM, int* BN) {
 
 template <class Cfg, int MODE, bool STATS, bool REFLECT, int RING>
 static int launch_ring(hipStream_t s, const ConvKParams& p) {
-    auto kern = conv_igemm_kernel<Cfg, MODE, STATS, REFLECT, RING>;
+    constexpr auto kern = conv_igemm_kernel<Cfg, MODE, STATS, REFLECT, RING>;
     constexpr int LDS_BYTES = RING * Cfg::STAGE_BYTES;
-    static bool attr_done = false;  // per instantiation
-    if (!attr_done) {
-        T2V_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES));
-        attr_done = true;
-    }
+    T2V_HIP_CHECK(optin_dynamic_lds<kern>(LDS_BYTES));
     const int nblocks = p.mtiles * p.ntiles * p.nphases;
     hipLaunchKernelGGL(kern, dim3(nblocks, p.batch > 1 ? p.batch : 1), dim3(512), LDS_BYTES, s, p);
     T2V_HIP_CHECK(hipGetLastError());

@@ -8,6 +8,9 @@
 // XCD-aware tile walk are conv_igemm_kernel's, and no workspace grows.  A 16-byte LDS slot holds four channels as
 // [hi01 lo01 hi23 lo23]; an MFMA operand (8 bf16 = 8 k per lane) is the hi -- or the lo -- dwords of two slots, chosen, not
 // shuffled.  The k order inside a 32-deep stage is permuted identically for A and B.
+// Shared text: the loader waves' K loop (loader_k_loop), xcd_band, dma16 and the dynamic-LDS opt-in are k_loops.h's, the split
+// stores transform_common.h's.  The loader geometry and the epilogue are copies of conv_igemm_kernel's, and the MFMA waves' loop
+// is wino_split_gemm_kernel's written out again: shared, together with the loader loop, it cost that kernel 0.4 % (see there).
 //   split_pairs_kernel        : fp32 -> the pair layout (the single-layer entry's input pass; the packed weights, in place)
 //   conv_igemm_split_kernel   : 128 x 128 output tile per block, 4 MFMA waves (64 x 64 each) + 4 loader waves, a ring of three
 //                               32 KiB stages: one block per CU (64 accumulator + 64 fragment registers per lane), as
@@ -18,8 +21,6 @@
 // The kernels of this opt-in form are a library of their own, libt2v_split.so, which libt2v_hip.so loads as a dependency: what
 // it exports are the three launches at the end of this file, which report a hipError_t; arguments are checked by their callers
 // in libt2v_hip.so (capi.hip: launch_conv_igemm_split, launch_split_pairs; elementwise.hip: launch_inorm_apply_split).
-#include <atomic>
-
 #include "t2v_internal.h"
 #include "k_loops.h"
 #include "transform_common.h"
@@ -34,11 +35,7 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 __global__ __launch_bounds__(256) void split_pairs_kernel(const float4* x, uint4* y, long n4) {   // (y == x allowed)
     const long stride = (long)gridDim.x * blockDim.x;
-    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
-        const float4 v = x[i];
-        const SplitPair a = split_bf16x2(make_float2(v.x, v.y)), b = split_bf16x2(make_float2(v.z, v.w));
-        y[i] = make_uint4(a.hi, a.lo, b.hi, b.lo);
-    }
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) store_split_quad(y, i, x[i]);
 }
 
 // the same pass with the split store: y receives {hi.x, hi.y | lo.x, lo.y} per channel pair; y == x is
@@ -49,10 +46,8 @@ __global__ __launch_bounds__(256) void inorm_apply_split_kernel(const float4* x,
                                                                 const float4* __restrict__ res1, uint4* y, long n4, int C4,
                                                                 int relu) {
     y += (long)blockIdx.y * n4;
-    inorm_apply_body(x, mean_rstd, gamma, beta, res1, nullptr, n4, C4, relu, NormJoinSide{}, [&](long i, float4 v) {
-        const SplitPair a = split_bf16x2(make_float2(v.x, v.y)), b = split_bf16x2(make_float2(v.z, v.w));
-        y[i] = make_uint4(a.hi, a.lo, b.hi, b.lo);
-    });
+    inorm_apply_body(x, mean_rstd, gamma, beta, res1, nullptr, n4, C4, relu, NormJoinSide{},
+                     [&](long i, float4 v) { store_split_quad(y, i, v); });
 }
 
 
@@ -73,13 +68,7 @@ __global__ __launch_bounds__(512) void conv_igemm_split_kernel(const ConvKParams
     // ---- block -> (phase, tile): conv_igemm_kernel's walk (phases heaviest first, tiles banded per XCD) ----
     const int tiles_per_phase = p.mtiles * p.ntiles;
     const int phase = blockIdx.x / tiles_per_phase;
-    int rem;
-    {
-        const int nb = tiles_per_phase, b = blockIdx.x - phase * tiles_per_phase;
-        const int xcd = b & 7, idx = b >> 3;
-        const int q = nb >> 3, r = nb & 7;
-        rem = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-    }
+    const int rem = xcd_band(blockIdx.x - phase * tiles_per_phase, tiles_per_phase);
     const int mt = rem / p.ntiles;
     const int nt = rem - mt * p.ntiles;
     const int m0 = mt * kBM, n0 = nt * kBN;
@@ -303,18 +292,9 @@ __global__ __launch_bounds__(512) void conv_igemm_split_kernel(const ConvKParams
 
 template <bool STATS>
 hipError_t launch_split(hipStream_t s, const ConvKParams& p) {
-    auto kern = conv_igemm_split_kernel<STATS>;
-    // the opt-in to 96 KiB of dynamic LDS is per device: one flag per instantiation and device (a race sets it twice)
-    constexpr int kMaxDevices = 64;
-    static std::atomic<bool> attr_done[kMaxDevices];
-    int dev = 0;
-    hipError_t e = hipGetDevice(&dev);
+    constexpr auto kern = conv_igemm_split_kernel<STATS>;
+    const hipError_t e = optin_dynamic_lds<kern>(kSplitLds);
     if (e != hipSuccess) return e;
-    if (dev < 0 || dev >= kMaxDevices || !attr_done[dev].load(std::memory_order_acquire)) {
-        e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, kSplitLds);
-        if (e != hipSuccess) return e;
-        if (dev >= 0 && dev < kMaxDevices) attr_done[dev].store(true, std::memory_order_release);
-    }
     hipLaunchKernelGGL(kern, dim3(p.mtiles * p.ntiles * p.nphases), dim3(512), kSplitLds, s, p);
     return hipGetLastError();
 }

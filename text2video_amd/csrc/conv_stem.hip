@@ -20,18 +20,12 @@
 #include <stdlib.h>
 
 #include "t2v_internal.h"
+#include "k_loops.h"
 
 namespace t2v {
 
 typedef float f32x4s __attribute__((ext_vector_type(4)));
 typedef float f32x16s __attribute__((ext_vector_type(16)));
-
-__device__ __forceinline__ void st_dma16(const float* base, int nbytes, char* lds_dst, int voff, int soff) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    const __amdgpu_buffer_rsrc_t srd = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(base), 0, nbytes, 0x00020000);
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(srd, (__attribute__((address_space(3))) void*)lds_dst, 16, voff, soff, 0, 0);
-#endif
-}
 
 // CR = real input channels where the kernel knows how to skip the storage padding (9 of 12, 6 of 8: `DENSE`), else CS
 template <int CS, int NT, int CR = CS>
@@ -63,13 +57,7 @@ __global__ __launch_bounds__(512) void conv_stem7x7_kernel(const StemParams p) {
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);   // 0..7
 
     // XCD-banded tile order (block b runs on XCD b % 8: a band of tile rows per XCD shares halos in its L2)
-    int tile;
-    {
-        const int nb = gridDim.x, b = blockIdx.x;
-        const int xcd = b & 7, idx = b >> 3;
-        const int q = nb >> 3, r = nb & 7;
-        tile = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-    }
+    const int tile = xcd_band(blockIdx.x, gridDim.x);
     const int tiles_x = (p.W + C::TILE - 1) / C::TILE;   // ragged right / bottom tiles: clamped gather, masked epilogue
     const int x0 = (tile % tiles_x) * C::TILE, y0 = (tile / tiles_x) * C::TILE;
 
@@ -88,7 +76,7 @@ __global__ __launch_bounds__(512) void conv_stem7x7_kernel(const StemParams p) {
             gy = max(min(gy, 2 * p.H - 2 - gy), 0);   // (past the reflected border: only feeds masked outputs)
             gx = max(min(gx, 2 * p.W - 2 - gx), 0);
             const int voff = pix < C::NPIX ? ((gy * p.W + gx) * CS + 4 * j) * 4 : 0x7fff0000;
-            st_dma16(p.x, x_bytes, s_halo + instr * 1024, voff, 0);
+            dma16(p.x, x_bytes, s_halo + instr * 1024, voff, 0);
         }
     }
     if (tid < 64) reinterpret_cast<float*>(s_halo + C::HALO_INSTR * 1024)[tid] = 0.f;
@@ -105,7 +93,7 @@ __global__ __launch_bounds__(512) void conv_stem7x7_kernel(const StemParams p) {
 #pragma unroll
         for (int i = 0; i < (C::W_INSTR + 7) / 8; ++i) {
             const int instr = wave + 8 * i;
-            if (instr < C::W_INSTR) st_dma16(p.w, w_bytes, s_w + instr * 1024, w_voff[i], kh * (7 * CS * 4));
+            if (instr < C::W_INSTR) dma16(p.w, w_bytes, s_w + instr * 1024, w_voff[i], kh * (7 * CS * 4));
         }
     };
     stage_w(0);
@@ -258,13 +246,9 @@ __global__ __launch_bounds__(512) void conv_stem7x7_kernel(const StemParams p) {
 template <int CS, int NT, int CR>
 static int launch_stem(hipStream_t s, const StemParams& p) {
     using C = StemCfg<CS, NT, CR>;
-    auto kern = conv_stem7x7_kernel<CS, NT, CR>;
-    static bool attr_done = false;
-    if (!attr_done) {
-        T2V_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, C::LDS));
-        attr_done = true;
-    }
-    hipLaunchKernelGGL(kern, dim3(((p.H + C::TILE - 1) / C::TILE) * ((p.W + C::TILE - 1) / C::TILE)), dim3(512), C::LDS, s, p);
+    constexpr auto kern = conv_stem7x7_kernel<CS, NT, CR>;
+    T2V_HIP_CHECK(optin_dynamic_lds<kern>(C::LDS));
+    hipLaunchKernelGGL(kern,dim3(((p.H + C::TILE - 1) / C::TILE) * ((p.W + C::TILE - 1) / C::TILE)), dim3(512), C::LDS, s, p);
     T2V_HIP_CHECK(hipGetLastError());
     return T2V_OK;
 }

@@ -559,13 +559,9 @@ int launch_wino_wgrad_sk(hipStream_t s, const float* V, const float* Md, float* 
     // 0.24 GB (PMC, profiles/pmc/r06_wino_wgrad_sk_one_per_cu.txt), 3.8 TB/s taken from the kernels the form exists to
     // let in beside it
     if (!k.rounds && k.tiles >= grid && k.tiles % grid == 0) k.rounds = k.tiles / grid, k.half_round = 0;
-    auto kern = wino_wgrad_sk_kernel<16, 4>;
+    constexpr auto kern = wino_wgrad_sk_kernel<16, 4>;
     constexpr int lds = 4 * 2 * 16 * 128 * 4;
-    static bool attr_done = false;
-    if (!attr_done) {
-        T2V_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, sk_exclusive_lds(lds)));
-        attr_done = true;
-    }
+    T2V_HIP_CHECK(optin_dynamic_lds<kern>(sk_exclusive_lds(lds)));
     // one block per CU (the caller's two streams both carry GEMMs): the block also asks for more than half a CU's LDS, so that
     // the OTHER stream's GEMM block cannot move in beside it -- two GEMMs on a CU share the MFMA pipe without gain and leave
     // the bandwidth-bound kernels no room (today the kernel's 131 registers have the same effect)
@@ -593,13 +589,9 @@ int launch_wgrad_reduce(hipStream_t s, const float* partial, int splits, long n,
 
 template <bool REFLECT, int PIX, int RING>
 static int launch_wgrad_variant(hipStream_t s, const WgradParams& p) {
-    auto kern = conv_wgrad_kernel<REFLECT, PIX, RING>;
+    constexpr auto kern = conv_wgrad_kernel<REFLECT, PIX, RING>;
     constexpr int lds = RING * 2 * PIX * 128 * 4 + 16;   // + the arrival flag of the in-kernel combine
-    static bool attr_done = false;   // per instantiation
-    if (!attr_done) {
-        T2V_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-        attr_done = true;
-    }
+    T2V_HIP_CHECK(optin_dynamic_lds<kern>(lds));
     const int nblocks = p.ntaps * p.ntiles * p.ctiles * p.splits;
     hipLaunchKernelGGL(kern, dim3(nblocks), dim3(512), lds, s, p);
     T2V_HIP_CHECK(hipGetLastError());

@@ -1,14 +1,59 @@
-// k_loops.h -- what the wave-specialised GEMM kernels share (conv_igemm.hip, conv_wgrad.hip, winograd_split.hip): 4 MFMA waves
-// + 4 loader waves per block, an LDS ring of RING stages, one s_barrier per stage -- the loader waves' K loop, and for the
-// fixed-grid ("stream-K") kernels the accumulator hand-over between two blocks.
+// k_loops.h -- what the wave-specialised GEMM kernels share (conv_igemm.hip, conv_wgrad.hip, winograd_split.hip,
+// conv_igemm_split.hip): 4 MFMA waves + 4 loader waves per block, an LDS ring of RING stages, one s_barrier per stage -- the
+// loader waves' K loop, and for the fixed-grid ("stream-K") kernels the accumulator hand-over between two blocks.  Also the
+// small pieces every kernel with an LDS-DMA loader or more than 64 KiB of dynamic LDS needs (conv_stem.hip and conv_head.hip
+// as well): dma16, the XCD-banded tile order, the dynamic-LDS opt-in.
 #pragma once
 #include <hip/hip_runtime.h>
+
+#include <atomic>
 
 #include "t2v_internal.h"
 
 namespace t2v {
 
 typedef unsigned int v4u __attribute__((__vector_size__(16)));   // 16 raw bytes of a b128 buffer load / store
+
+// XCD-banded tile order: block b of nb runs on XCD b % 8 (relied on for speed only), and every XCD gets one contiguous band
+// of the nb tiles -- the first nb % 8 bands one tile longer -- so that neighbouring tiles share operands in that XCD's L2.
+__host__ __device__ constexpr int xcd_band(int b, int nb) {
+    const int xcd = b & 7, idx = b >> 3;
+    const int q = nb >> 3, r = nb & 7;
+    return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
+}
+constexpr bool xcd_band_permutes(int nb) {   // b -> xcd_band(b, nb) hits every tile 0 .. nb - 1 exactly once
+    bool seen[64] = {};
+    for (int b = 0; b < nb; ++b) {
+        const int t = xcd_band(b, nb);
+        if (t < 0 || t >= nb || seen[t]) return false;
+        seen[t] = true;
+    }
+    return true;
+}
+constexpr bool xcd_band_permutes_up_to(int n) {
+    for (int nb = 1; nb <= n; ++nb)
+        if (!xcd_band_permutes(nb)) return false;
+    return true;
+}
+static_assert(xcd_band_permutes_up_to(64), "xcd_band: not a permutation of the tiles");
+
+// The opt-in to more than 64 KiB of dynamic LDS (hipFuncAttributeMaxDynamicSharedMemorySize) for one kernel, before its
+// launch.  The attribute is per device: one flag per (kernel, device), atomic -- two host threads that race set it twice --
+// and a device index outside the table sets it every time.  `bytes` is the same at every call for one kernel.  (static: the
+// flags stay out of the libraries' exports.)
+template <auto Kernel>
+static hipError_t optin_dynamic_lds(int bytes) {
+    constexpr int kMaxDevices = 64;
+    static std::atomic<bool> done[kMaxDevices];
+    int dev = 0;
+    hipError_t e = hipGetDevice(&dev);
+    if (e != hipSuccess) return e;
+    const bool tabled = dev >= 0 && dev < kMaxDevices;
+    if (tabled && done[dev].load(std::memory_order_acquire)) return hipSuccess;
+    e = hipFuncSetAttribute(reinterpret_cast<const void*>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+    if (e == hipSuccess && tabled) done[dev].store(true, std::memory_order_release);
+    return e;
+}
 
 // One LDS-DMA instruction through buffer addressing: 64 lanes x 16 B -> 1 KiB at the wave-uniform LDS
 // address `lds_dst`; source = base + voff (per lane, bytes) + soff (scalar, bytes).  Lanes with

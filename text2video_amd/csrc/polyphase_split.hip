@@ -11,8 +11,6 @@
 namespace t2v {
 namespace {
 
-typedef unsigned short u16;
-
 // polyphase_input_kernel<UP, NORM> (polyphase.hip) with the split store: the same thread -> (tile, sub-block, channel pair)
 // map, so a padding tile's zeros and every position come from the thread that writes them in the fp32 form.
 // Vp: [2][81][Tt][C2] channel pairs.
@@ -58,10 +56,7 @@ __global__ void polyphase_weight_split_kernel(const float* __restrict__ w, u16* 
                 g[a][b] = (n < Cout && c < Cin) ? (double)w[at] : 0.0;
             }
         polyphase_weight_transform<UP>(g, [&](int pos, float u) {
-            const unsigned hi = bf16_rne(u), lo = bf16_rne(u - bf16_float(hi));
-            const size_t at = (size_t)pos * total + i;
-            Up[at] = (u16)hi;
-            Up[(size_t)81 * total + at] = (u16)lo;
+            store_split_planes(Up, (size_t)pos * total + i, (size_t)81 * total, u);
         });
     }
 }

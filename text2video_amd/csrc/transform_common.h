@@ -304,6 +304,19 @@ __device__ __forceinline__ SplitPair split_bf16x2(float2 v) {
     const unsigned lx = bf16_rne(v.x - bf16_float(hx)), ly = bf16_rne(v.y - bf16_float(hy));
     return {hx | (hy << 16), lx | (ly << 16)};
 }
+// the two stores of a finished fp32 value in that form: four channels as the 16-byte slot {hi01, lo01, hi23, lo23} of the
+// direct kernels (conv_igemm_split.hip), one value as a bf16 in the hi plane and one `plane` elements on in the lo plane
+// (the filter transforms of winograd_split.hip and polyphase_split.hip)
+__device__ __forceinline__ void store_split_quad(uint4* y, long i, float4 v) {
+    const SplitPair a = split_bf16x2(make_float2(v.x, v.y)), b = split_bf16x2(make_float2(v.z, v.w));
+    y[i] = make_uint4(a.hi, a.lo, b.hi, b.lo);
+}
+typedef unsigned short u16;
+__device__ __forceinline__ void store_split_planes(u16* hi_plane, size_t at, size_t plane, float v) {
+    const unsigned hi = bf16_rne(v), lo = bf16_rne(v - bf16_float(hi));
+    hi_plane[at] = (u16)hi;
+    hi_plane[plane + at] = (u16)lo;
+}
 
 // ---- polyphase F(4,2) input transform (polyphase.hip) with a store policy, as winograd4_input_item above: the fp32 kernel
 // stores the finished value, the split-bf16 one (polyphase_split.hip) its two bf16 terms.

@@ -18,7 +18,6 @@
 namespace t2v {
 namespace {
 
-typedef unsigned short u16;
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
@@ -82,10 +81,7 @@ __global__ void winograd4_weight_split_kernel(const float* __restrict__ w, u16* 
 #pragma unroll
             for (int b = 0; b < 3; ++b) g[a][b] = (n < Cout && c < Cin) ? (double)w[(((size_t)n * Cin + c) * 3 + a) * 3 + b] : 0.0;
         winograd4_weight_transform(g, [&](int pos, float u) {
-            const unsigned hi = bf16_rne(u), lo = bf16_rne(u - bf16_float(hi));
-            const size_t at = (size_t)pos * total + i;
-            Up[at] = (u16)hi;
-            Up[(size_t)36 * total + at] = (u16)lo;
+            store_split_planes(Up, (size_t)pos * total + i, (size_t)36 * total, u);
         });
     }
 }
@@ -97,7 +93,10 @@ __global__ void winograd4_weight_split_kernel(const float* __restrict__ w, u16* 
 // the loaders keep kRing - 1 stages in flight, wait with a counted vmcnt until all but the newest have landed and meet the MFMA
 // waves at ONE barrier per stage; a slot is refilled only after the barrier behind its last read.  Both wave kinds execute
 // nk + 1 barriers for every nk >= 1 (stages past the end re-load the last one: same instruction count per stage, so the
-// vmcnt constants hold for K / 32 below the ring depth as well).
+// vmcnt constants hold for K / 32 below the ring depth as well).  The loaders' loop is k_loops.h's loader_k_loop.  The
+// MFMA waves' loop below is conv_igemm_split_kernel's written out a second time, on purpose: with both loops shared this kernel's
+// GEMM stage ran 0.4 % slower at the trunk shapes (0.8 % with the guard on the last prefetch kept, 0.45 % with this loop
+// inline and the guard dropped); with the loader loop alone shared it runs as before (profiles/split_shared_times.txt).
 // A trailing half tile (Tt % 128 == 64): its loaders re-read rows 0..63 for the missing ones, the MFMA waves of those rows
 // skip their work (not their barriers) and store nothing.
 constexpr int kBM = 128, kBN = 128, kSBK = 32, kRing = 3;
@@ -114,13 +113,7 @@ __global__ __launch_bounds__(512) void wino_split_gemm_kernel(const u16* __restr
     const bool is_loader = wave >= 4;
     const int wid = wave & 3;
     // block -> tile: a contiguous run of tiles per XCD (block b runs on XCD b % 8: relied on for speed only)
-    int tile;
-    {
-        const int nb = gridDim.x, b = blockIdx.x;
-        const int xcd = b & 7, idx = b >> 3;
-        const int q = nb >> 3, r = nb & 7;
-        tile = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-    }
+    const int tile = xcd_band(blockIdx.x, gridDim.x);
     const int per_pos = mtiles * ntiles;
     const int p = tile / per_pos, rest = tile - p * per_pos;
     const int mt = rest / ntiles, nt = rest - mt * ntiles;
@@ -152,19 +145,7 @@ __global__ __launch_bounds__(512) void wino_split_gemm_kernel(const u16* __restr
                     dma16(B, b_bytes, dst, voff[n], kt * (kSBK * 2));
             }
         };
-        constexpr int AHEAD = kRing - 1;
-#pragma unroll
-        for (int st = 0; st < AHEAD; ++st) issue_stage(st < nk ? st : nk - 1, st);
-        asm volatile("s_waitcnt vmcnt(%0)" ::"n"((AHEAD - 1) * kLd) : "memory");
-        __builtin_amdgcn_s_barrier();      // B0: stage 0 visible
-        int slot = AHEAD % kRing;
-        for (int kt = 0; kt < nk; ++kt) {
-            issue_stage(kt + AHEAD < nk ? kt + AHEAD : nk - 1, slot);
-            asm volatile("s_waitcnt vmcnt(%0)" ::"n"((AHEAD - 1) * kLd) : "memory");
-            __builtin_amdgcn_s_barrier();  // barrier(kt): stage kt + 1 visible
-            slot = slot == kRing - 1 ? 0 : slot + 1;
-        }
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // nothing may land in this block's LDS after it has ended
+        loader_k_loop<kRing, kLd>(0, nk, issue_stage);   // (ends with vmcnt(0): nothing lands in this block's LDS after it)
         return;
     }
 
@@ -276,12 +257,7 @@ bool wino_split_gemm_ok(int npos, int Tt, int K, int N) {
 int launch_wino_split_gemm(hipStream_t s, int npos, const float* V, const float* U, float* M, int Tt, int K, int N) {
     T2V_REQUIRE(wino_split_gemm_ok(npos, Tt, K, N), "split-bf16 gemm: %d positions, Tt=%d (%% 64), K=%d (%% 32), N=%d (%% 128) not supported",
                 npos, Tt, K, N);
-    static bool attr_done = false;
-    if (!attr_done) {
-        T2V_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(wino_split_gemm_kernel),
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, kSplitGemmLds));
-        attr_done = true;
-    }
+    T2V_HIP_CHECK(optin_dynamic_lds<wino_split_gemm_kernel>(kSplitGemmLds));
     const int mtiles = (Tt + kBM - 1) / kBM, ntiles = N / kBN;
     hipLaunchKernelGGL(wino_split_gemm_kernel, dim3(npos * mtiles * ntiles), dim3(512), kSplitGemmLds, s,
                        reinterpret_cast<const u16*>(V), reinterpret_cast<const u16*>(U), M, npos, Tt, N, K, mtiles, ntiles);
