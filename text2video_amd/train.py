@@ -13,7 +13,8 @@ discriminator (--num_D 2), face discriminator (--add_face_disc), temporal discri
 feature-matching losses, the VGG19 perceptual loss (frozen torchvision weights supplied with --vgg_weights), the
 flow / warp / weight losses against a SUPPLIED reference flow (zero flow + its confidence mask by default:
 FlowNet2, which produces it upstream, is not in the reference tree -- SURVEY 8d config 5), Adam(lr 2e-4,
-beta1 0.5), data-parallel gradient all-reduce.
+beta1 0.5), data-parallel gradient all-reduce.  Beyond that recipe: upstream's high-resolution continuation, the two-scale
+generator (--n_scales_spatial 2: TrainableLocalGenerator, TwoScaleGenerator) with --niter_fix_global.
 """
 import collections
 import contextlib
@@ -561,9 +562,13 @@ def masked_l1(a, b, mask, C, c0=0):
 class TrainableGenerator(torch.nn.Module):
     """CompositeGenerator with or without its flow branch, upstream parameter names."""
 
+    LOCAL = False
+
     def __init__(self, spec, state_dict, device="cuda"):
         super().__init__()
-        assert not spec.is_local, "train step: the global generator (n_scales_spatial 1)"
+        if bool(spec.is_local) != self.LOCAL:
+            raise ValueError("%s: a spec with is_local=%s is built by %s" % (
+                type(self).__name__, bool(spec.is_local), "TrainableLocalGenerator" if spec.is_local else "TrainableGenerator"))
         self.spec = spec
         self.keys = layer_keys(spec)
         self.params = torch.nn.ParameterDict()
@@ -576,11 +581,47 @@ class TrainableGenerator(torch.nn.Module):
     def named_upstream_parameters(self):
         return {k.replace("/", "."): v for k, v in self.params.items()}
 
-    def forward(self, pose, prev, use_raw_only=False, full=False, need_flow=True):
+    def _heads(self, img_feat, flow_feat, prev, use_raw_only, off_tape=False):
+        """The 7x7 heads on the decoders' outputs -> (fake, raw, flow_w) as forward(full=True) returns them; flow_feat None:
+        no flow branch, or a raw-only frame whose flow nobody reads.  (forward() below keeps its own copy of these lines: the
+        single-scale step does not pass through here.)
+        off_tape: the coarse scale of a two-scale generator.  Its frame feeds only its own FIFO, no loss reads it (upstream
+        scores the finest scale alone), so the heads run outside the autograd graph on detached features and detached views of
+        their parameters: no backward node is announced for them (expect_gradient), nothing is counted on the weights."""
+        s = self.spec
+        G, H, W = s.ngf, img_feat.shape[1], img_feat.shape[2]
+        d7 = ops.conv_desc(H, W, G, 3, 7, 1, 3, ops.PAD_REFLECT)
+
+        def hp(key):
+            t = self.p(key)
+            if not off_tape:
+                return t
+            d = t.detach()
+            d._t2v_owner = t
+            return d
+
+        with (torch.no_grad() if off_tape else contextlib.nullcontext()):
+            if off_tape:
+                img_feat = img_feat.detach()
+                flow_feat = flow_feat.detach() if flow_feat is not None else None
+            ck = next(k for k, _, kind in self.keys if kind == "head")
+            raw = conv_block(img_feat, hp(ck + ".weight"), hp(ck + ".bias"), d7, norm=None, relu=0, act=ops.ACT_TANH)
+            if flow_feat is None:
+                return raw, (None if s.no_flow else raw), None
+            kf, kw = next(k for k, _, kind in self.keys if kind == "flow_w")
+            w3 = _CatParams.apply(hp(kf + ".weight"), hp(kw + ".weight"))
+            b3 = _CatParams.apply(hp(kf + ".bias"), hp(kw + ".bias"))
+            fw = conv_block(flow_feat, w3, b3, d7, norm=None, relu=0, act=ops.ACT_FLOW_W, slope=20.0 * (2 ** s.scale))
+            fake = raw if use_raw_only else _WarpComposite.apply(raw, fw, prev, s.prev_nc - 3)
+        return fake, raw, fw
+
+    def forward(self, pose, prev, use_raw_only=False, full=False, need_flow=True, feats=False):
         """pose [1,H,W,12], prev [1,H,W,8] NHWC -> fake [1,H,W,4] (RGB in channels 0..2).  full=True returns
         (fake, raw, flow_w): raw = the tanh image before the blend, flow_w [1,H,W,4] = (flow_x, flow_y in pixels,
         weight, 0); both None without a flow branch.  use_raw_only: the first frame of a sequence under
-        --no_first_img (fake is raw; flow and weight are still computed, the flow losses see them)."""
+        --no_first_img (fake is raw; flow and weight are still computed, the flow losses see them).
+        feats=True (the coarse scale of TwoScaleGenerator): returns (fake, raw, flow_w, img_feat, flow_feat) -- the two
+        decoder outputs [1,H,W,ngf] the heads read, attached; the heads themselves run off the tape (_heads)."""
         s = self.spec
         n, G = s.n_downsample, s.ngf
         H, W = pose.shape[1], pose.shape[2]
@@ -619,6 +660,10 @@ class TrainableGenerator(torch.nn.Module):
         # path runs them, were tried in round 3: +0.7 % with the fixed-grid kernels on; removed)
         d = encoder(pose, s.input_nc, nb_enc) + encoder(prev, s.prev_nc, nb_enc)
         img_feat = decoder(resblocks(d, nb_res))
+        if feats:
+            next(it)        # (the image head's entry: _heads looks the heads up by kind)
+            flow_feat = None if (s.no_flow or (use_raw_only and not need_flow)) else decoder(resblocks(d, nb_res))
+            return self._heads(img_feat, flow_feat, prev, use_raw_only, off_tape=True) + (img_feat, flow_feat)
         ck, _, _ = next(it)
         raw = conv_block(img_feat, self.p(ck + ".weight"), self.p(ck + ".bias"),
                          ops.conv_desc(H, W, G, 3, 7, 1, 3, ops.PAD_REFLECT), norm=None, relu=0, act=ops.ACT_TANH)
@@ -638,6 +683,110 @@ class TrainableGenerator(torch.nn.Module):
                         act=ops.ACT_FLOW_W, slope=20.0 * (2 ** s.scale))
         fake = raw if use_raw_only else _WarpComposite.apply(raw, fw, prev, s.prev_nc - 3)
         return (fake, raw, fw) if full else fake
+
+
+class TrainableLocalGenerator(TrainableGenerator):
+    """CompositeLocalGenerator: the fine-scale enhancer netG{s >= 1}, fed by the coarse scale's two decoder
+    outputs; upstream parameter names (layer_keys of a local spec).  spec.ngf is this scale's own width (ngf_global / 2^scale)."""
+    LOCAL = True
+
+    def forward(self, pose, prev, img_feat_coarse, flow_feat_coarse, use_raw_only=False, full=False, need_flow=True):
+        """pose [1,H,W,12], prev [1,H,W,8], img_feat_coarse / flow_feat_coarse [1,H/2,W/2,2*ngf] (flow_feat_coarse None where
+        the flow branch does not run) -> what TrainableGenerator.forward returns."""
+        s = self.spec
+        G = s.ngf
+        H, W = pose.shape[1], pose.shape[2]
+        if H % 2 or W % 2 or tuple(img_feat_coarse.shape[1:]) != (H // 2, W // 2, 2 * G):
+            raise ValueError("TrainableLocalGenerator: a %d x %d frame with ngf %d takes coarse features [1, %d, %d, %d], not %s"
+                             % (H, W, G, H // 2, W // 2, 2 * G, list(img_feat_coarse.shape)))
+        norm = "instance"   # BatchNorm2d(train) with N=1 == instance norm + affine (SURVEY R3)
+        it = iter(self.keys)
+
+        def cna(x, desc, relu=1, res=None, need_dx=True):
+            ck, nk, kind = next(it)
+            g = self.p(nk + ".weight") if s.norm == "batch" else None
+            b = self.p(nk + ".bias") if s.norm == "batch" else None
+            return conv_block(x, self.p(ck + ".weight"), self.p(ck + ".bias"), desc, g, b, res, norm, relu,
+                              need_dx=need_dx)
+
+        def encoder(x, in_nc, res=None):
+            h = cna(x, ops.conv_desc(H, W, in_nc, G, 7, 1, 3, ops.PAD_REFLECT), need_dx=False)
+            return cna(h, ops.conv_desc(H, W, G, 2 * G, 3, 2, 1, ops.PAD_ZERO), res=res)
+
+        def up(h):
+            d3 = ops.conv_desc(H // 2, W // 2, 2 * G, 2 * G, 3, 1, 1, ops.PAD_REFLECT)
+            for _ in range(s.n_blocks):
+                t = cna(h, d3, relu=1)
+                h = cna(t, d3, relu=0, res=h)
+            return cna(h, ops.conv_desc(H // 2, W // 2, 2 * G, G, 3, 2, 1, ops.PAD_ZERO, True))
+
+        # model_down_seg(x) + model_down_img(prev): the second encoder's last block takes the first one's output as its
+        # residual, so the add rides in that block's norm-apply pass (y = relu(norm(c)) + res)
+        d = encoder(prev, s.prev_nc, res=encoder(pose, s.input_nc))
+        img_feat = up(d + img_feat_coarse)
+        next(it)        # (the image head's entry: _heads looks the heads up by kind)
+        flow_feat = None
+        if not (s.no_flow or (use_raw_only and not need_flow)):
+            flow_feat = up(d + flow_feat_coarse)
+        out = self._heads(img_feat, flow_feat, prev, use_raw_only)
+        return out if full else out[0]
+
+
+class TwoScaleGenerator(torch.nn.Module):
+    """--n_scales_spatial 2: the global generator G0 on the H/2 x W/2 level of the pyramid and the local enhancer G1 on the
+    frame itself, per frame what Vid2VidModelG.inference_nhwc_batch does.  The coarse pose window is ops.avgpool3x3s2 of the
+    fine one; each scale keeps the FIFO of its OWN generated frames (detached); G0's two decoder outputs reach G1 attached, so
+    the losses -- all on G1's outputs -- train G0's trunk through them.  G0's three head convolutions feed only its FIFO and
+    receive no gradient (as upstream): head_params() names them, the trainer keeps them out of the optimiser and the buckets."""
+
+    def __init__(self, G0, G1):
+        super().__init__()
+        self.G0, self.G1 = G0, G1
+        self.spec = G1.spec
+
+    def head_params(self):
+        return [p for k, p in self.G0.named_upstream_parameters().items() if k.startswith("model_final_")]
+
+    def check_geometry(self, H, W):
+        m = 2 ** (self.G0.spec.n_downsample + 1)
+        if H % m or W % m:
+            raise ValueError("two-scale generator: a %d x %d frame is no multiple of %d = 2^(n_downsample_G %d + 1) in both "
+                             "dimensions (the coarse scale halves it, G0 halves that %d times)"
+                             % (H, W, m, self.G0.spec.n_downsample, self.G0.spec.n_downsample))
+
+    def zero_prev(self, H, W, device):
+        """the FIFOs in front of a sequence's first frame: (finest scale's [1,H,W,8], coarse scale's [1,H/2,W/2,8])"""
+        cs = ops.round_up(self.spec.prev_nc, 4)
+        return (torch.zeros(1, H, W, cs, dtype=torch.float32, device=device),
+                torch.zeros(1, H // 2, W // 2, cs, dtype=torch.float32, device=device))
+
+    @staticmethod
+    def shift(prev, frame):
+        """fake_B_prev = cat(fake_B_prev[1:], fake_B) on one scale's FIFO (n_frames_G 3), the new frame detached"""
+        new = torch.zeros_like(prev)
+        new[..., :3] = prev[..., 3:6]
+        new[..., 3:6] = frame.detach()[..., :3]
+        return new
+
+    def forward(self, pose, prev, use_raw_only=False, need_flow=True):
+        """pose [1,H,W,12]; prev = (fine FIFO, coarse FIFO) -> (fake, raw, flow_w) of the finest scale as
+        TrainableGenerator.forward(full=True) returns them, the coarse scale's frame [1,H/2,W/2,4] (detached), and the pair of
+        FIFOs behind this frame."""
+        H, W = pose.shape[1], pose.shape[2]
+        self.check_geometry(H, W)
+        prev1, prev0 = prev
+        with torch.no_grad():
+            pose0 = ops.avgpool3x3s2(pose[0]).unsqueeze(0)
+        fake0, _, _, img_feat, flow_feat = self.G0(pose0, prev0, use_raw_only=use_raw_only, full=True, need_flow=need_flow,
+                                                   feats=True)
+        fake, raw, fw = self.G1(pose, prev1, img_feat, flow_feat, use_raw_only=use_raw_only, full=True, need_flow=need_flow)
+        return fake, raw, fw, fake0, (self.shift(prev1, fake), self.shift(prev0, fake0))
+
+
+def global_generator_frozen(epoch, niter_fix_global):
+    """--niter_fix_global N (upstream's update_fixed_params): with two spatial scales only the local enhancer trains during
+    the epochs 1 .. N; from epoch N + 1 on both generators do.  N = 0: both from the start."""
+    return 1 <= epoch <= niter_fix_global
 
 
 class TrainableDiscriminator(torch.nn.Module):
@@ -783,7 +932,7 @@ class HipVGG19Features(torch.nn.Module):
 def vgg_loss(vgg, fake, real, real_feats=None):
     """VGGLoss [RECALL upstream models/networks.py]: sum_i w_i * L1(vgg(fake)_i, vgg(real)_i.detach()),
     w = 1/32, 1/16, 1/8, 1/4, 1.  Upstream first halves inputs wider than 1024 px with AvgPool2d(2, 2); that only
-    happens in multi-scale (n_scales_spatial > 1) training, which this train step does not cover."""
+    happens in two-scale training at 2048 px, which stays refused here."""
     if fake.shape[2] > 1024:
         raise NotImplementedError("vgg_loss: inputs wider than 1024 px (upstream's AvgPool2d(2,2) pre-scaling)")
     fr = real_feats          # the real frames' taps, when the caller already has them (two fake inputs, one real)
@@ -1048,7 +1197,9 @@ class Vid2VidTrainer:
         self.opt, self.device = opt, device
         # flags of upstream's train.py that would train a DIFFERENT configuration here: refuse instead of ignoring
         for flag, bad, why in (("no_lsgan", bool(getattr(opt, "no_lsgan", False)), "only the LSGAN (MSE) objective is built"),
-                               ("n_scales_spatial", getattr(opt, "n_scales_spatial", 1) > 1, "the train step covers the global generator"),
+                               ("n_scales_spatial", getattr(opt, "n_scales_spatial", 1) > 2,
+                                "two spatial scales are built (the global generator and one local enhancer), not %d"
+                                % getattr(opt, "n_scales_spatial", 1)),
                                ("max_frames_backpropagate", getattr(opt, "max_frames_backpropagate", 1) > 1,
                                 "generated previous frames are always detached (the recipe's default, 1)"),
                                ("use_single_G", bool(getattr(opt, "use_single_G", False)), "no first-frame generator"),
@@ -1057,14 +1208,24 @@ class Vid2VidTrainer:
                                 "the split-bf16 trunk is a forward-only form; training computes in fp32")):
             if bad:
                 raise NotImplementedError("--%s: %s" % (flag, why))
-        for flag, on in (("pool_size", getattr(opt, "pool_size", 1) > 1), ("niter_fix_global", getattr(opt, "niter_fix_global", 0) > 0)):
-            if on:
-                print("warning: --%s has no effect here (single-scale training, no image pool)" % flag, flush=True)
+        if getattr(opt, "pool_size", 1) > 1:
+            print("warning: --pool_size has no effect here (no image pool)", flush=True)
         input_nc = opt.label_nc if opt.label_nc != 0 else opt.input_nc
         self.spec = GeneratorSpec(input_nc=input_nc * opt.n_frames_G, prev_nc=(opt.n_frames_G - 1) * opt.output_nc,
                                   ngf=opt.ngf, n_downsample=opt.n_downsample_G, n_blocks=opt.n_blocks,
                                   no_flow=bool(opt.no_flow), norm=opt.norm)
-        self.G = TrainableGenerator(self.spec, synthetic_state_dict(self.spec, seed, "vid2vid"), device)
+        self.two_scale = getattr(opt, "n_scales_spatial", 1) == 2
+        # fix_global: G0 is frozen (--niter_fix_global, the first epochs of a two-scale run: set_epoch)
+        self.fix_global = False
+        if self.two_scale:
+            from .model import generator_specs
+            self.spec, spec1 = generator_specs(opt)
+            self.G = TwoScaleGenerator(TrainableGenerator(self.spec, synthetic_state_dict(self.spec, seed, "vid2vid"), device),
+                                       TrainableLocalGenerator(spec1, synthetic_state_dict(spec1, seed + 30, "vid2vid"), device))
+            self.nets_G = [("G0", self.G.G0), ("G1", self.G.G1)]
+        else:
+            self.G = TrainableGenerator(self.spec, synthetic_state_dict(self.spec, seed, "vid2vid"), device)
+            self.nets_G = [("G0", self.G)]
         d_in = input_nc + opt.output_nc
         self.D = TrainableDiscriminator(d_in, discriminator_state_dict(d_in, opt.ndf, opt.n_layers_D, opt.num_D, opt.norm,
                                                                        seed + 1), opt.ndf, opt.n_layers_D, opt.num_D,
@@ -1107,7 +1268,9 @@ class Vid2VidTrainer:
         if getattr(opt, "TTUR", False):    # [RECALL upstream: two time-scale update rule]
             betas, lr_g, lr_d = (0.0, 0.9), opt.lr / 2.0, opt.lr * 2.0
         self.lr_scale = (lr_g / opt.lr, lr_d / opt.lr)
-        self.optG = FusedAdam(self.G.parameters(), lr_g, betas)
+        if self.two_scale:      # (the first epoch's phase; run_train calls set_epoch at every epoch's start)
+            self.fix_global = global_generator_frozen(1, getattr(opt, "niter_fix_global", 0))
+        self.optG = FusedAdam(self._trainable_generator_params(), lr_g, betas)
         self.optD = FusedAdam(d_params, lr_d, betas)
         # persistent flat gradient buckets (the backward nodes write into them; exchanged in place)
         self.bucketsG = GradBuckets(self.optG.params, name="G")
@@ -1120,6 +1283,44 @@ class Vid2VidTrainer:
         # --display_web): pose [H,W,12], fake, raw, real [H,W,4] and, with the flow branch, fw [H,W,4] = (flow_x, flow_y,
         # weight, 0), flow_ref [H,W,4], conf_ref [H,W].  References into the step's own tensors: no copy, no kernel.
         self.keep_visuals, self.visuals = False, None
+
+    def _trainable_generator_params(self):
+        """What optG and bucketsG hold.  One scale: every generator parameter.  Two scales: G1's, and -- unless G0 is frozen
+        (fix_global) -- G0's trunk; G0's three head convolutions never receive a gradient (TwoScaleGenerator), so they are in
+        neither: not updated, no Adam moments, not exchanged, and no bucket waits for them.  Sets requires_grad on G0 to match."""
+        if not self.two_scale:
+            return list(self.G.parameters())
+        for p in self.G.G0.parameters():
+            p.requires_grad_(not self.fix_global)
+        heads = {id(p) for p in self.G.head_params()}
+        g0 = [] if self.fix_global else [p for p in self.G.G0.parameters() if id(p) not in heads]
+        return g0 + list(self.G.G1.parameters())
+
+    def set_epoch(self, epoch):
+        """--niter_fix_global N with two spatial scales: G0 is frozen during the epochs 1 .. N (global_generator_frozen).  Where
+        `epoch` changes the phase, the optimiser's parameter tables and the gradient buckets are rebuilt over the new trainable
+        set: a parameter that stays keeps its Adam moments and step count, one that joins starts from zero moments."""
+        if not self.two_scale:
+            return
+        frozen = global_generator_frozen(epoch, getattr(self.opt, "niter_fix_global", 0))
+        if frozen == self.fix_global:
+            return
+        self.fix_global = frozen
+        old = self.optG
+        if getattr(old, "_pending", None) is not None:
+            old._pending[1].synchronize()     # (its last step's table copies have left its pinned staging buffers)
+        for p in old.params:
+            param_state(p).gslot = None
+        kept = {id(p): i for i, p in enumerate(old.params)}
+        self.optG = FusedAdam(self._trainable_generator_params(), old.lr, old.betas, old.eps)
+        for j, p in enumerate(self.optG.params):
+            i = kept.get(id(p))
+            if i is not None:
+                self.optG.m[j], self.optG.v[j], self.optG.steps[j] = old.m[i], old.v[i], old.steps[i]
+        self.bucketsG = GradBuckets(self.optG.params, name="G")
+        print("epoch %d: the global generator G0 %s (--niter_fix_global %d): %d generator tensors train"
+              % (epoch, "is frozen" if frozen else "trains with G1", getattr(self.opt, "niter_fix_global", 0),
+                 len(self.optG.params)), flush=True)
 
     def _d_input(self, A3, img4):
         z = torch.zeros(A3.shape[:-1] + (2,), dtype=torch.float32, device=A3.device)
@@ -1405,11 +1606,27 @@ class Vid2VidTrainer:
         self.bucketsD.begin_step()
         flow_on = not self.spec.no_flow
         first = prev is None
-        if first:   # a new sequence starts: zero previous frames, raw-only first frame (--no_first_img)
+        if self.two_scale:
+            # `prev` is the pair (finest scale's FIFO, coarse scale's FIFO); every loss below reads the finest scale's frames
+            # only, `prevs` are its FIFOs
+            if first:
+                self.G.check_geometry(H, W)
+                prev = self.G.zero_prev(H, W, dev)
+        elif first:   # a new sequence starts: zero previous frames, raw-only first frame (--no_first_img)
             prev = torch.zeros(1, H, W, ops.round_up(self.spec.prev_nc, 4), dtype=torch.float32, device=dev)
+        if first:
             self._hist_real, self._hist_fake = [], []
         fakes, raws, fws, prevs = [], [], [], []
         for f in range(F_):
+            if self.two_scale:
+                fk, rw, fw, _, nprev = self.G(pose[f:f + 1], prev, use_raw_only=first and f == 0,
+                                              need_flow=real_prev is not None)
+                fakes.append(fk)
+                raws.append(rw)
+                fws.append(fw)
+                prevs.append(prev[0])
+                prev = nprev
+                continue
             fk, rw, fw = self.G(pose[f:f + 1], prev, use_raw_only=first and f == 0, full=True,
                                 need_flow=real_prev is not None)
             fakes.append(fk)
@@ -1564,7 +1781,7 @@ class Vid2VidTrainer:
         their initialisation"""
         import os
         d = directory or os.path.join(self.opt.checkpoints_dir, self.opt.name)
-        nets = [("G0", self.G), ("D", self.D)] + ([("D_f", self.Df)] if self.Df is not None else []) + \
+        nets = self.nets_G + [("D", self.D)] + ([("D_f", self.Df)] if self.Df is not None else []) + \
                [("D_T%d" % sc, dt) for sc, dt in enumerate(self.DT)]
         for tag, net in nets:
             path = os.path.join(d, "%s_net_%s.pth" % (epoch_label, tag))
@@ -1615,7 +1832,8 @@ class Vid2VidTrainer:
                     sd[base + "num_batches_tracked"] = torch.tensor(rs[2], dtype=torch.long)
             return sd
 
-        torch.save(state_dict(self.G), os.path.join(d, "%s_net_G0.pth" % epoch_label))
+        for tag, net in self.nets_G:      # (G0, and with two spatial scales G1: create_model loads the pair)
+            torch.save(state_dict(net), os.path.join(d, "%s_net_%s.pth" % (epoch_label, tag)))
         torch.save(state_dict(self.D), os.path.join(d, "%s_net_D.pth" % epoch_label))
         if self.Df is not None:
             torch.save(state_dict(self.Df), os.path.join(d, "%s_net_D_f.pth" % epoch_label))
@@ -1855,6 +2073,7 @@ def run_train(opt, steps=None, watch=None):
     stats, it, total_samples = [], 0, (start_epoch - 1) * per_epoch * world + epoch_iter
     last_epoch = opt.niter + opt.niter_decay
     for epoch in range(start_epoch, last_epoch + 1):
+        trainer.set_epoch(epoch)      # (--niter_fix_global with two spatial scales; a resumed run enters its epoch's phase here)
         for k in range(epoch_iter // world, per_epoch):
             if steps is not None and it >= steps:
                 break
