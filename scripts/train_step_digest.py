@@ -5,12 +5,15 @@ For every case and switch setting one line:
     parameter and BatchNorm running statistic of G, D, D_f and D_T* after the last step, as Vid2VidTrainer.save writes them>
 Two runs agree on a line exactly when every loss and every weight they computed is the same.
 
-Usage: train_step_digest.py [--root TREE] [--cases a,b,c] [--switches all|default]
+Usage: train_step_digest.py [--root TREE] [--cases a,b,c,d] [--switches all|default]
   a: 128x128, ngf 32, flow branch, two D scales, face D; 3 steps
   b: 128x128, ngf 64 (the kept input transforms, the fixed-grid GEMMs forced: T2V_WINO_GEMM_SK=2); 3 steps
   c: 64x64, two temporal D scales; 5 steps, the fourth begins a new sequence (prev=None: its first frame is raw-only, the
      flow branch's collected weight gradients are flushed)
-Case a also runs with each of the train step's A/B switches set to its other value."""
+  d: 64x64, two spatial scales (G0 + the local enhancer G1; the state digest covers both files); 3 steps, the third begins a
+     new sequence
+Case a also runs with each of the train step's A/B switches set to its other value, case d also pass by pass
+(T2V_D_BATCHED=0)."""
 import argparse
 import hashlib
 import os
@@ -19,7 +22,7 @@ import tempfile
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--root", default=os.path.dirname(os.path.dirname(os.path.abspath(__file__))), help="the tree to import")
-ap.add_argument("--cases", default="a,b,c")
+ap.add_argument("--cases", default="a,b,c,d")
 ap.add_argument("--switches", default="all", choices=["all", "default"])
 args = ap.parse_args()
 sys.path.insert(0, os.path.abspath(args.root))
@@ -41,9 +44,14 @@ CASES = {
                     "--n_scales_temporal", "0"]),
     "c": dict(size=64, seed=0, rng=0, steps=5, face=False, env={}, new_sequence_at=3,
               argv=["--ngf", "16", "--n_blocks", "2", "--num_D", "1", "--fineSize", "64", "--n_scales_temporal", "2", "--no_vgg"]),
+    "d": dict(size=64, seed=3, rng=4, steps=3, face=False, env={}, new_sequence_at=2,
+              argv=["--ngf", "16", "--n_blocks", "2", "--n_downsample_G", "2", "--num_D", "2", "--ndf", "16", "--no_vgg",
+                    "--fineSize", "64", "--loadSize", "64", "--n_scales_temporal", "0", "--n_scales_spatial", "2",
+                    "--n_blocks_local", "1"]),
 }
+PASS_BY_PASS = {"T2V_D_BATCHED": "0"}
 SWITCHES = [{}, {"T2V_GRAD_DIRECT": "0"}, {"T2V_WGRAD_STREAM": "0", "T2V_PACK_PREFETCH": "0"}, {"T2V_WGRAD_BATCH": "0"},
-            {"T2V_WGRAD_PAIR": "0"}, {"T2V_WGRAD_KEEP_V": "0"}, {"T2V_D_BATCHED": "0"}, {"T2V_D_BWD_STREAM": "1"}]
+            {"T2V_WGRAD_PAIR": "0"}, {"T2V_WGRAD_KEEP_V": "0"}, PASS_BY_PASS, {"T2V_D_BWD_STREAM": "1"}]
 
 
 def run(name, case, switches, ckpt):
@@ -94,5 +102,5 @@ def run(name, case, switches, ckpt):
 
 with tempfile.TemporaryDirectory() as ckpt:
     for name in args.cases.split(","):
-        for switches in (SWITCHES if (name == "a" and args.switches == "all") else [{}]):
+        for switches in {"a": SWITCHES, "d": [{}, PASS_BY_PASS]}.get(name, [{}]) if args.switches == "all" else [{}]:
             run(name, CASES[name], switches, ckpt)

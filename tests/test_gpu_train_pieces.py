@@ -32,14 +32,14 @@ def _init(net, seed):
 @pytest.mark.parametrize("norm", ["batch", "instance"])
 def test_multiscale_discriminator_forward_and_losses(norm):
     from oracle.generator_ref import MultiscaleDiscriminator
-    from text2video_amd.discriminator import HipMultiscaleDiscriminator, feature_matching_loss, gan_loss
+    from text2video_amd.train import TrainableDiscriminator, feature_matching_loss, gan_loss
     B, H, W = 2, 64, 96
     ref = _init(MultiscaleDiscriminator(6, 64, 3, 2, norm), 5)
-    hip = HipMultiscaleDiscriminator(6, 64, 3, 2, norm, "cuda:0").load_state_dict(ref.state_dict())
+    hip = TrainableDiscriminator(6, ref.state_dict(), 64, 3, 2, norm, "cuda:0")
     fake, real = _rand(B, 6, H, W, seed=1), _rand(B, 6, H, W, seed=2)
     with torch.no_grad():
         want_f, want_r = ref(fake), ref(real)
-    got_f, got_r = hip.forward(_nhwc_batch(fake, 8)), hip.forward(_nhwc_batch(real, 8))
+        got_f, got_r = hip(_nhwc_batch(fake, 8)), hip(_nhwc_batch(real, 8))
     for i in range(2):
         for j in range(5):
             w = want_f[i][j]
@@ -58,13 +58,13 @@ def test_multiscale_discriminator_forward_and_losses(norm):
 def test_face_discriminator_128_crop():
     """--add_face_disc: single-scale PatchGAN on a 128x128 crop."""
     from oracle.generator_ref import MultiscaleDiscriminator
-    from text2video_amd.discriminator import HipMultiscaleDiscriminator
+    from text2video_amd.train import TrainableDiscriminator
     ref = _init(MultiscaleDiscriminator(6, 64, 3, 1, "batch"), 6)
-    hip = HipMultiscaleDiscriminator(6, 64, 3, 1, "batch", "cuda:0").load_state_dict(ref.state_dict())
+    hip = TrainableDiscriminator(6, ref.state_dict(), 64, 3, 1, "batch", "cuda:0")
     x = _rand(1, 6, 128, 128, seed=3)
     with torch.no_grad():
         want = ref(x)
-    got = hip.forward(_nhwc_batch(x, 8))
+        got = hip(_nhwc_batch(x, 8))
     assert got[0][-1].shape[1:3] == (19, 19)
     for j in range(5):
         w = want[0][j]

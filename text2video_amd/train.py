@@ -559,6 +559,14 @@ def masked_l1(a, b, mask, C, c0=0):
 # ------------------------------------------------------------------------------------------------
 # networks
 # ------------------------------------------------------------------------------------------------
+def shift(prev, frame):
+    """fake_B_prev = cat(fake_B_prev[1:], fake_B) on one scale's FIFO (n_frames_G 3), the new frame detached"""
+    new = torch.zeros_like(prev)
+    new[..., :3] = prev[..., 3:6]
+    new[..., 3:6] = frame.detach()[..., :3]
+    return new
+
+
 class TrainableGenerator(torch.nn.Module):
     """CompositeGenerator with or without its flow branch, upstream parameter names."""
 
@@ -684,6 +692,19 @@ class TrainableGenerator(torch.nn.Module):
         fake = raw if use_raw_only else _WarpComposite.apply(raw, fw, prev, s.prev_nc - 3)
         return (fake, raw, fw) if full else fake
 
+    # what the trainer's frame loop asks of a generator (TwoScaleGenerator answers the same three calls)
+    def check_geometry(self, H, W):
+        pass
+
+    def zero_prev(self, H, W, device):
+        """the FIFO in front of a sequence's first frame: [1,H,W,8]"""
+        return torch.zeros(1, H, W, ops.round_up(self.spec.prev_nc, 4), dtype=torch.float32, device=device)
+
+    def frame(self, pose, prev, use_raw_only=False, need_flow=True):
+        """-> forward(full=True)'s (fake, raw, flow_w), the FIFO this frame read, the FIFO behind it"""
+        fake, raw, fw = self(pose, prev, use_raw_only=use_raw_only, full=True, need_flow=need_flow)
+        return fake, raw, fw, prev, shift(prev, fake)
+
 
 class TrainableLocalGenerator(TrainableGenerator):
     """CompositeLocalGenerator: the fine-scale enhancer netG{s >= 1}, fed by the coarse scale's two decoder
@@ -760,14 +781,6 @@ class TwoScaleGenerator(torch.nn.Module):
         return (torch.zeros(1, H, W, cs, dtype=torch.float32, device=device),
                 torch.zeros(1, H // 2, W // 2, cs, dtype=torch.float32, device=device))
 
-    @staticmethod
-    def shift(prev, frame):
-        """fake_B_prev = cat(fake_B_prev[1:], fake_B) on one scale's FIFO (n_frames_G 3), the new frame detached"""
-        new = torch.zeros_like(prev)
-        new[..., :3] = prev[..., 3:6]
-        new[..., 3:6] = frame.detach()[..., :3]
-        return new
-
     def forward(self, pose, prev, use_raw_only=False, need_flow=True):
         """pose [1,H,W,12]; prev = (fine FIFO, coarse FIFO) -> (fake, raw, flow_w) of the finest scale as
         TrainableGenerator.forward(full=True) returns them, the coarse scale's frame [1,H/2,W/2,4] (detached), and the pair of
@@ -780,7 +793,12 @@ class TwoScaleGenerator(torch.nn.Module):
         fake0, _, _, img_feat, flow_feat = self.G0(pose0, prev0, use_raw_only=use_raw_only, full=True, need_flow=need_flow,
                                                    feats=True)
         fake, raw, fw = self.G1(pose, prev1, img_feat, flow_feat, use_raw_only=use_raw_only, full=True, need_flow=need_flow)
-        return fake, raw, fw, fake0, (self.shift(prev1, fake), self.shift(prev0, fake0))
+        return fake, raw, fw, fake0, (shift(prev1, fake), shift(prev0, fake0))
+
+    def frame(self, pose, prev, use_raw_only=False, need_flow=True):
+        """TrainableGenerator.frame on the pair of FIFOs; the FIFO the frame read is the finest scale's: the losses read that scale"""
+        fake, raw, fw, _, behind = self(pose, prev, use_raw_only=use_raw_only, need_flow=need_flow)
+        return fake, raw, fw, prev[0], behind
 
 
 def global_generator_frozen(epoch, niter_fix_global):
@@ -943,6 +961,11 @@ def vgg_loss(vgg, fake, real, real_feats=None):
     return sum(wi * _L1.apply(a, b, a.numel()) for wi, a, b in zip(VGG_WEIGHTS, ff, fr))
 
 
+def _plus(total, term):
+    """total + term, where None is the empty sum (no `0.0 + term` node in the graph)"""
+    return term if total is None else total + term
+
+
 def gan_loss(pred_scales, target_is_real):
     return sum(_MseConst.apply(st[-1], 1.0 if target_is_real else 0.0) for st in pred_scales)
 
@@ -1073,6 +1096,18 @@ class LossBook:
         for j, k in enumerate(keys):
             res[k] = host[T + j]
         return res
+
+
+def read_losses(named, book):
+    """A step's reported losses, in `named`'s order -- the order the step built its terms in, whichever form built them.
+    named: {name: one-element device tensor | host number | None = `book` holds the terms of that name (or lists it in
+    zero_names)}.  One host read for the step (LossBook.read: the book's values and the device tensors together)."""
+    host = book.read({k: v for k, v in named.items() if torch.is_tensor(v)})
+    if host:
+        ops.check_async_errors()      # (the read-back above synchronised: errors the step's kernels could only flag)
+    for k in book.zero_names:
+        host.setdefault(k, 0.0)
+    return {k: host[k] if k in host else float(v) for k, v in named.items()}
 
 
 # ------------------------------------------------------------------------------------------------
@@ -1408,6 +1443,40 @@ class Vid2VidTrainer:
             rows.append(torch.cat(w + [torch.zeros(H, W, nz, dtype=torch.float32, device=dev)], -1))
         return torch.stack(rows).contiguous()
 
+    def _d_jobs(self, A3, real, fake, raw, face_boxes):
+        """The step's discriminator work, one job at a time: (net, [real input, fake input(, raw input)], (D, G_GAN,
+        G_GAN_Feat) names of the reported sums, face_weight) -- the image discriminator, the face discriminator where there are
+        boxes, every temporal scale that has a full window.  A generator: a job's inputs (autograd nodes on the generated
+        frames) are built when the caller asks for it, so whatever the caller builds between two jobs stays between them in the
+        graph; the sequence history is trimmed once the last job has been taken."""
+        F_ = real.shape[0]
+        # with a flow branch upstream scores fake_B_raw with the same discriminator (and VGG) as well
+        yield self.D, [self._d_input(A3, t) for t in (real, fake) + (() if raw is None else (raw,))], \
+            ("D", "G_GAN", "G_GAN_Feat"), 1.0
+        if self.Df is not None and face_boxes is not None:
+            def crop(t):
+                return torch.stack([t[i, b[0]:b[1], b[2]:b[3]] for i, b in enumerate(face_boxes)]).contiguous()
+            cA = crop(A3)
+            # face_weight = 2 on the generator's face terms [RECALL upstream Vid2VidModelD.forward]
+            yield self.Df, [self._d_input(cA, crop(real)), self._d_input(cA, crop(fake))], ("D_f", "G_f_GAN", "G_f_GAN_Feat"), 2.0
+        # temporal discriminators: every window (t-2d, t-d, t), d = n_frames_D**s, that ends on a frame of this chunk;
+        # older frames come from the sequence history (generated ones detached)
+        if self.DT:
+            n_old = len(self._hist_real)
+            reals = self._hist_real + [real[i] for i in range(F_)]
+            fks = self._hist_fake + [fake[i] for i in range(F_)]
+            for sc, dt in enumerate(self.DT):
+                d = self.tD ** sc
+                ends = [t for t in range(n_old, n_old + F_) if t - (self.tD - 1) * d >= 0]
+                if not ends:
+                    continue
+                flows = self._temporal_flows(reals, ends, d)
+                yield dt, [self._temporal_stack(frames, ends, d, dt, flows) for frames in (reals, fks)], \
+                    ("D_T%d" % sc, "G_T_GAN%d" % sc, "G_T_GAN_Feat%d" % sc), 1.0
+            keep = (self.tD - 1) * self.tD ** (len(self.DT) - 1)
+            self._hist_real = [r.detach() for r in reals][-keep:]
+            self._hist_fake = [f.detach() for f in fks][-keep:]
+
     def _d_pass(self, net, inputs, book, names, face_weight=1.0):
         """One discriminator on its real input and its one or two generated inputs (fake, raw) as ONE batch of passes
         (TrainableDiscriminator.forward(groups=...)): every layer is one conv launch, one data-gradient launch and one
@@ -1448,6 +1517,33 @@ class Vid2VidTrainer:
                         book.l1(n_feat, f[sl], f[:F_], fm_w, seed=gf[sl])
                     tG.append(f); sG.append(gf)
         return tG, sG, tD, sD
+
+    def _d_terms(self, net, inputs, face_weight, shared):
+        """_d_pass's test twin (T2V_D_BATCHED=0, which also serves T2V_D_SHARED_FWD=0): the same job one launch per pass and
+        per loss term, the scalar graph on autograd -> (G's GAN term, G's feature-matching term, D's term).
+        compute_loss_D(netD, real_A, real_B, fake) [RECALL upstream Vid2VidModelD]: real pass, fake pass on the detached
+        frame (D's loss), fake pass for G's GAN + feature-matching loss with D's parameters detached (only their data gradient
+        is wanted).  shared: one forward on a generated input serves both losses, as in _d_pass; the running statistics
+        still move twice.  A second generated input (raw) adds its terms to the first's, and the real term once more: upstream's
+        second real pass returns the values of the first (same weights, same batch)."""
+        opt = self.opt
+        pr = net(inputs[0])
+        d_real = d_fake = g_gan = g_fm = None
+        for x in inputs[1:]:
+            if shared:
+                with bn_updates(2):
+                    pfd = pfg = net(x)
+            else:
+                pfd, pfg = net(x.detach()), net(x, frozen=True)
+            d_real, d_fake = _plus(d_real, gan_loss(pr, True)), _plus(d_fake, gan_loss(pfd, False))
+            g_gan = _plus(g_gan, gan_loss(pfg, True))
+            if not opt.no_ganFeat:
+                g_fm = _plus(g_fm, feature_matching_loss(pfg, pr, opt.n_layers_D, opt.lambda_feat))
+        if g_fm is None:
+            g_fm = 0.0
+        if face_weight != 1.0:
+            g_gan, g_fm = g_gan * face_weight, g_fm * face_weight
+        return g_gan, g_fm, 0.5 * (d_fake + d_real)
 
     def _d_backward_on_its_own_stream(self, outputs, seeds, d_params):
         """The discriminators' own backward pass (their LSGAN terms: seeds on the logits only) without the autograd engine:
@@ -1493,71 +1589,25 @@ class Vid2VidTrainer:
         side_gemm_hint()
         return side
 
-    def _train_step_batched(self, pose, real, face_boxes, prev, real_prev, flow_ref, conf_ref, first, fakes, raws, fws, prevs,
-                            fake, A3):
-        """The step from the generated frames on (default path): every discriminator runs its real / fake / raw passes as one
-        batch (_d_pass), the LSGAN and feature-matching terms are one launch (LossBook), and both backward passes start from
-        the terms' gradient seeds.  The flow / warp / weight and VGG terms stay scalar nodes of the autograd graph."""
-        opt, dev = self.opt, pose.device
-        F_, H, W = pose.shape[0], pose.shape[1], pose.shape[2]
-        flow_on = not self.spec.no_flow
-        book = self.book = getattr(self, "book", None) or LossBook(dev)
-        book.reset()
-        raw = torch.cat(raws, 0) if flow_on else None
-        fw_all = torch.cat(fws, 0) if (flow_on and real_prev is not None) else None
-        tG, sG, tD, sD = self._d_pass(self.D, [self._d_input(A3, real), self._d_input(A3, fake)]
-                                      + ([self._d_input(A3, raw)] if flow_on else []), book, ("D", "G_GAN", "G_GAN_Feat"))
-        rest, extra = None, {}          # the terms that stay on the scalar graph: their sum, their values
-        vgg_term = self._vgg_term(fake, raw, real)
-        if vgg_term is not None:
-            rest, extra["G_VGG"] = vgg_term, vgg_term
-        if flow_on and real_prev is not None:
-            flow_sum, flow_named = self._flow_terms(fake, fw_all, real, real_prev, prevs, flow_ref, conf_ref, first)
-            rest = flow_sum if rest is None else rest + flow_sum
-            extra.update(flow_named)
-        if self.Df is not None and face_boxes is not None:
-            def crop(t):
-                return torch.stack([t[i, b[0]:b[1], b[2]:b[3]] for i, b in enumerate(face_boxes)]).contiguous()
-            cA = crop(A3)
-            # face_weight = 2 on the generator's face terms [RECALL upstream Vid2VidModelD.forward]
-            a, b_, c, d = self._d_pass(self.Df, [self._d_input(cA, crop(real)), self._d_input(cA, crop(fake))], book,
-                                         ("D_f", "G_f_GAN", "G_f_GAN_Feat"), 2.0)
-            tG += a; sG += b_; tD += c; sD += d
-        # temporal discriminators: every window (t-2d, t-d, t), d = n_frames_D**s, that ends on a frame of this chunk;
-        # older frames come from the sequence history (generated ones detached)
-        if self.DT:
-            n_old = len(self._hist_real)
-            reals = self._hist_real + [real[i] for i in range(F_)]
-            fks = self._hist_fake + [fake[i] for i in range(F_)]
-            for sc, dt in enumerate(self.DT):
-                d_ = self.tD ** sc
-                ends = [t for t in range(n_old, n_old + F_) if t - (self.tD - 1) * d_ >= 0]
-                if not ends:
-                    continue
-
-                flows = self._temporal_flows(reals, ends, d_)
-
-                def stack(frames):
-                    return self._temporal_stack(frames, ends, d_, dt, flows)
-                a, b_, c, d = self._d_pass(dt, [stack(reals), stack(fks)], book,
-                                           ("D_T%d" % sc, "G_T_GAN%d" % sc, "G_T_GAN_Feat%d" % sc))
-                tG += a; sG += b_; tD += c; sD += d
-            keep = (self.tD - 1) * self.tD ** (len(self.DT) - 1)
-            self._hist_real = [r.detach() for r in reals][-keep:]
-            self._hist_fake = [f.detach() for f in fks][-keep:]
-        book.run()          # values and gradient seeds of all LSGAN / feature-matching terms: one launch
+    def _backward_and_update(self, tG, sG, tD, sD, off_in_g_pass):
+        """Both backward passes, the gradient exchange and both optimiser steps.  tG / sG: the tensors G's pass starts from and
+        their gradient seeds (None: a scalar), tD / sD: the same for D's pass; off_in_g_pass: the parameters whose gradients
+        are switched off during G's pass -- D's, wherever one D forward serves both losses.
+        The pass-by-pass form comes with ([loss_G], [None], [loss_D], [None], ...): a scalar loss is the result of a
+        multiplication or an addition, never of a _ConvBlock, so _d_backward_on_its_own_stream declines it before it touches
+        anything (its isinstance test on grad_fn) and D's pass takes the engine, whatever T2V_D_BWD_STREAM says."""
         g_params, d_params = self.optG.params, self.optD.params
+        # G's backward: the nodes deliver into bucketsG and launch its buckets' collectives as they complete; what is
+        # left goes out in absorb() -- all of it in flight under the discriminators' backward pass
         self.bucketsG.seal()
         self.bucketsD.seal()
-        if rest is not None and torch.is_tensor(rest) and rest.requires_grad:
-            tG, sG = tG + [rest], sG + [None]
         # D's loss reaches D's parameters through plain chains of _ConvBlock nodes (logits -> ... -> first layer, no data
         # gradient into the frames) and shares nothing with the generator's backward pass but the saved tensors both read:
         # with T2V_D_BWD_STREAM=1 the chains are walked by hand on a stream of their own BEFORE the generator's pass is
         # enqueued, so that the GPU runs them beside its first ~20 ms, which otherwise have no second queue (measured both
         # ways, off by default: DESIGN 6b "the discriminators' own backward pass beside the generator's")
         d_side = self._d_backward_on_its_own_stream(tD, sD, d_params)
-        with param_gradients_off(d_params):
+        with param_gradients_off(off_in_g_pass):
             gG = torch.autograd.grad(tG, g_params, grad_outputs=sG, retain_graph=True, allow_unused=True)
         gG = flush_pending_weight_gradients(g_params, gG)
         self.bucketsG.absorb(gG)
@@ -1567,27 +1617,18 @@ class Vid2VidTrainer:
         else:
             with input_gradients_off():      # D's loss: no data gradient into the (attached) generated frames
                 gD = torch.autograd.grad(tD, d_params, grad_outputs=sD, allow_unused=True)
-        gD = flush_pending_weight_gradients(d_params, gD)
+        gD = flush_pending_weight_gradients(d_params, gD)      # (a discriminator layer one of whose passes fed no loss term)
         self.bucketsD.absorb(gD)
-        if self.time_comm:
-            torch.cuda.synchronize()
+        if self.time_comm:       # T2V_TRAIN_COMM_TIMING=1: what of the exchange is still running once the backward kernels
+            torch.cuda.synchronize()      # have drained = its exposed (not hidden) part
         t0 = time.perf_counter()
         self.comm_bytes = self.bucketsG.finish() + self.bucketsD.finish()
         if self.time_comm and self.comm_bytes:
             torch.cuda.synchronize()
             self.comm_ms = 1e3 * (time.perf_counter() - t0)
-        check_presence_across_ranks([self.bucketsG, self.bucketsD], dev)
+        check_presence_across_ranks([self.bucketsG, self.bucketsD], tD[0].device)
         self.optG.step()
         self.optD.step()
-        losses = book.read({k: v for k, v in extra.items() if torch.is_tensor(v)})      # (the step's one host read)
-        losses.update({k: float(v) for k, v in extra.items() if not torch.is_tensor(v)})
-        for k in book.zero_names:
-            losses.setdefault(k, 0.0)
-        ops.check_async_errors()      # (the read-back above synchronised: errors the step's kernels could only flag)
-        # (reported in the order the one-term-per-launch path reports them)
-        order = ["G_GAN", "G_GAN_Feat", "D", "G_VGG", "F_Flow", "F_Warp", "W", "G_Warp", "G_f_GAN", "G_f_GAN_Feat", "D_f"] + \
-            [n % sc for sc in range(len(self.DT)) for n in ("G_T_GAN%d", "G_T_GAN_Feat%d", "D_T%d")]
-        return {k: losses[k] for k in order if k in losses}, prev
 
     def train_step(self, pose, real, face_boxes=None, prev=None, real_prev=None, flow_ref=None, conf_ref=None):
         """pose [F,H,W,12] (sliding windows), real [F,H,W,4] NHWC on the device; face_boxes: list of
@@ -1600,175 +1641,78 @@ class Vid2VidTrainer:
             return self._train_step(pose, real, face_boxes, prev, real_prev, flow_ref, conf_ref)
 
     def _train_step(self, pose, real, face_boxes, prev, real_prev=None, flow_ref=None, conf_ref=None):
-        opt, dev = self.opt, pose.device
+        dev = pose.device
         F_, H, W = pose.shape[0], pose.shape[1], pose.shape[2]
         self.bucketsG.begin_step()
         self.bucketsD.begin_step()
         flow_on = not self.spec.no_flow
         first = prev is None
-        if self.two_scale:
-            # `prev` is the pair (finest scale's FIFO, coarse scale's FIFO); every loss below reads the finest scale's frames
-            # only, `prevs` are its FIFOs
-            if first:
-                self.G.check_geometry(H, W)
-                prev = self.G.zero_prev(H, W, dev)
-        elif first:   # a new sequence starts: zero previous frames, raw-only first frame (--no_first_img)
-            prev = torch.zeros(1, H, W, ops.round_up(self.spec.prev_nc, 4), dtype=torch.float32, device=dev)
-        if first:
+        if first:   # a new sequence starts: zero previous frames, raw-only first frame (--no_first_img)
+            self.G.check_geometry(H, W)
+            prev = self.G.zero_prev(H, W, dev)
             self._hist_real, self._hist_fake = [], []
+        # `prev` is what the generator carries from frame to frame (two scales: the pair of FIFOs); `prevs` are the FIFOs the
+        # frames read at the finest scale, the scale every loss below reads
         fakes, raws, fws, prevs = [], [], [], []
         for f in range(F_):
-            if self.two_scale:
-                fk, rw, fw, _, nprev = self.G(pose[f:f + 1], prev, use_raw_only=first and f == 0,
-                                              need_flow=real_prev is not None)
-                fakes.append(fk)
-                raws.append(rw)
-                fws.append(fw)
-                prevs.append(prev[0])
-                prev = nprev
-                continue
-            fk, rw, fw = self.G(pose[f:f + 1], prev, use_raw_only=first and f == 0, full=True,
-                                need_flow=real_prev is not None)
+            fk, rw, fw, read, prev = self.G.frame(pose[f:f + 1], prev, use_raw_only=first and f == 0,
+                                                  need_flow=real_prev is not None)
             fakes.append(fk)
             raws.append(rw)
             fws.append(fw)
-            prevs.append(prev)
-            nprev = torch.zeros_like(prev)
-            nprev[..., :3] = prev[..., 3:6]
-            nprev[..., 3:6] = fk.detach()[..., :3]
-            prev = nprev
+            prevs.append(read)
         fake = torch.cat(fakes, 0)
+        raw = torch.cat(raws, 0) if flow_on else None
+        fw_all = torch.cat(fws, 0) if (flow_on and real_prev is not None) else None
         A3 = pose[..., 6:9]
         if self.keep_visuals:
             self.visuals = {"pose": pose[-1], "fake": fakes[-1][0].detach(), "real": real[-1],
                             "raw": (raws[-1] if raws[-1] is not None else fakes[-1])[0].detach()}
             if fws[-1] is not None:
                 self.visuals["fw"] = fws[-1][0].detach()
-        # compute_loss_D(netD, real_A, real_B, fake) [RECALL upstream Vid2VidModelD]: real pass, fake pass on the
-        # detached frame (D's loss), fake pass for G's GAN + feature-matching loss.  The generator-side passes run
-        # with D's parameters detached: only their data gradient is wanted.
-        # One forward on the fake frames serves both losses (T2V_D_SHARED_FWD=0: two forwards, as upstream runs them): D's
+        # One D forward on a generated input serves both losses (T2V_D_SHARED_FWD=0: two forwards, as upstream runs them): D's
         # loss reaches D's parameters through it, G's loss reaches the frames through it with D's parameter gradients
         # switched off for that backward pass (param_gradients_off) -- the same values either way, a D forward less per
-        # fake input.  The running statistics still move twice (upstream's two forwards).
+        # generated input.
         shared = switch("T2V_D_SHARED_FWD")
-        # T2V_D_BATCHED=0: one launch per pass and per loss term, the scalar graph on autograd (the form this path replaced;
-        # kept as its test twin)
+        # batched (the default): every discriminator runs its real / fake / raw passes as one batch (_d_pass), the LSGAN and
+        # feature-matching terms are one launch (LossBook), and both backward passes start from the terms' gradient seeds.
+        # T2V_D_BATCHED=0: one launch per pass and per loss term, the scalar graph on autograd (_d_terms; the form the batched
+        # one replaced, kept as its test twin).  The flow / warp / weight and VGG terms are scalar nodes of the graph in both.
         batched = shared and switch("T2V_D_BATCHED")
-        self._shared_d = shared
+        book = self.book = getattr(self, "book", None) or LossBook(dev)
+        book.reset()
+        tG, sG, tD, sD = [], [], [], []     # batched: the tensors the two backward passes start from, their gradient seeds
+        loss_G = loss_D = None              # the sums on the scalar graph
+        named = {}                          # what the step reports, in this order (read_losses)
+        for net, inputs, names, face_weight in self._d_jobs(A3, real, fake, raw, face_boxes):
+            if batched:
+                for have, new in zip((tG, sG, tD, sD), self._d_pass(net, inputs, book, names, face_weight)):
+                    have += new
+                g_gan = g_fm = l_d = None       # (the book has them)
+            else:
+                g_gan, g_fm, l_d = self._d_terms(net, inputs, face_weight, shared)
+                loss_G, loss_D = _plus(_plus(loss_G, g_gan), g_fm), _plus(loss_D, l_d)
+            n_d, n_gan, n_feat = names
+            named.update({n_gan: g_gan, n_feat: g_fm, n_d: l_d})
+            if net is not self.D:
+                continue
+            # behind the image discriminator and in front of the others: the generator's terms no discriminator is part of
+            vgg_term = self._vgg_term(fake, raw, real)
+            if vgg_term is not None:
+                loss_G, named["G_VGG"] = _plus(loss_G, vgg_term), vgg_term
+            if fw_all is not None:
+                flow_sum, flow_named = self._flow_terms(fake, fw_all, real, real_prev, prevs, flow_ref, conf_ref, first)
+                loss_G = _plus(loss_G, flow_sum)
+                named.update(flow_named)
         if batched:
-            return self._train_step_batched(pose, real, face_boxes, prev, real_prev, flow_ref, conf_ref, first, fakes, raws, fws,
-                                            prevs, fake, A3)
-
-        def d_fake(net, x_attached):
-            """-> (prediction for D's loss, prediction for G's loss)"""
-            if shared:
-                with bn_updates(2):
-                    pf = net(x_attached)
-                return pf, pf
-            return net(x_attached.detach()), net(x_attached, frozen=True)
-
-        pr = self.D(self._d_input(A3, real))
-        pfd, pfg = d_fake(self.D, self._d_input(A3, fake))
-        loss_D_real, loss_D_fake = gan_loss(pr, True), gan_loss(pfd, False)
-        loss_G_gan = gan_loss(pfg, True)
-        loss_G_fm = feature_matching_loss(pfg, pr, opt.n_layers_D, opt.lambda_feat) if not opt.no_ganFeat else 0.0
-        raw = fw_all = None
-        if flow_on:
-            # with a flow branch upstream scores fake_B_raw with the same discriminator (and VGG) as well; its second
-            # real pass returns the values of the first (same weights, same batch): that term is simply added again
-            raw = torch.cat(raws, 0)
-            fw_all = torch.cat(fws, 0) if real_prev is not None else None
-            pfd_r, pfg_r = d_fake(self.D, self._d_input(A3, raw))
-            loss_D_real = loss_D_real + gan_loss(pr, True)
-            loss_D_fake = loss_D_fake + gan_loss(pfd_r, False)
-            loss_G_gan = loss_G_gan + gan_loss(pfg_r, True)
-            if not opt.no_ganFeat:
-                loss_G_fm = loss_G_fm + feature_matching_loss(pfg_r, pr, opt.n_layers_D, opt.lambda_feat)
-        loss_D = 0.5 * (loss_D_fake + loss_D_real)
-        loss_G = loss_G_gan + loss_G_fm
-        loss_G_vgg = self._vgg_term(fake, raw if flow_on else None, real)
-        if loss_G_vgg is not None:
-            loss_G = loss_G + loss_G_vgg
-        def _f(t):   # kept on the device: one host read at the end of the step instead of a sync per loss term
-            return t.detach() if torch.is_tensor(t) else float(t)
-
-        losses = {"G_GAN": _f(loss_G_gan), "G_GAN_Feat": _f(loss_G_fm), "D": _f(loss_D)}
-        if loss_G_vgg is not None:
-            losses["G_VGG"] = _f(loss_G_vgg)
-        if flow_on and real_prev is not None:
-            flow_sum, flow_named = self._flow_terms(fake, fw_all, real, real_prev, prevs, flow_ref, conf_ref, first)
-            loss_G = loss_G + flow_sum
-            losses.update({k: _f(v) for k, v in flow_named.items()})
-        if self.Df is not None and face_boxes is not None:
-            def crop(t):
-                return torch.stack([t[i, b[0]:b[1], b[2]:b[3]] for i, b in enumerate(face_boxes)]).contiguous()
-            fr = self.Df(self._d_input(crop(A3), crop(real)))
-            ffd, ffg = d_fake(self.Df, self._d_input(crop(A3), crop(fake)))
-            loss_Df = 0.5 * (gan_loss(ffd, False) + gan_loss(fr, True))
-            # face_weight = 2 on the generator's face terms [RECALL upstream Vid2VidModelD.forward]
-            lg = gan_loss(ffg, True) * 2.0
-            lf = feature_matching_loss(ffg, fr, opt.n_layers_D, opt.lambda_feat) * 2.0 if not opt.no_ganFeat else 0.0
-            loss_G = loss_G + lg + lf
-            loss_D = loss_D + loss_Df
-            losses.update({"G_f_GAN": _f(lg), "G_f_GAN_Feat": _f(lf), "D_f": _f(loss_Df)})
-        # temporal discriminators: every window (t-2d, t-d, t), d = n_frames_D**s, that ends on a frame of this chunk;
-        # older frames come from the sequence history (generated ones detached)
-        if self.DT:
-            n_old = len(self._hist_real)
-            reals = self._hist_real + [real[i] for i in range(F_)]
-            fks = self._hist_fake + [fake[i] for i in range(F_)]
-            for sc, dt in enumerate(self.DT):
-                d = self.tD ** sc
-                ends = [t for t in range(n_old, n_old + F_) if t - (self.tD - 1) * d >= 0]
-                if not ends:
-                    continue
-                flows = self._temporal_flows(reals, ends, d)
-
-                def stack(frames):
-                    return self._temporal_stack(frames, ends, d, dt, flows)
-                tr, tf = stack(reals), stack(fks)
-                pr_t = dt(tr)
-                pfd_t, pfg_t = d_fake(dt, tf)
-                l_dt = 0.5 * (gan_loss(pfd_t, False) + gan_loss(pr_t, True))
-                lg = gan_loss(pfg_t, True)
-                lf = feature_matching_loss(pfg_t, pr_t, opt.n_layers_D, opt.lambda_feat) if not opt.no_ganFeat else 0.0
-                loss_G = loss_G + lg + lf
-                loss_D = loss_D + l_dt
-                losses.update({"G_T_GAN%d" % sc: _f(lg), "G_T_GAN_Feat%d" % sc: _f(lf), "D_T%d" % sc: _f(l_dt)})
-            keep = (self.tD - 1) * self.tD ** (len(self.DT) - 1)
-            self._hist_real = [r.detach() for r in reals][-keep:]
-            self._hist_fake = [f.detach() for f in fks][-keep:]
-        g_params = self.optG.params
-        d_params = self.optD.params
-        # G's backward: the nodes deliver into bucketsG and launch its buckets' collectives as they complete; what is
-        # left goes out in absorb() -- all of it in flight under the discriminators' backward pass
-        self.bucketsG.seal()
-        self.bucketsD.seal()
-        with param_gradients_off(d_params if getattr(self, "_shared_d", False) else []):
-            gG = torch.autograd.grad(loss_G, g_params, retain_graph=True, allow_unused=True)
-        gG = flush_pending_weight_gradients(g_params, gG)
-        self.bucketsG.absorb(gG)
-        with input_gradients_off():      # D's loss: no data gradient into the (attached) fake frames
-            gD = torch.autograd.grad(loss_D, d_params, allow_unused=True)
-        gD = flush_pending_weight_gradients(d_params, gD)      # (a discriminator layer one of whose passes fed no loss term)
-        self.bucketsD.absorb(gD)
-        if self.time_comm:       # T2V_TRAIN_COMM_TIMING=1: what of the exchange is still running once the backward kernels
-            torch.cuda.synchronize()      # have drained = its exposed (not hidden) part
-        t0 = time.perf_counter()
-        self.comm_bytes = self.bucketsG.finish() + self.bucketsD.finish()
-        if self.time_comm and self.comm_bytes:
-            torch.cuda.synchronize()
-            self.comm_ms = 1e3 * (time.perf_counter() - t0)
-        check_presence_across_ranks([self.bucketsG, self.bucketsD], dev)
-        self.optG.step()
-        self.optD.step()
-        keys = [k for k, v in losses.items() if torch.is_tensor(v)]
-        if keys:
-            for k, v in zip(keys, torch.stack([losses[k].reshape(()) for k in keys]).tolist()):
-                losses[k] = v
-            ops.check_async_errors()      # (the read-back above synchronised: errors the step's kernels could only flag)
-        return losses, prev
+            book.run()          # values and gradient seeds of all LSGAN / feature-matching terms: one launch
+            if torch.is_tensor(loss_G) and loss_G.requires_grad:
+                tG, sG = tG + [loss_G], sG + [None]
+        else:
+            tG, sG, tD, sD = [loss_G], [None], [loss_D], [None]
+        self._backward_and_update(tG, sG, tD, sD, self.optD.params if shared else [])
+        return read_losses(named, book), prev
 
     def update_learning_rate(self, epoch):
         """linear decay to zero over the niter_decay epochs after `niter` [RECALL upstream update_learning_rate]"""
