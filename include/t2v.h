@@ -649,6 +649,10 @@ int t2v_optical_flow(t2v_ctx* ctx, void* stream, const float* cur, int cur_cs, i
 int t2v_optical_flow_u8(t2v_ctx* ctx, void* stream, const uint8_t* cur, int cur_cs, const uint8_t* prev, int prev_cs, int H,
                         int W, int levels, int iters, int radius, float lambda, float* workspace, float* flow_out);
 
+/* t2v_optical_flow_refined / t2v_optical_flow_refined_u8 -- this estimate with a Horn-Schunck refinement at every pyramid
+ * level, which fills textureless regions (additive to ABI 22) -- are declared and defined in t2v_flow_refine.h, the header
+ * of libt2v_flow.so, a library of its own that links this one. */
+
 /* ------------------------------------------------------------------------------------------
  * Image resampling for the training loader (ABI 21): PIL's `Image.resize` of a clip's frames, the crop and
  * torchvision's ToTensor + Normalize(.5, .5) in ONE launch, bit for bit what the CPU path computes.

@@ -1,6 +1,6 @@
 """Time Vid2VidTrainer.train_step at config-5 size on one GPU (1 sequence per GPU, max_frames_per_gpu 2): generator
 (with the flow branch unless --no_flow) forward + backward, 2-scale discriminator (+ face discriminator), all losses,
-Adam.  Usage: train_bench.py [--size 512] [--iters 3] [--no_flow] [--vgg] [--no_face] [--flow_ref lk]"""
+Adam.  Usage: train_bench.py [--size 512] [--iters 3] [--no_flow] [--vgg] [--no_face] [--flow_ref lk|lkhs]"""
 import argparse, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -14,8 +14,9 @@ ap.add_argument("--frames", type=int, default=2)
 ap.add_argument("--iters", type=int, default=3)
 ap.add_argument("--no_flow", action="store_true")
 ap.add_argument("--no_face", action="store_true")
-ap.add_argument("--flow_ref", default="zero", choices=["zero", "lk"], help="train.py's --flow_ref: lk = the reference flow of the "
-                "flow / warp losses is ops.optical_flow of the real frames (one call per frame) instead of zero")
+ap.add_argument("--flow_ref", default="zero", choices=["zero", "lk", "lkhs"], help="train.py's --flow_ref: lk = the reference flow "
+                "of the flow / warp losses is ops.optical_flow of the real frames (one call per frame) instead of zero; lkhs = "
+                "that flow with the Horn-Schunck refinement (64 steps per level, alpha 0.2)")
 ap.add_argument("--vgg", action="store_true", help="add the VGG19 perceptual loss (seeded random weights)")
 ap.add_argument("--aten_stacks", action="store_true", help="one step under torch.profiler: where the ATen fills / adds / "
                 "copies of the step come from (python call sites, by count)")
@@ -99,7 +100,7 @@ if args.host_time:
           % (1e3 * sum(m - s0 for m, s0 in zip(host_marks, starts)) / len(starts), dt * 1e3))
 print("train step %dx%d, %d frames, %s%s%s%s: %.1f ms/step (median %.2f, min %.2f, max %.2f of %d; %s MHz), peak mem %.1f GB | %s"
       % (H, W, F, "no flow" if args.no_flow else "flow branch on", "" if args.no_face else " + face D", " + VGG" if args.vgg else "",
-         ", --flow_ref lk" if args.flow_ref == "lk" else "", dt * 1e3, np.median(per_step), per_step.min(), per_step.max(),
+         ", --flow_ref %s" % args.flow_ref if args.flow_ref != "zero" else "", dt * 1e3, np.median(per_step), per_step.min(), per_step.max(),
          len(per_step), clock.mean_mhz(), torch.cuda.max_memory_allocated() / 2**30, " ".join("%s %.3f" % kv for kv in losses.items())))
 if args.cprofile:
     import cProfile, pstats, io

@@ -71,15 +71,18 @@ def _decoded_pairs(pairs, dir_a, dir_b, device, gpu_decode, fallback):
             yield rel, tensors[j], tensors[len(batch) + j]
 
 
-def compare_trees(dir_a, dir_b, pattern="fake_B_*", device="cuda:0", temporal=False, gpu_decode=False, fallback=None):
+def compare_trees(dir_a, dir_b, pattern="fake_B_*", device="cuda:0", temporal=False, gpu_decode=False, fallback=None,
+                  temporal_flow="lk"):
     """-> the report: {"definition", "overall", "sequences": {dir: summary}, "unpaired_a", "unpaired_b", "size_mismatch"};
     temporal: every summary gains "temporal" (metrics.pool_temporal over the directory's consecutive pairs), the report
-    "temporal_definition" and "temporal_skipped" (second files of pairs that changed size or are narrower than 8 pixels).
+    "temporal_definition", "temporal_flow" (the estimator: lk, or lkhs = ops.optical_flow_u8 with the Horn-Schunck refinement)
+    and "temporal_skipped" (second files of pairs that changed size or are narrower than 8 pixels).
     gpu_decode: decode on the GPU (the same report); `fallback`, a list, receives (file, reason) of what Pillow decoded then"""
     from ._xp import torch
     from . import metrics as M
     from . import ops
     pairs, only_a, only_b = pair_files(dir_a, dir_b, pattern)
+    flow_kw = ops.temporal_flow_kwargs(temporal_flow)
     per_seq, mismatch, pending = {}, [], []
     t_pending, t_skipped, last = [], [], None      # last: (directory, device a, device b) of the previous paired file
     for rel, a, b in _decoded_pairs(pairs, dir_a, dir_b, device, gpu_decode, [] if fallback is None else fallback):
@@ -97,8 +100,8 @@ def compare_trees(dir_a, dir_b, pattern="fake_B_*", device="cuda:0", temporal=Fa
                     t_skipped.append(rel)
                 else:
                     pa, pb = last[1], last[2]
-                    trow = ops.temporal_metrics(da, pa, db, pb, ops.optical_flow_u8(db, pb), ops.optical_flow_u8(pb, db),
-                                                ops.optical_flow_u8(da, pa))
+                    trow = ops.temporal_metrics(da, pa, db, pb, ops.optical_flow_u8(db, pb, **flow_kw),
+                                                ops.optical_flow_u8(pb, db, **flow_kw), ops.optical_flow_u8(da, pa, **flow_kw))
                     t_pending.append((seq, a.shape[0] * a.shape[1], trow))
             last = (seq, da, db)
     for rel, n_values, row in pending:       # (the copies wait for the GPU once everything is enqueued)
@@ -115,7 +118,8 @@ def compare_trees(dir_a, dir_b, pattern="fake_B_*", device="cuda:0", temporal=Fa
         rep["overall"]["temporal"] = M.pool_temporal([p for parts in t_seq.values() for p in parts])
         for seq, summary in rep["sequences"].items():
             summary["temporal"] = M.pool_temporal(t_seq.get(seq, []))
-        rep["temporal_definition"], rep["temporal_skipped"] = ops.TEMPORAL_DEFINITION, t_skipped
+        rep["temporal_definition"], rep["temporal_skipped"] = ops.temporal_definition(temporal_flow), t_skipped
+        rep["temporal_flow"] = temporal_flow
     return rep
 
 
@@ -129,6 +133,8 @@ def main(argv=None):
     ap.add_argument("dir_b")
     ap.add_argument("--pattern", default="fake_B_*", help="shell pattern the files' base names must match")
     ap.add_argument("--temporal", action="store_true", help="add warping error, tOF and the flicker term of consecutive files")
+    ap.add_argument("--temporal_flow", default=None, choices=["lk", "lkhs"], help="with --temporal: the flow estimator, lk "
+                    "(default) or lkhs = with the Horn-Schunck refinement; named in the report")
     ap.add_argument("--gpu_decode", action="store_true", help="decode the JPEG files on the GPU, in batches (the same report)")
     ap.add_argument("--json", default=None, metavar="OUT", help="write the report to this file")
     ap.add_argument("--gpu_ids", default="0")
@@ -136,12 +142,14 @@ def main(argv=None):
     for d in (args.dir_a, args.dir_b):
         if not os.path.isdir(d):
             ap.error("%s is not a directory" % d)
+    if args.temporal_flow is not None and not args.temporal:
+        ap.error("--temporal_flow %s: the estimator of --temporal, which is not given" % args.temporal_flow)
     if os.environ.get("T2V_LEAN", "1") != "0":
         from . import _xp
         _xp.use_lean()          # no torch needed for an allocator and a stream (honoured when torch is not loaded yet)
     fallback = []
     rep = compare_trees(args.dir_a, args.dir_b, args.pattern, "cuda:%d" % int(str(args.gpu_ids).split(",")[0]), args.temporal,
-                        args.gpu_decode, fallback)
+                        args.gpu_decode, fallback, **({"temporal_flow": args.temporal_flow} if args.temporal_flow else {}))
     if fallback:
         print("--gpu_decode: Pillow decoded %d file(s), the first: %s (%s)" % ((len(fallback),) + fallback[0]), file=sys.stderr)
     for seq, s in list(rep["sequences"].items()) + [("overall", rep["overall"])]:

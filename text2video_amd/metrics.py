@@ -89,8 +89,10 @@ class SequenceRows:
     temporal=True, two of ops.temporal_metrics per frame after the first (--metrics_temporal).  Both kinds live in ONE buffer
     (`buf`: the [2n,4] picture rows, then the [2n,6] temporal rows), which goes to the host in one copy when the sequence ends."""
 
-    def __init__(self, torch, seq, capacity, device, temporal=False):
+    def __init__(self, torch, seq, capacity, device, temporal=False, temporal_flow="lk"):
         self.seq, self.capacity, self.temporal = seq, capacity, bool(temporal)
+        self.temporal_flow = temporal_flow                              # --temporal_flow: lk, or lkhs = the refined estimate
+        self._flow_kw = ops.temporal_flow_kwargs(temporal_flow)
         n = 2 * capacity
         if self.temporal:
             self.buf = torch.empty(n * (4 + ops.TEMPORAL_COLUMNS), dtype=torch.float64, device=device)
@@ -117,9 +119,9 @@ class SequenceRows:
                 if self.flows is None or tuple(self.flows[0].shape[:2]) != tuple(fake_u8.shape[:2]):
                     self.flows = [self._torch.empty(fake_u8.shape[0], fake_u8.shape[1], 4, dtype=self._torch.float32,
                                                     device=fake_u8.device) for _ in range(3)]
-                fwd = ops.optical_flow_u8(real_u8, prev_real, out=self.flows[0])        # real t -> t-1
-                bwd = ops.optical_flow_u8(prev_real, real_u8, out=self.flows[1])        # real t-1 -> t
-                gen = ops.optical_flow_u8(fake_u8, prev_fake, out=self.flows[2])        # generated t -> t-1
+                fwd = ops.optical_flow_u8(real_u8, prev_real, out=self.flows[0], **self._flow_kw)        # real t -> t-1
+                bwd = ops.optical_flow_u8(prev_real, real_u8, out=self.flows[1], **self._flow_kw)        # real t-1 -> t
+                gen = ops.optical_flow_u8(fake_u8, prev_fake, out=self.flows[2], **self._flow_kw)        # generated t -> t-1
                 ops.temporal_metrics(fake_u8, prev_fake, real_u8, prev_real, fwd, bwd, gen, boxes, out=self.trows,
                                      out_row=2 * len(self.frames))
             self.prev = (fake_u8, real_u8)
@@ -167,9 +169,10 @@ def pool_temporal(parts):
     return out
 
 
-def summarise(frames, rows, trows=None):
+def summarise(frames, rows, trows=None, temporal_flow="lk"):
     """frames: [(name, (H, W), face box or None)]; rows: host array [2 * len(frames), 4]; trows: host array
-    [2 * len(frames), 6] of the temporal rows (frame 0's are not read) or None -> the metrics.json document"""
+    [2 * len(frames), 6] of the temporal rows (frame 0's are not read) or None -> the metrics.json document, whose
+    "temporal_definition" names the flow estimator the rows were taken with (temporal_flow)"""
     out, whole, faces, t_whole, t_faces = [], [], [], [], []
     for j, (name, (H, W), face) in enumerate(frames):
         s = ops.metrics_summary(rows[2 * j], 3 * H * W)
@@ -197,7 +200,7 @@ def summarise(frames, rows, trows=None):
     if trows is not None:
         summary["temporal"] = pool_temporal(t_whole)
         summary["temporal"]["face"] = pool_temporal(t_faces)
-        doc["temporal_definition"] = ops.TEMPORAL_DEFINITION
+        doc["temporal_definition"] = ops.temporal_definition(temporal_flow)
     return doc
 
 

@@ -290,7 +290,8 @@ def run_test(opt, model=None, device=None, dataset=None):
                                  % ((data["A_path"],) + real.shape[:2] + tuple(u8.shape[:2])))
             if L.metrics is None or L.metrics.seq != data["seq"]:
                 close_metrics(L)
-                L.metrics = M.SequenceRows(torch, data["seq"], dataset.seq_lengths()[data["seq"]], dev, want_temporal)
+                L.metrics = M.SequenceRows(torch, data["seq"], dataset.seq_lengths()[data["seq"]], dev, want_temporal,
+                                            getattr(opt, "temporal_flow", None) or "lk")
             ring = pinned.get((k, "real") + real.shape)
             if ring is None:
                 ring = pinned[(k, "real") + real.shape] = \
@@ -452,7 +453,7 @@ def run_test(opt, model=None, device=None, dataset=None):
         real_frames.close()
         for ev, host, rows in seq_metrics:       # <results>/<seq>/metrics.json, by the process that generated the sequence
             ev.synchronize()
-            doc = M.summarise(rows.frames, *rows.split_host(host.numpy()))
+            doc = M.summarise(rows.frames, *rows.split_host(host.numpy()), temporal_flow=rows.temporal_flow)
             M.write_json(os.path.join(vis.save_dir, rows.seq, "metrics.json"), doc)
             metrics_out[rows.seq] = doc["summary"]
     marks["to_last_jpeg_s"] = time.perf_counter() - t_start

@@ -10,7 +10,7 @@ import ctypes
 
 from ._xp import torch     # the real torch, or leantorch under vid2vid/test.py's torch-free frame loop
 
-from . import _lib
+from . import _flowlib, _lib
 from ._lib import (ACT_FLOW_W, ACT_LRELU, ACT_NONE, ACT_TANH, ALGO_DIRECT, ALGO_WINOGRAD,  # noqa: F401
                    ALGO_DIRECT_BF16X2, ALGO_POLYPHASE, ALGO_POLYPHASE_BF16X2, ALGO_WINOGRAD_F4, ALGO_WINOGRAD_F4_BF16X2, PAD_REFLECT, PAD_ZERO, VISUALS_FLOW, VISUALS_IMAGE, VISUALS_MAX_PANELS,
                    VISUALS_UNIT, ConvDesc, check)
@@ -494,22 +494,50 @@ def flow_warp_composite_backward(d_out, d_warp, raw, fw, prev, prev_c0, want_d_p
     return d_raw, d_fw, d_prev
 
 
-_flow_workspaces = {}      # (device, H, W, levels) -> workspace of optical_flow
+_flow_workspaces = {}      # (device, H, W, levels, refined) -> workspace of optical_flow
+FLOW_ALPHA = 0.2           # the smoothness weight and the Jacobi steps per level the documents' figures were taken with
+FLOW_REFINE_ITERS = 64
+TEMPORAL_FLOWS = ("lk", "lkhs")
 
 
-def optical_flow_workspace(H, W, levels=None, device=None):
-    """A workspace optical_flow accepts for this geometry (one call at a time may use it)."""
-    n = int(_lib.load().t2v_optical_flow_workspace_floats(H, W, int(levels or 0)))
+def optical_flow_workspace(H, W, levels=None, device=None, refined=False):
+    """A workspace optical_flow accepts for this geometry (one call at a time may use it); refined: one that a call with
+    refine_iters > 0 accepts as well (t2v_optical_flow_refined_workspace_floats)."""
+    n = int((_flowlib.load().t2v_optical_flow_refined_workspace_floats if refined
+             else _lib.load().t2v_optical_flow_workspace_floats)(H, W, int(levels or 0)))
     if n == 0:
         raise ValueError("optical_flow: unsupported size %d x %d or level count %r" % (H, W, levels))
     return torch.empty(n, dtype=torch.float32, device=device)
 
 
-def optical_flow(cur, prev, cur_c0=0, prev_c0=0, levels=None, iters=3, radius=3, lam=1e-3, out=None, workspace=None):
+def _flow_workspace(c, name, like, H, W, levels, refined, workspace, strict):
+    """the workspace a flow call hands the library: the caller's (checked), the cached one of the geometry, or -- for a shape
+    the library refuses -- any pointer (it says so itself: nothing is launched, the pointer is not read)"""
+    lv = int(levels or 0)
+    need = (_flowlib.load().t2v_optical_flow_refined_workspace_floats if refined
+            else c.lib.t2v_optical_flow_workspace_floats)(H, W, lv)
+    if workspace is None:
+        key = (like.device, H, W, lv, bool(refined))
+        workspace = _flow_workspaces.get(key)
+        if workspace is None and need:
+            workspace = _flow_workspaces[key] = optical_flow_workspace(H, W, levels, like.device, refined)
+    elif strict and not (workspace.is_cuda and workspace.dtype == torch.float32 and workspace.is_contiguous()):
+        raise ValueError("%s: workspace must be a contiguous fp32 device tensor of the stated size" % name)
+    elif workspace.numel() < need:
+        raise ValueError("%s: workspace %s" % (name, "must be a contiguous fp32 device tensor of the stated size" if strict
+                                               else "too small"))
+    return like if workspace is None else workspace
+
+
+def optical_flow(cur, prev, cur_c0=0, prev_c0=0, levels=None, iters=3, radius=3, lam=1e-3, out=None, workspace=None,
+                 refine_iters=0, alpha=FLOW_ALPHA, iters_per_launch=0):
     """Dense optical flow from cur to prev (t2v_optical_flow: coarse-to-fine iterative Lucas-Kanade on the grey images):
     cur [H,W,cs], prev [H,W,cs'] NHWC, three channels from cur_c0 / prev_c0 -> [H,W,4] = (u, v, 0, 0) in pixels with
     cur(x, y) ~ prev(x + u, y + v), the flow flow_warp takes.  levels None: the default rule (include/t2v.h).  The
-    workspace is cached per geometry when none is given (calls on one stream follow each other, so they may share it)."""
+    workspace is cached per geometry when none is given (calls on one stream follow each other, so they may share it).
+    refine_iters > 0: t2v_optical_flow_refined (libt2v_flow.so, include/t2v_flow_refine.h) -- every level's LK estimate goes through that many Horn-Schunck Jacobi
+    steps with smoothness weight alpha, which fills textureless regions; iters_per_launch (0: the library's choice) never
+    changes the result.  refine_iters = 0 (the default) is the LK entry itself."""
     c = context()
     _chk(cur, "cur")
     _chk(prev, "prev")
@@ -517,25 +545,24 @@ def optical_flow(cur, prev, cur_c0=0, prev_c0=0, levels=None, iters=3, radius=3,
     if cur.dim() != 3 or prev.dim() != 3 or prev.shape[:2] != cur.shape[:2]:
         raise ValueError("optical_flow: cur and prev must be [H,W,C] of one size")
     lv = int(levels or 0)
-    if workspace is None:
-        key = (cur.device, H, W, lv)
-        workspace = _flow_workspaces.get(key)
-        if workspace is None and c.lib.t2v_optical_flow_workspace_floats(H, W, lv):
-            workspace = _flow_workspaces[key] = optical_flow_workspace(H, W, levels, cur.device)
-    elif workspace.numel() < c.lib.t2v_optical_flow_workspace_floats(H, W, lv):
-        raise ValueError("optical_flow: workspace too small")
-    if workspace is None:      # a shape the library refuses: let it say so (nothing is launched, the pointer is not read)
-        workspace = cur
+    refined = int(refine_iters) != 0 or int(iters_per_launch) != 0 or float(alpha) != FLOW_ALPHA
+    workspace = _flow_workspace(c, "optical_flow", cur, H, W, levels, int(refine_iters) > 0, workspace, False)
     out = torch.empty(H, W, 4, dtype=torch.float32, device=cur.device) if out is None else out
-    check(c.lib.t2v_optical_flow(c.handle, _stream(), _p(cur), cur.shape[-1], cur_c0, _p(prev), prev.shape[-1], prev_c0,
-                                 H, W, lv, int(iters), int(radius), float(lam), _p(workspace), _p(out)), "optical_flow")
+    if refined:
+        check(_flowlib.load().t2v_optical_flow_refined(c.handle, _stream(), _p(cur), cur.shape[-1], cur_c0, _p(prev), prev.shape[-1],
+                                             prev_c0, H, W, lv, int(iters), int(radius), float(lam), float(alpha),
+                                             int(refine_iters), int(iters_per_launch), _p(workspace), _p(out)), "optical_flow")
+    else:
+        check(c.lib.t2v_optical_flow(c.handle, _stream(), _p(cur), cur.shape[-1], cur_c0, _p(prev), prev.shape[-1], prev_c0,
+                                     H, W, lv, int(iters), int(radius), float(lam), _p(workspace), _p(out)), "optical_flow")
     return out
 
 
-def optical_flow_u8(cur, prev, levels=None, iters=3, radius=3, lam=1e-3, out=None, workspace=None):
+def optical_flow_u8(cur, prev, levels=None, iters=3, radius=3, lam=1e-3, out=None, workspace=None, refine_iters=0,
+                    alpha=FLOW_ALPHA, iters_per_launch=0):
     """optical_flow on the delivered bytes (t2v_optical_flow_u8): cur, prev uint8 device images [H,W,3 or 4] (channels 0..2,
     the stride chosen per image) -> [H,W,4] = (u, v, 0, 0), bit for bit optical_flow on the fp32 images pose_u8_to_f32 makes
-    of the same bytes.  Workspace, level rule and refusals as optical_flow; the flows are finite."""
+    of the same bytes.  Workspace, level rule, refinement arguments and refusals as optical_flow; the flows are finite."""
     c = context()
     for t, name in ((cur, "cur"), (prev, "prev")):
         if not (t.is_cuda and t.dtype == torch.uint8 and t.is_contiguous() and t.dim() == 3):
@@ -544,23 +571,27 @@ def optical_flow_u8(cur, prev, levels=None, iters=3, radius=3, lam=1e-3, out=Non
     if tuple(prev.shape[:2]) != (H, W):
         raise ValueError("optical_flow_u8: cur and prev must be [H,W,C] of one size")
     lv = int(levels or 0)
-    need = c.lib.t2v_optical_flow_workspace_floats(H, W, lv)
-    if workspace is None:
-        key = (cur.device, H, W, lv)
-        workspace = _flow_workspaces.get(key)
-        if workspace is None and need:
-            workspace = _flow_workspaces[key] = optical_flow_workspace(H, W, levels, cur.device)
-    elif not (workspace.is_cuda and workspace.dtype == torch.float32 and workspace.is_contiguous()) or workspace.numel() < need:
-        raise ValueError("optical_flow_u8: workspace must be a contiguous fp32 device tensor of the stated size")
-    if workspace is None:      # a shape the library refuses: let it say so (nothing is launched, the pointer is not read)
-        workspace = cur
+    refined = int(refine_iters) != 0 or int(iters_per_launch) != 0 or float(alpha) != FLOW_ALPHA
+    workspace = _flow_workspace(c, "optical_flow_u8", cur, H, W, levels, int(refine_iters) > 0, workspace, True)
     out = torch.empty(H, W, 4, dtype=torch.float32, device=cur.device) if out is None else out
     _chk(out, "out")
     if tuple(out.shape) != (H, W, 4):
         raise ValueError("optical_flow_u8: out must be [H,W,4]")
-    check(c.lib.t2v_optical_flow_u8(c.handle, _stream(), _p(cur), cur.shape[2], _p(prev), prev.shape[2], H, W, lv, int(iters),
-                                    int(radius), float(lam), _p(workspace), _p(out)), "optical_flow_u8")
+    if refined:
+        check(_flowlib.load().t2v_optical_flow_refined_u8(c.handle, _stream(), _p(cur), cur.shape[2], _p(prev), prev.shape[2], H, W, lv,
+                                                int(iters), int(radius), float(lam), float(alpha), int(refine_iters),
+                                                int(iters_per_launch), _p(workspace), _p(out)), "optical_flow_u8")
+    else:
+        check(c.lib.t2v_optical_flow_u8(c.handle, _stream(), _p(cur), cur.shape[2], _p(prev), prev.shape[2], H, W, lv, int(iters),
+                                        int(radius), float(lam), _p(workspace), _p(out)), "optical_flow_u8")
     return out
+
+
+def temporal_flow_kwargs(choice):
+    """--temporal_flow {lk, lkhs} -> the refinement arguments of the optical_flow_u8 calls behind the temporal metrics"""
+    if choice not in TEMPORAL_FLOWS:
+        raise ValueError("temporal flow %r: one of %s" % (choice, ", ".join(TEMPORAL_FLOWS)))
+    return dict(refine_iters=FLOW_REFINE_ITERS, alpha=FLOW_ALPHA) if choice == "lkhs" else {}
 
 
 def avgpool3x3s2(x):
@@ -984,6 +1015,18 @@ TEMPORAL_DEFINITION = ("warp_mse = mean squared error (8-bit units) between fram
                        "warp_mse_real = the same on the real pair (the floor); tof = mean endpoint error in px between the "
                        "generated pair's flow and the real pair's; tdiff_mse = mean ((a_t - a_t-1) - (b_t - b_t-1))^2; flows: "
                        "ops.optical_flow_u8 (coarse-to-fine Lucas-Kanade), float64 sums")
+
+
+def temporal_definition(flow="lk"):
+    """TEMPORAL_DEFINITION with the flow estimator of the choice named (lk: the text as it is)"""
+    if flow == "lk":
+        return TEMPORAL_DEFINITION
+    temporal_flow_kwargs(flow)
+    return TEMPORAL_DEFINITION.replace("(coarse-to-fine Lucas-Kanade)", "with refine_iters=%d, alpha=%g (coarse-to-fine Lucas-Kanade "
+                                       "refined by Horn-Schunck steps at every level: --temporal_flow lkhs)"
+                                       % (FLOW_REFINE_ITERS, FLOW_ALPHA))
+
+
 TEMPORAL_COLUMNS = 6       # n_valid, warp_sse_a, warp_sse_b, n_flow, epe_sum, tdiff_sse
 
 

@@ -150,6 +150,9 @@ class TestOptions(BaseOptions):
           "temporal-consistency figures of the pair (t-1, t) against the real pair (ops.optical_flow_u8 + ops.temporal_metrics): "
           "warping error under the real flow's forward-backward mask, tOF, and the flow-free flicker term, under "
           "\"temporal\" in metrics.json and --timing_json")
+        g("--temporal_flow", type=str, default=None, choices=["lk", "lkhs"], help="with --metrics_temporal: the flow estimator, "
+          "lk (default) = ops.optical_flow_u8 as it is, lkhs = with the Horn-Schunck refinement (64 steps per level, alpha 0.2); "
+          "the choice is named in the reports")
 
         g("--gpu_jpeg", action="store_true", help="encode fake_B_*.jpg / real_A_*.jpg on the GPU (ops.jpeg_encode_u8: the "
           "bytes Pillow writes) instead of copying every frame to the host and encoding it on threads there")
@@ -161,6 +164,10 @@ class TestOptions(BaseOptions):
             self.parser.error("--jpeg_quality %d: the quality of --gpu_jpeg, which is not given" % opt.jpeg_quality)
         if opt.jpeg_quality is not None and not 1 <= opt.jpeg_quality <= 100:
             self.parser.error("--jpeg_quality %d is not in 1..100" % opt.jpeg_quality)
+        if opt.temporal_flow is not None and not opt.metrics_temporal:
+            self.parser.error("--temporal_flow %s: the estimator of --metrics_temporal, which is not given" % opt.temporal_flow)
+        if opt.temporal_flow is None:
+            opt.temporal_flow = "lk"
         if opt.metrics_temporal:
             opt.metrics = True
         if opt.metrics and opt.shard_chunks:
@@ -182,6 +189,19 @@ class TrainOptions(BaseOptions):
         if opt.gpu_decode and not (opt.train_loader == "prefetch" and opt.gpu_resize):
             self.parser.error("--gpu_decode: the decoder in front of --train_loader prefetch --gpu_resize, which %s not given"
                               % ("are" if opt.train_loader != "prefetch" and not opt.gpu_resize else "is"))
+        if opt.flow_refine_iters is not None and opt.flow_ref != "lkhs":
+            self.parser.error("--flow_refine_iters %d: the Jacobi steps of --flow_ref lkhs, which is not given"
+                              % opt.flow_refine_iters)
+        if opt.flow_alpha is not None and opt.flow_ref != "lkhs":
+            self.parser.error("--flow_alpha %g: the smoothness weight of --flow_ref lkhs, which is not given" % opt.flow_alpha)
+        if opt.flow_refine_iters is not None and not 1 <= opt.flow_refine_iters <= 1024:
+            self.parser.error("--flow_refine_iters %d is not in 1..1024" % opt.flow_refine_iters)
+        if opt.flow_alpha is not None and not 0 < opt.flow_alpha < float("inf"):
+            self.parser.error("--flow_alpha %g is not a positive finite number" % opt.flow_alpha)
+        if opt.flow_refine_iters is None:
+            opt.flow_refine_iters = 64
+        if opt.flow_alpha is None:
+            opt.flow_alpha = 0.2
         return opt
 
     def extra(self):
@@ -215,9 +235,15 @@ class TrainOptions(BaseOptions):
         g("--lambda_T", type=float, default=10.0)
         g("--no_ganFeat", action="store_true")
         g("--no_vgg", action="store_true")
-        g("--flow_ref", type=str, default="zero", choices=["zero", "lk"], help="reference flow of the flow / warp losses and "
-          "the temporal discriminators' flow channels when the caller passes none (upstream: FlowNet2, not available): zero "
-          "flow, or lk = the dense Lucas-Kanade estimate between the real frames (ops.optical_flow)")
+        g("--flow_ref", type=str, default="zero", choices=["zero", "lk", "lkhs"], help="reference flow of the flow / warp losses "
+          "and the temporal discriminators' flow channels when the caller passes none (upstream: FlowNet2, not available): "
+          "zero flow, lk = the dense Lucas-Kanade estimate between the real frames (ops.optical_flow), or lkhs = that "
+          "estimate with a Horn-Schunck refinement at every pyramid level, which fills textureless regions "
+          "(ops.optical_flow(..., refine_iters=N))")
+        g("--flow_refine_iters", type=int, default=None, help="with --flow_ref lkhs: Jacobi steps per pyramid level, 1..1024 "
+          "(default 64)")
+        g("--flow_alpha", type=float, default=None, help="with --flow_ref lkhs: the smoothness weight alpha, grey values in "
+          "[-1, 1] (default 0.2)")
         g("--train_loader", type=str, default="sync", choices=["sync", "prefetch"], help="sync: every clip is read, "
           "rasterised and resized on the main thread between optimiser steps; prefetch: the same clips prepared ahead by "
           "--nThreads rasteriser processes and decoder threads (TrainPoseDataset.iter_clips) and uploaded from pinned "

@@ -1282,8 +1282,13 @@ class Vid2VidTrainer:
                                                                                   opt.norm, seed + 10 + s),
                                                   opt.ndf, opt.n_layers_D, opt.num_D, opt.norm, device))
         self._hist_real, self._hist_fake = [], []    # frames of the running sequence (fakes detached)
-        # where the reference flow comes from when the caller passes none: "zero", or "lk" = ops.optical_flow on the real frames
+        # where the reference flow comes from when the caller passes none: "zero", "lk" = ops.optical_flow on the real frames,
+        # or "lkhs" = the same with the Horn-Schunck refinement (--flow_refine_iters steps per level, --flow_alpha)
         self.flow_ref_mode = getattr(opt, "flow_ref", "zero")
+        self._flow_kw = {}
+        if self.flow_ref_mode == "lkhs":
+            self._flow_kw = dict(refine_iters=int(getattr(opt, "flow_refine_iters", None) or 64),
+                                 alpha=float(getattr(opt, "flow_alpha", None) or 0.2))
         d_params = list(self.D.parameters()) + (list(self.Df.parameters()) if self.Df else [])
         for dt in self.DT:
             d_params += list(dt.parameters())
@@ -1382,14 +1387,15 @@ class Vid2VidTrainer:
         #   W      = MaskedL1(weight, 0, conf)  (--no_first_img)    G_Warp = MaskedL1(fake_B, resample(fake_B_prev, flow_ref), conf) * lambda_T
         # flow_ref / conf_ref come from FlowNet2 upstream; here they are inputs (zero flow by default)
         with torch.no_grad():
-            if flow_ref is None and self.flow_ref_mode == "lk":
-                # --flow_ref lk: the dense Lucas-Kanade estimate between the real frames stands in for FlowNet2's
-                flow_ref = torch.stack([ops.optical_flow(real[i], real_prev[i]) for i in range(F_)])
+            if flow_ref is None and self.flow_ref_mode in ("lk", "lkhs"):
+                # --flow_ref lk / lkhs: the dense Lucas-Kanade estimate between the real frames (lkhs: refined) stands in for
+                # FlowNet2's
+                flow_ref = torch.stack([ops.optical_flow(real[i], real_prev[i], **self._flow_kw) for i in range(F_)])
             if flow_ref is None:
                 if not getattr(self, "_warned_zero_flow", False):
                     self._warned_zero_flow = True
                     print("warning: flow / warp / weight losses run against a synthetic ZERO reference flow (FlowNet2 is not "
-                          "in the reference tree; pass flow_ref / conf_ref or --flow_ref lk, or --no_flow to train without the "
+                          "in the reference tree; pass flow_ref / conf_ref or --flow_ref lk / lkhs, or --no_flow to train without the "
                           "flow branch)", flush=True)
                 flow_ref = torch.zeros(F_, H, W, 4, dtype=torch.float32, device=dev)
                 real_prev_warp = real_prev
@@ -1420,13 +1426,13 @@ class Vid2VidTrainer:
         t for t in ends) -> [len(ends),H,W,2*(tD-1)], channels 2k, 2k+1 = (u, v) of optical_flow(w[k+1], w[k]); the real
         and the generated stack of a temporal discriminator both carry them (upstream: flow_ref_skipped).  None under
         --flow_ref zero: those channels stay zero."""
-        if self.flow_ref_mode != "lk":
+        if self.flow_ref_mode not in ("lk", "lkhs"):
             return None
         with torch.no_grad():
             rows = []
             for t in ends:
                 w = [reals[t - (self.tD - 1 - k) * d] for k in range(self.tD)]
-                rows.append(torch.cat([ops.optical_flow(w[k + 1], w[k])[..., :2] for k in range(self.tD - 1)], -1))
+                rows.append(torch.cat([ops.optical_flow(w[k + 1], w[k], **self._flow_kw)[..., :2] for k in range(self.tD - 1)], -1))
             return torch.stack(rows)
 
     def _temporal_stack(self, frames, ends, d, dt, flows=None):
