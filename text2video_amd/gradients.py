@@ -4,6 +4,7 @@ its uses in one graph, and the flat buckets the slots live in with their data-pa
 import collections
 import contextlib
 import os
+import struct
 import types
 
 import torch
@@ -543,6 +544,44 @@ def _scale(x, f):
     ops.scale_(x, f) if x.is_cuda else x.mul_(f)
 
 
+def _fold(grad, acc, mode, scale):
+    """ops.grad_fold on flat views (HIP kernel on device tensors); on host tensors the same two fp32 operations in torch"""
+    if grad.is_cuda:
+        ops.grad_fold(grad, acc, mode, scale)
+    elif mode == ops.GRAD_FOLD_OPEN:
+        acc.copy_(grad)
+    elif mode == ops.GRAD_FOLD_ADD:
+        acc.add_(grad)
+    else:
+        torch.add(acc, grad, out=grad)
+        grad.mul_(scale)
+
+
+def clips_per_rank(batch_size, world):
+    """--batchSize on `world` ranks -> (K, warning or None).  K = batchSize // world clips per rank and optimiser step; up
+    to one clip per rank (batchSize <= world) the batch stays one clip per rank, with a warning where that is not what the
+    flag says; above, batchSize must be a multiple of world (ValueError)."""
+    batch_size, world = int(batch_size), int(world)
+    if batch_size <= world:
+        warn = None
+        if batch_size not in (1, world):
+            warn = ("warning: --batchSize %d, but the batch is one clip per rank = %d (list %d devices in --gpu_ids)"
+                    % (batch_size, world, batch_size))
+        return 1, warn
+    if batch_size % world:
+        raise ValueError("--batchSize %d is not a multiple of the %d ranks (devices in --gpu_ids): every rank walks "
+                         "batchSize / ranks clips per optimiser step" % (batch_size, world))
+    return batch_size // world, None
+
+
+def clip_slots(iteration, rank, world, K):
+    """[(slot, clip index)] of rank `rank` in iteration `iteration` (counted from the start of training): the batch is
+    world * K global clip slots, slot s = rank * K + j for the rank's j-th clip, and slot s of iteration i reads clip
+    i * (world * K) + s -- whichever way the slots are split over ranks.  K = 1: clip i * world + rank."""
+    batch = world * K
+    return [(rank * K + j, iteration * batch + rank * K + j) for j in range(K)]
+
+
 class GradBuckets:
     """Persistent flat gradient buckets of one optimiser's parameters + their data-parallel exchange.
 
@@ -609,9 +648,31 @@ class GradBuckets:
         self.members = [[i for i, _ in mem] for mem in members]
         self.nbytes = 0
         self._works, self._open, self._launched = [], [], 0
+        # several clips per optimiser step (begin_step(micro=(j, K)), K > 1): `acc`, of the size of `flat`, takes the sum of
+        # the clips' gradients bucket by bucket (_launch); _any: parameters a clip of the step so far has delivered to
+        self.acc, self._micro, self._any = None, (0, 1), [False] * len(self.params)
+        self._written = [False] * len(self.params)      # a kernel wrote the slot in a micro-step of this optimiser step
+        self._mean = 1.0                                # fp32(1 / K) of the K last seen
 
     # -- one train step -----------------------------------------------------------------------------
-    def begin_step(self):
+    def begin_step(self, micro=(0, 1)):
+        """micro = (j, K): clip j of the K this rank walks before the optimiser step (micro-steps).  Every micro-step is a
+        step of its own for the backward nodes -- the first node of a parameter writes its slot, later ones add --; a bucket
+        that is complete (_launch) is folded into `acc`, and in the last micro-step the mean over the K clips goes back
+        into `flat` in front of the bucket's collective:  ((g_0 + g_1) + ... + g_{K-1}) * fp32(1 / K)."""
+        j, K = micro
+        if not 0 <= j < K:
+            raise ValueError("begin_step: micro-step %d of %d" % (j, K))
+        if j == 0:
+            self._any = [False] * len(self.params)
+            self._written = [False] * len(self.params)
+        elif self._micro != (j - 1, K):
+            raise RuntimeError("begin_step: micro-step %d of %d follows micro-step %d of %d" % ((j, K) + self._micro))
+        if K != self._micro[1]:
+            self._mean = struct.unpack("f", struct.pack("f", 1.0 / K))[0]      # fp32(1 / K), as the kernel receives it
+        self._micro = (j, K)
+        if K > 1 and self.acc is None:
+            self.acc = torch.zeros_like(self.flat)
         for sl in self.slots:
             sl.expect = sl.got = 0
             sl.filled = False
@@ -652,9 +713,21 @@ class GradBuckets:
         for i in self.members[b]:
             if not self.slots[i].filled and not self.slots[i].zero_valid:
                 _zero(self.slots[i].view)
-        if not self.exchange:
+        j, K = self._micro
+        fold = None if K == 1 else (ops.GRAD_FOLD_OPEN if j == 0 else ops.GRAD_FOLD_CLOSE if j == K - 1 else ops.GRAD_FOLD_ADD)
+        # (the bucket goes out with the step's last clip only)
+        issue = self.exchange and j == K - 1
+        if fold is None and not issue:
             return
-        import torch.distributed as dist
+        if fold is not None:
+            # CLOSE rewrites the whole bucket with the mean.  A slot whose zeros are on record (zero_valid) keeps them only if
+            # no kernel wrote it in any micro-step of this optimiser step: (0 + 0) * s = 0; otherwise the record goes
+            for i in self.members[b]:
+                sl = self.slots[i]
+                if sl.filled and not sl.zero_valid:
+                    self._written[i] = True
+                if fold == ops.GRAD_FOLD_CLOSE and self._written[i]:
+                    sl.zero_valid = False
         # The collective is ordered behind the stream it is issued on, and it needs the weight-gradient stream's kernels AND the
         # current stream's (and the step's main stream's, when this node runs on another).  With weight gradients in flight it
         # is issued FROM the weight-gradient stream, which first takes in what the other streams hold so far: the backward
@@ -668,12 +741,21 @@ class GradBuckets:
             if self._main is not None and cur != self._main:
                 side.wait_stream(self._main)
             with torch.cuda.stream(side):
-                self._issue(b)
+                self._fold_and_issue(b, fold, issue)
             return
         wgrad_join()
         if self._main is not None and torch.cuda.current_stream() != self._main:
             torch.cuda.current_stream().wait_stream(self._main)
-        self._issue(b)
+        self._fold_and_issue(b, fold, issue)
+
+    def _fold_and_issue(self, b, fold, issue):
+        """on the stream the bucket's collective is issued from, behind everything that wrote the bucket: its fold into (the
+        last clip: out of) the accumulator, then the collective"""
+        if fold is not None:
+            lo, hi = self.bounds[b]
+            _fold(self.flat[lo:hi], self.acc[lo:hi], fold, self._mean)
+        if issue:
+            self._issue(b)
 
     def _issue(self, b):
         import torch.distributed as dist
@@ -714,8 +796,8 @@ class GradBuckets:
         self.collecting = False
 
     def finish(self):
-        """Wait for the collectives; p.grad = the slot (None where no rank-local node delivered: Adam then skips the
-        parameter, as torch 0.4.1's does).  Returns the bytes exchanged."""
+        """Wait for the collectives; p.grad = the slot (None where no rank-local node delivered, in any clip of the optimiser
+        step so far: Adam then skips the parameter, as torch 0.4.1's does).  Returns the bytes exchanged."""
         import torch.distributed as dist
         wgrad_join()
         for work, buf, avg, shard in self._works:
@@ -726,14 +808,16 @@ class GradBuckets:
             if buf is not None and not avg and self.world > 1:
                 _scale(buf, 1.0 / self.world)
         self._works = []
-        for p, sl in zip(self.params, self.slots):
-            p.grad = sl.view if sl.filled else None
+        for k, (p, sl) in enumerate(zip(self.params, self.slots)):
+            if sl.filled:
+                self._any[k] = True
+            p.grad = sl.view if self._any[k] else None
         return self.nbytes
 
     def presence(self):
         """a checksum of WHICH parameters received gradients on this rank: must agree across ranks, or the replicas'
         optimiser steps differ (Adam skips parameters without gradient)"""
-        return float(sum((k + 1) * (k + 7) for k, sl in enumerate(self.slots) if sl.filled) % 1000003)
+        return float(sum((k + 1) * (k + 7) for k, sl in enumerate(self.slots) if sl.filled or self._any[k]) % 1000003)
 
 
 def check_presence_across_ranks(buckets, device):

@@ -10,7 +10,7 @@ import ctypes
 
 from ._xp import torch     # the real torch, or leantorch under vid2vid/test.py's torch-free frame loop
 
-from . import _flowlib, _lib
+from . import _flowlib, _gradfoldlib, _lib
 from ._lib import (ACT_FLOW_W, ACT_LRELU, ACT_NONE, ACT_TANH, ALGO_DIRECT, ALGO_WINOGRAD,  # noqa: F401
                    ALGO_DIRECT_BF16X2, ALGO_POLYPHASE, ALGO_POLYPHASE_BF16X2, ALGO_WINOGRAD_F4, ALGO_WINOGRAD_F4_BF16X2, PAD_REFLECT, PAD_ZERO, VISUALS_FLOW, VISUALS_IMAGE, VISUALS_MAX_PANELS,
                    VISUALS_UNIT, ConvDesc, check)
@@ -1492,6 +1492,23 @@ def scale_(x, s):
     assert x.is_contiguous()
     check(c.lib.t2v_scale(c.handle, _stream(), _p(x), x.numel(), float(s)), "scale")
     return x
+
+
+GRAD_FOLD_OPEN, GRAD_FOLD_ADD, GRAD_FOLD_CLOSE = _gradfoldlib.OPEN, _gradfoldlib.ADD, _gradfoldlib.CLOSE
+
+
+def grad_fold(grad, acc, mode, scale=1.0):
+    """One clip's gradients `grad` folded into the accumulator `acc` of an optimiser step over several clips (libt2v_gradfold.so,
+    include/t2v_grad_fold.h), on flat fp32 device tensors of equal size: GRAD_FOLD_OPEN acc = grad; GRAD_FOLD_ADD
+    acc = acc + grad; GRAD_FOLD_CLOSE grad = (acc + grad) * scale, one fp32 addition and one fp32 multiplication per element."""
+    c = context()
+    _chk(grad, "grad")
+    _chk(acc, "acc")
+    if grad.numel() != acc.numel():
+        raise ValueError("grad_fold: grad has %d elements, acc %d" % (grad.numel(), acc.numel()))
+    check(_gradfoldlib.load().t2v_grad_fold(c.handle, _stream(), _p(grad), _p(acc), grad.numel(), int(mode), float(scale)),
+          "grad_fold")
+    return grad if mode == GRAD_FOLD_CLOSE else acc
 
 
 def zero_(x):

@@ -30,7 +30,11 @@ def _common(p):
       "transposed layers that run as direct convolutions (128 <-> 256 channels), their contraction in the same split-bf16 "
       "arithmetic where that measured faster; the norm apply pass in front of such a layer stores the two bf16 terms of each "
       "value in place of it")
-    g("--batchSize", type=int, default=1)
+    g("--batchSize", type=int, default=1,
+      help="train.py: clips per optimiser step over all ranks (devices in --gpu_ids).  Up to the number of ranks the batch "
+      "is one clip per rank; above it, it must be a multiple of the ranks and every rank walks batchSize / ranks clips per "
+      "step, summing their gradients before the one exchange and optimiser step (--gpu_ids 0 --batchSize 8 trains the "
+      "batch --gpu_ids 0,...,7 --batchSize 8 trains)")
     g("--loadSize", type=int, default=512)
     g("--fineSize", type=int, default=512)
     g("--input_nc", type=int, default=3)

@@ -28,7 +28,8 @@ from .backward import ConvDataGrad
 from .generator import GeneratorSpec, layer_keys, synthetic_state_dict  # noqa: F401
 from .gradients import (STEP, GradBuckets, GradientExchange, GradSlot, ParamState, _acc, _batched_winograd_wgrad,  # noqa: F401
                         _desc_key, _keep_v_slot, _kept_winograd_wgrad, _paired_direct_wgrad, allreduce_gradients,
-                        allreduce_gradients_begin, batched_weight_gradients, cached_pack, check_presence_across_ranks,
+                        allreduce_gradients_begin, batched_weight_gradients, cached_pack, check_presence_across_ranks, clip_slots,
+                        clips_per_rank,
                         deliver, deliver_direct, deliver_into, direct_weight_gradient, expect_gradient,
                         flush_pending_weight_gradients, grad_slot, invalidate_packs, owner, param_state, prefetch_packs,
                         side_gemm_hint, switch, wgrad_fork, wgrad_join, wgrad_stream_on, winograd_weight_gradient)
@@ -78,6 +79,21 @@ def bn_updates(n):
         _BN_UPDATES[0] = old
 
 
+_BN_FROZEN = [False]
+
+
+@contextlib.contextmanager
+def bn_frozen():
+    """no forward inside the scope moves running statistics, whatever bn_updates or a caller's `times` says (the clips of an
+    optimiser step behind its first: Vid2VidTrainer.train_step)"""
+    old = _BN_FROZEN[0]
+    _BN_FROZEN[0] = True
+    try:
+        yield
+    finally:
+        _BN_FROZEN[0] = old
+
+
 def running_stats(gamma, create=True):
     """[running_mean, running_var, num_batches_tracked] of the BatchNorm2d whose weight is `gamma` (kept on the parameter
     object; created at torch's initial values 0 / 1 / 0)."""
@@ -96,7 +112,7 @@ def running_update_args(gamma, n, times=None):
     the generator in train mode at test time) but part of a faithful checkpoint.  Returns (running_mean,
     running_var, momentum, times) for the finalize call, which moves them in its own launch, or None (no affine norm,
     fewer than two values per channel); counts the updates on the statistics' step counter."""
-    if gamma is None or n < 2:
+    if gamma is None or n < 2 or _BN_FROZEN[0]:
         return None
     times = _BN_UPDATES[0] if times is None else int(times)
     rs = running_stats(gamma)
@@ -1282,6 +1298,7 @@ class Vid2VidTrainer:
                                                                                   opt.norm, seed + 10 + s),
                                                   opt.ndf, opt.n_layers_D, opt.num_D, opt.norm, device))
         self._hist_real, self._hist_fake = [], []    # frames of the running sequence (fakes detached)
+        self._hist_slots = {}                        # clip j of a step of several clips (train_step(micro=)) -> its pair
         # where the reference flow comes from when the caller passes none: "zero", "lk" = ops.optical_flow on the real frames,
         # or "lkhs" = the same with the Horn-Schunck refinement (--flow_refine_iters steps per level, --flow_alpha)
         self.flow_ref_mode = getattr(opt, "flow_ref", "zero")
@@ -1595,13 +1612,15 @@ class Vid2VidTrainer:
         side_gemm_hint()
         return side
 
-    def _backward_and_update(self, tG, sG, tD, sD, off_in_g_pass):
+    def _backward_and_update(self, tG, sG, tD, sD, off_in_g_pass, update=True):
         """Both backward passes, the gradient exchange and both optimiser steps.  tG / sG: the tensors G's pass starts from and
         their gradient seeds (None: a scalar), tD / sD: the same for D's pass; off_in_g_pass: the parameters whose gradients
         are switched off during G's pass -- D's, wherever one D forward serves both losses.
         The pass-by-pass form comes with ([loss_G], [None], [loss_D], [None], ...): a scalar loss is the result of a
         multiplication or an addition, never of a _ConvBlock, so _d_backward_on_its_own_stream declines it before it touches
-        anything (its isinstance test on grad_fn) and D's pass takes the engine, whatever T2V_D_BWD_STREAM says."""
+        anything (its isinstance test on grad_fn) and D's pass takes the engine, whatever T2V_D_BWD_STREAM says.
+        update=False (a clip of the optimiser step that is not its last): the buckets keep the clip's gradients in their
+        accumulators, nothing is exchanged and no optimiser steps."""
         g_params, d_params = self.optG.params, self.optD.params
         # G's backward: the nodes deliver into bucketsG and launch its buckets' collectives as they complete; what is
         # left goes out in absorb() -- all of it in flight under the discriminators' backward pass
@@ -1632,25 +1651,40 @@ class Vid2VidTrainer:
         if self.time_comm and self.comm_bytes:
             torch.cuda.synchronize()
             self.comm_ms = 1e3 * (time.perf_counter() - t0)
+        if not update:
+            return
         check_presence_across_ranks([self.bucketsG, self.bucketsD], tD[0].device)
         self.optG.step()
         self.optD.step()
 
-    def train_step(self, pose, real, face_boxes=None, prev=None, real_prev=None, flow_ref=None, conf_ref=None):
+    def train_step(self, pose, real, face_boxes=None, prev=None, real_prev=None, flow_ref=None, conf_ref=None, micro=(0, 1)):
         """pose [F,H,W,12] (sliding windows), real [F,H,W,4] NHWC on the device; face_boxes: list of
         (ys,ye,xs,xe) per frame; prev: the carried FIFO of generated frames (None: a new sequence starts).
         With the flow branch: real_prev [F,H,W,4] = the real frame before each frame enables the flow / warp
         losses against flow_ref [F,H,W,4] (flow_x, flow_y in pixels; default zero flow) and its confidence mask
         conf_ref [F,H,W] (default: ||real - resample(real_prev, flow_ref)|| < 0.02, the rule upstream's FlowNet2
-        wrapper applies [RECALL]).  Returns (dict of scalar losses, FIFO for the next chunk)."""
-        with batched_weight_gradients(self.optG.params + self.optD.params):
-            return self._train_step(pose, real, face_boxes, prev, real_prev, flow_ref, conf_ref)
+        wrapper applies [RECALL]).  Returns (dict of scalar losses, FIFO for the next chunk).
+        micro = (j, K): this chunk belongs to clip j of the K clips the rank walks in lock-step (--batchSize above the
+        number of ranks).  Every call is one clip's complete forward and backward passes; the gradient buckets sum the K
+        clips' gradients in the order j = 0 .. K-1 and the call with j = K-1 exchanges their mean and steps both optimisers
+        (GradBuckets.begin_step).  The caller carries each clip's FIFO; the frame history of the temporal discriminators is
+        kept here per clip.  BatchNorm running statistics move with clip 0 only, as on DataParallel's replica 0."""
+        j, K = micro
+        if K > 1:
+            self._hist_real, self._hist_fake = self._hist_slots.get(j, ([], []))
+        try:
+            with batched_weight_gradients(self.optG.params + self.optD.params), \
+                    (bn_frozen() if j > 0 else contextlib.nullcontext()):
+                return self._train_step(pose, real, face_boxes, prev, real_prev, flow_ref, conf_ref, micro)
+        finally:
+            if K > 1:
+                self._hist_slots[j] = (self._hist_real, self._hist_fake)
 
-    def _train_step(self, pose, real, face_boxes, prev, real_prev=None, flow_ref=None, conf_ref=None):
+    def _train_step(self, pose, real, face_boxes, prev, real_prev=None, flow_ref=None, conf_ref=None, micro=(0, 1)):
         dev = pose.device
         F_, H, W = pose.shape[0], pose.shape[1], pose.shape[2]
-        self.bucketsG.begin_step()
-        self.bucketsD.begin_step()
+        self.bucketsG.begin_step(micro)
+        self.bucketsD.begin_step(micro)
         flow_on = not self.spec.no_flow
         first = prev is None
         if first:   # a new sequence starts: zero previous frames, raw-only first frame (--no_first_img)
@@ -1717,7 +1751,7 @@ class Vid2VidTrainer:
                 tG, sG = tG + [loss_G], sG + [None]
         else:
             tG, sG, tD, sD = [loss_G], [None], [loss_D], [None]
-        self._backward_and_update(tG, sG, tD, sD, self.optD.params if shared else [])
+        self._backward_and_update(tG, sG, tD, sD, self.optD.params if shared else [], update=micro[0] == micro[1] - 1)
         return read_losses(named, book), prev
 
     def update_learning_rate(self, epoch):
@@ -1796,29 +1830,31 @@ class _ClipFeeder:
     copy stream one clip ahead of the compute stream (an event orders the two), and finished on the device once per clip:
     real_all [T,H,W,4] = the normalised frames, of which every chunk's `real` and `real_prev` are slices.  Under
     --gpu_resize the loader hands over the decoded frames and ONE launch (ops.resample_crop_normalize_u8) resizes, crops
-    and normalises them; a geometry over the kernel's tap limit is resized with Pillow here instead.  real_all is kept
-    per geometry and its pad channel zeroed when it is created; the upload buffers alternate between two slots."""
+    and normalises them; a geometry over the kernel's tap limit is resized with Pillow here instead.
+    k: clips per iteration (run_train walks them in lock-step): k clips are held while the next k are staged.  real_all is
+    kept per held clip and geometry, its pad channel zeroed when it is created; the upload buffers rotate through 2 k slots."""
 
-    def __init__(self, ds, opt, dev, schedule):
+    def __init__(self, ds, opt, dev, schedule, k=1):
         import collections
         import threading
         self.opt, self.dev = opt, dev
         self.gpu_resize = bool(getattr(opt, "gpu_resize", False))
         self.gpu_decode = self.gpu_resize and bool(getattr(opt, "gpu_decode", False))
         self._jpeg_ws = None                              # the decode calls' workspace (used on the copy stream only)
-        self._jpeg_status = [None, None]                  # slot -> (device int32, pinned int32) of its clip's statuses
+        self.k = k
+        self._jpeg_status = [None] * (2 * k)              # slot -> (device int32, pinned int32) of its clip's statuses
         self.jpeg_clips = self.jpeg_fallback_frames = self.h2d_bytes = 0
         self.copy_stream = torch.cuda.Stream(device=dev)
         self._free = collections.defaultdict(list)      # shape -> pinned tensors not in use
         self._pinned = {}                                 # address of a handed-out array -> its pinned tensor
         self._slots = {}                                  # (slot, what, shape) -> device uint8 buffer
-        self._slot_done = [None, None]                    # compute-stream event: the slot's last clip has been consumed
-        self._real_all = {}                               # (T, H, W) -> [T,H,W,4] fp32
+        self._slot_done = [None] * (2 * k)                # compute-stream event: the slot's last clip has been consumed
+        self._real_all = {}                               # (held clip j, T, H, W) -> [T,H,W,4] fp32
         self._n = 0
-        self._staged = None
-        self._held = []                                   # pinned tensors of the clip being consumed
+        self._staged = collections.deque()
+        self._held = []                                   # (slot, pinned tensors) of the clips being consumed, at most k
         self._lock = threading.Lock()
-        self._it = ds.iter_clips(schedule, ahead=2, gpu_resize=self.gpu_resize, alloc=self._alloc, gpu_decode=self.gpu_decode)
+        self._it = ds.iter_clips(schedule, ahead=2 * k, gpu_resize=self.gpu_resize, alloc=self._alloc, gpu_decode=self.gpu_decode)
 
     def _alloc(self, shape):      # called from the loader's threads
         shape = tuple(int(v) for v in shape)
@@ -1865,13 +1901,16 @@ class _ClipFeeder:
         return pj, Bu
 
     def stage(self):
-        """take the next clip from the loader (waits for it if the loader is behind) and start its upload"""
-        if self._staged is not None:
-            return
+        """take the next clips from the loader (waits for them if the loader is behind) and start their uploads, until k
+        are staged"""
+        while len(self._staged) < self.k and self._stage_one():
+            pass
+
+    def _stage_one(self):
         clip = next(self._it, None)
         if clip is None:
-            return
-        slot = self._n % 2
+            return False
+        slot = self._n % (2 * self.k)
         self._n += 1
         if self._slot_done[slot] is not None:
             self.copy_stream.wait_event(self._slot_done[slot])
@@ -1883,25 +1922,31 @@ class _ClipFeeder:
                 pb, Bu = self._upload(clip["raw"] if self.gpu_resize else clip["B"], slot, "B")
             ev = torch.cuda.Event()
             ev.record(self.copy_stream)
-        self._staged = (clip, slot, A, Bu, ev, [pa, pb])
+        self._staged.append((clip, slot, A, Bu, ev, [pa, pb]))
+        return True
 
     def take(self):
-        """-> (clip, A uint8 [T,H,W,3] on the device, real_all fp32 [T,H,W,4]); None when the schedule is exhausted"""
+        """-> (clip, A uint8 [T,H,W,3] on the device, real_all fp32 [T,H,W,4]); None when the schedule is exhausted.  The
+        k clips of an iteration are taken one after the other and stay valid until the next iteration's first take."""
         from . import ops as _ops
-        self.stage()
-        if self._staged is None:
+        if not self._staged:
+            self.stage()
+        if not self._staged:
             return None
-        clip, slot, A, Bu, ev, pinned = self._staged
-        self._staged = None
-        with self._lock:      # the previous clip is done with its host arrays (its uploads completed long ago)
-            for t in self._held:
-                self._free[tuple(t.shape)].append(t)
-        self._held = pinned
+        clip, slot, A, Bu, ev, pinned = self._staged.popleft()
+        if len(self._held) >= self.k:
+            with self._lock:      # the previous clips are done with their host arrays (their uploads completed long ago)
+                for _, ts in self._held:
+                    for t in ts:
+                        self._free[tuple(t.shape)].append(t)
+            self._held = []
+        j = len(self._held)
+        self._held.append((slot, pinned))
         torch.cuda.current_stream().wait_event(ev)
         T_, H, W = A.shape[0], A.shape[1], A.shape[2]
-        real_all = self._real_all.get((T_, H, W))
+        real_all = self._real_all.get((j, T_, H, W))
         if real_all is None:
-            real_all = self._real_all[(T_, H, W)] = torch.zeros(T_, H, W, 4, device=self.dev)
+            real_all = self._real_all[(j, T_, H, W)] = torch.zeros(T_, H, W, 4, device=self.dev)
         prm = clip["params"]
         if "jpeg" in clip:
             # the statuses came with the event the step waits on anyway (the clip was staged a step ago); a frame the
@@ -1926,14 +1971,15 @@ class _ClipFeeder:
                 real_all[..., :3] = (torch.from_numpy(B).to(self.dev).float() / 255.0 - 0.5) / 0.5
         else:
             real_all[..., :3] = (Bu.float() / 255.0 - 0.5) / 0.5
-        self._slot = slot
         return clip, A, real_all
 
     def consumed(self):
-        """the clip's last chunk has been launched: its upload slot may be overwritten once the compute stream gets here"""
+        """the held clips' last chunk has been launched: the upload slot of each may be overwritten once the compute stream
+        gets here"""
         ev = torch.cuda.Event()
         ev.record()
-        self._slot_done[self._slot] = ev
+        for slot, _ in self._held:
+            self._slot_done[slot] = ev
 
     def close(self):
         self._it.close()
@@ -1943,8 +1989,9 @@ def run_train(opt, steps=None, watch=None):
     """train.py main: one process per GPU under torchrun (the reference used nn.DataParallel threads).
 
     Epoch structure of upstream train.py [RECALL]: `niter` epochs at the initial learning rate + `niter_decay` epochs
-    of linear decay to zero; an epoch is one clip per training sequence (batchSize = number of ranks clips per
-    iteration); `latest` checkpoints every `save_latest_freq` samples and at every `save_epoch_freq`-th epoch end (also
+    of linear decay to zero; an epoch is one clip per training sequence, `batch` = ranks x K clips per iteration
+    (K = batchSize // ranks clips per rank where --batchSize is above the number of ranks, else 1: clips_per_rank);
+    `latest` checkpoints every `save_latest_freq` samples and at every `save_epoch_freq`-th epoch end (also
     under the epoch number), with `iter.txt` = (epoch, samples done in it) beside them; `--continue_train` reloads
     the `which_epoch` nets, reads iter.txt and resumes there (fresh Adam moments: upstream saves none).
     `steps` caps the total number of iterations (tests, benches); `watch`: a dict that receives the run's "trainer" and,
@@ -1952,7 +1999,14 @@ def run_train(opt, steps=None, watch=None):
 
     --display_web: rank 0 shows the last frame of the step that completes every `display_freq` samples (the rule of
     `save_latest_freq`) through TrainDisplay -- rendered on the GPU behind the step, written by a thread -- and appends
-    every printed iteration line to loss_log.txt."""
+    every printed iteration line to loss_log.txt.
+
+    K > 1: the batch is `batch` global clip slots, slot s = rank * K + j the rank's j-th clip (clip_slots): which clip and
+    which synthetic-data generator a slot reads depends on s and the iteration alone, so --gpu_ids 0,1 --batchSize 2 and
+    --gpu_ids 0 --batchSize 2 train on the same batch (promised for --synthetic_data; a real dataset keeps one
+    TrainPoseDataset per rank, whose random draws depend on the rank).  The rank's K clips walk their chunks in lock-step:
+    per chunk K micro-steps train_step(micro=(j, K)), the last of which exchanges the mean gradient and steps the
+    optimisers.  Each clip carries its own FIFO; a printed loss is the mean over the rank's K clips."""
     import os
     import time
     import numpy as np
@@ -1963,6 +2017,8 @@ def run_train(opt, steps=None, watch=None):
         rank, local_rank, world = 0, (opt.gpu_ids[0] if getattr(opt, "gpu_ids", None) else 0), 1
     dev = "cuda:%d" % local_rank
     torch.cuda.set_device(local_rank)
+    K, batch_warning = clips_per_rank(getattr(opt, "batchSize", world), world)
+    batch = world * K
     trainer = Vid2VidTrainer(opt, dev)
     display = None
     if rank == 0 and getattr(opt, "display_web", False):
@@ -1972,16 +2028,15 @@ def run_train(opt, steps=None, watch=None):
     if watch is not None:
         watch["trainer"], watch["display"] = trainer, display
     Dm.rendezvous("trainer built")      # (before the first gradient exchange: a rank that died building its replica is named)
-    if rank == 0 and getattr(opt, "batchSize", world) not in (1, world):
-        print("warning: --batchSize %d, but the batch is one clip per rank = %d (list %d devices in --gpu_ids)"
-              % (opt.batchSize, world, opt.batchSize), flush=True)
+    if rank == 0 and batch_warning:
+        print(batch_warning, flush=True)
     F_ = opt.max_frames_per_gpu
     synthetic = getattr(opt, "synthetic_data", False)
     ds = None
     if not synthetic:
         from .pose_dataset import TrainPoseDataset
         ds = TrainPoseDataset(opt, seed=1000 + rank)
-    per_epoch = 1 if synthetic else max(1, len(ds) // world)          # iterations per epoch (world clips each)
+    per_epoch = 1 if synthetic else max(1, len(ds) // batch)          # iterations per epoch (`batch` clips each)
     iter_path = os.path.join(opt.checkpoints_dir, opt.name, "iter.txt")
     start_epoch, epoch_iter = 1, 0
     if opt.continue_train:
@@ -2001,7 +2056,8 @@ def run_train(opt, steps=None, watch=None):
         if rank == 0:
             trainer.save(label, (epoch, done))
 
-    rng = np.random.default_rng(100 + rank)          # synthetic data: every rank has its own sequence
+    # synthetic data: every clip slot has its own sequence
+    rngs = [np.random.default_rng(100 + s) for s, _ in clip_slots(0, rank, world, K)]
     tG = opt.n_frames_G
     feeder = None
     if ds is not None and getattr(opt, "train_loader", "sync") == "prefetch":
@@ -2009,102 +2065,122 @@ def run_train(opt, steps=None, watch=None):
             """(clip index, n_frames_total) of every iteration from the resume point on: clips are drawn ahead of the
             epoch ends at which update_training_batch doubles the clip length, so each carries the length of its epoch"""
             cap = getattr(opt, "max_frames_total", 10 ** 9)
-            first_k = epoch_iter // world
+            first_k = epoch_iter // batch
             for e in range(start_epoch, opt.niter + opt.niter_decay + 1):
                 ratio = (e - 1) // max(1, opt.niter_step)
                 nft = min(cap, opt.n_frames_total * 2 ** ratio) if ratio > 0 else opt.n_frames_total
                 for kk in range(first_k, per_epoch):
-                    yield (((e - 1) * per_epoch + kk) * world + rank, nft)
+                    for _, index in clip_slots((e - 1) * per_epoch + kk, rank, world, K):      # (in slot order)
+                        yield (index, nft)
                 first_k = 0
-        feeder = _ClipFeeder(ds, opt, dev, schedule())
+        feeder = _ClipFeeder(ds, opt, dev, schedule(), K)
     elif ds is not None and getattr(opt, "gpu_resize", False) and rank == 0:
         print("warning: --gpu_resize has no effect without --train_loader prefetch", flush=True)
     last_pos = (start_epoch, epoch_iter)
-    stats, it, total_samples = [], 0, (start_epoch - 1) * per_epoch * world + epoch_iter
+    stats, it, total_samples = [], 0, (start_epoch - 1) * per_epoch * batch + epoch_iter
     last_epoch = opt.niter + opt.niter_decay
     for epoch in range(start_epoch, last_epoch + 1):
         trainer.set_epoch(epoch)      # (--niter_fix_global with two spatial scales; a resumed run enters its epoch's phase here)
-        for k in range(epoch_iter // world, per_epoch):
+        for k in range(epoch_iter // batch, per_epoch):
             if steps is not None and it >= steps:
                 break
             ts = time.perf_counter()
+            visuals = trainer.visuals
+            per_clip = []       # the reported losses of the iteration's last chunk, per clip of this rank
             if synthetic:
                 H = W = opt.fineSize
-                pose_np = np.where(rng.random((F_, H, W, 1)) < 0.02, rng.uniform(-1, 1, (F_, H, W, 9)), -1.0).astype(np.float32)
-                pose = torch.zeros(F_, H, W, 12, device=dev)
-                pose[..., :9] = torch.from_numpy(pose_np).to(dev)
-                real = torch.zeros(F_, H, W, 4, device=dev)
-                real[..., :3] = torch.tanh(torch.from_numpy(rng.standard_normal((F_, H, W, 3)).astype(np.float32))).to(dev)
-                side = max(8, opt.fineSize // 32 * 8)
-                boxes = [(H // 8, H // 8 + side, (W - side) // 2, (W - side) // 2 + side)] * F_ if opt.add_face_disc else None
-                real_prev = None
-                if not trainer.spec.no_flow:    # the real frame before each frame (flow / warp losses)
-                    real_prev = torch.cat([torch.tanh(torch.from_numpy(rng.standard_normal((1, H, W, 4)).astype(np.float32))).to(dev),
-                                           real[:-1]], 0)
-                    real_prev[..., 3] = 0
-                losses, _ = trainer.train_step(pose, real, boxes, real_prev=real_prev)
+                for j, rng in enumerate(rngs):
+                    pose_np = np.where(rng.random((F_, H, W, 1)) < 0.02, rng.uniform(-1, 1, (F_, H, W, 9)), -1.0).astype(np.float32)
+                    pose = torch.zeros(F_, H, W, 12, device=dev)
+                    pose[..., :9] = torch.from_numpy(pose_np).to(dev)
+                    real = torch.zeros(F_, H, W, 4, device=dev)
+                    real[..., :3] = torch.tanh(torch.from_numpy(rng.standard_normal((F_, H, W, 3)).astype(np.float32))).to(dev)
+                    side = max(8, opt.fineSize // 32 * 8)
+                    boxes = [(H // 8, H // 8 + side, (W - side) // 2, (W - side) // 2 + side)] * F_ if opt.add_face_disc else None
+                    real_prev = None
+                    if not trainer.spec.no_flow:    # the real frame before each frame (flow / warp losses)
+                        real_prev = torch.cat([torch.tanh(torch.from_numpy(rng.standard_normal((1, H, W, 4)).astype(np.float32))).to(dev),
+                                               real[:-1]], 0)
+                        real_prev[..., 3] = 0
+                    losses, _ = trainer.train_step(pose, real, boxes, real_prev=real_prev, micro=(j, K))
+                    per_clip.append(losses)
+                    if j == 0:
+                        visuals = trainer.visuals
                 what = ""
             else:
-                # one clip per rank per iteration, walked in chunks of max_frames_per_gpu frames with the generated
-                # frames carried over (detached) from chunk to chunk, one optimiser step per chunk -- upstream's
-                # truncated recurrence
-                real_all = None
-                if feeder is not None:
-                    # the same clip, prepared ahead; real_all [T,H,W,4]: its frames normalised once, pad channel zero
-                    clip, A, real_all = feeder.take()
-                else:
-                    clip = ds.sample(((epoch - 1) * per_epoch + k) * world + rank)
-                    A = torch.from_numpy(clip["A"]).to(dev)                      # [T,H,W,3] uint8
-                    B = torch.from_numpy(clip["B"]).to(dev)
-                T_, H, W = A.shape[0], A.shape[1], A.shape[2]
-                if world > 1:   # every rank must run the same number of chunks (one gradient all-reduce per chunk)
+                # K clips per rank per iteration (one where --batchSize does not exceed the ranks), walked together in chunks
+                # of max_frames_per_gpu frames with each clip's generated frames carried over (detached) from chunk to
+                # chunk, one optimiser step per chunk -- upstream's truncated recurrence
+                clips = []      # (clip, A [T,H,W,3] uint8, B uint8 or None, real_all or None)
+                for _, index in clip_slots((epoch - 1) * per_epoch + k, rank, world, K):
+                    if feeder is not None:
+                        # the same clip, prepared ahead; real_all [T,H,W,4]: its frames normalised once, pad channel zero
+                        clip, A, real_all = feeder.take()
+                        clips.append((clip, A, None, real_all))
+                    else:
+                        clip = ds.sample(index)
+                        clips.append((clip, torch.from_numpy(clip["A"]).to(dev),                      # [T,H,W,3] uint8
+                                      torch.from_numpy(clip["B"]).to(dev), None))
+                # every clip of the batch runs the same number of chunks (one gradient all-reduce per chunk)
+                T_ = min(A.shape[0] for _, A, _, _ in clips)
+                if world > 1:
                     import torch.distributed as dist
                     tmin = torch.tensor([T_], device=dev)
                     dist.all_reduce(tmin, op=dist.ReduceOp.MIN)
                     T_ = int(tmin.item())
-                prev = None
+                prevs = [None] * K
                 for c0 in range(tG - 1, T_, F_):
                     fr = list(range(c0, min(c0 + F_, T_)))
-                    pose = torch.zeros(len(fr), H, W, 12, device=dev)
-                    for j, t in enumerate(fr):
-                        for f in range(tG):                                    # window: oldest frame first
-                            ops.pose_u8_to_f32(A[t - tG + 1 + f], pose[j], 3 * f)
-                    real_prev = None
-                    if real_all is not None:      # slices of the clip's frames: no arithmetic per chunk
-                        real = real_all[fr[0]:fr[-1] + 1]
-                        if not trainer.spec.no_flow:
-                            real_prev = real_all[fr[0] - 1:fr[-1]]
-                    else:
-                        real = torch.zeros(len(fr), H, W, 4, device=dev)
-                        real[..., :3] = (B[fr].float() / 255.0 - 0.5) / 0.5
-                        if not trainer.spec.no_flow:
-                            real_prev = torch.zeros(len(fr), H, W, 4, device=dev)
-                            real_prev[..., :3] = (B[[t - 1 for t in fr]].float() / 255.0 - 0.5) / 0.5
-                    boxes = None
-                    if opt.add_face_disc:      # one region for the chunk (upstream boxes the whole batch of frames)
-                        box = get_face_region(clip["A"][fr], opt.fineSize)
-                        if world > 1:
-                            # the face terms decide which parameters (D_f) have gradients: every rank must take the same
-                            # branch, or the ranks' gradient buckets would differ in size and order -- the face
-                            # discriminator trains on a chunk only when EVERY rank's chunk shows a face
-                            import torch.distributed as dist
-                            has = torch.tensor([1 if box is not None else 0], device=dev if dist.get_backend() == "nccl" else "cpu")
-                            dist.all_reduce(has, op=dist.ReduceOp.MIN)
-                            if int(has.item()) == 0:
-                                box = None
-                        boxes = [box] * len(fr) if box is not None else None
-                    losses, prev = trainer.train_step(pose, real, boxes, prev, real_prev=real_prev)
+                    per_clip = []
+                    for j, (clip, A, B, real_all) in enumerate(clips):
+                        H, W = A.shape[1], A.shape[2]
+                        pose = torch.zeros(len(fr), H, W, 12, device=dev)
+                        for jj, t in enumerate(fr):
+                            for f in range(tG):                                    # window: oldest frame first
+                                ops.pose_u8_to_f32(A[t - tG + 1 + f], pose[jj], 3 * f)
+                        real_prev = None
+                        if real_all is not None:      # slices of the clip's frames: no arithmetic per chunk
+                            real = real_all[fr[0]:fr[-1] + 1]
+                            if not trainer.spec.no_flow:
+                                real_prev = real_all[fr[0] - 1:fr[-1]]
+                        else:
+                            real = torch.zeros(len(fr), H, W, 4, device=dev)
+                            real[..., :3] = (B[fr].float() / 255.0 - 0.5) / 0.5
+                            if not trainer.spec.no_flow:
+                                real_prev = torch.zeros(len(fr), H, W, 4, device=dev)
+                                real_prev[..., :3] = (B[[t - 1 for t in fr]].float() / 255.0 - 0.5) / 0.5
+                        boxes = None
+                        if opt.add_face_disc:      # one region for the chunk (upstream boxes the whole batch of frames)
+                            box = get_face_region(clip["A"][fr], opt.fineSize)
+                            if world > 1:
+                                # the face terms decide which parameters (D_f) have gradients: every rank must take the same
+                                # branch, or the ranks' gradient buckets would differ in size and order -- the face
+                                # discriminator trains on a chunk only when the chunk of EVERY rank's clip j shows a face
+                                import torch.distributed as dist
+                                has = torch.tensor([1 if box is not None else 0], device=dev if dist.get_backend() == "nccl" else "cpu")
+                                dist.all_reduce(has, op=dist.ReduceOp.MIN)
+                                if int(has.item()) == 0:
+                                    box = None
+                            boxes = [box] * len(fr) if box is not None else None
+                        losses, prevs[j] = trainer.train_step(pose, real, boxes, prevs[j], real_prev=real_prev, micro=(j, K))
+                        per_clip.append(losses)
+                        if j == 0:
+                            visuals = trainer.visuals
                 if feeder is not None:
                     feeder.consumed()
                     if steps is None or it + 1 < steps:
-                        feeder.stage()      # the next clip's upload runs beside this clip's chunks
-                what = ", seq %s, %d frames %dx%d step %d" % (clip["seq"], T_ - tG + 1, H, W, clip["t_step"])
-            if display is not None and (total_samples + world) % max(1, opt.display_freq) < world:
-                display.show(trainer.visuals, epoch, total_samples + world)      # (enqueued behind the step; no host wait)
+                        feeder.stage()      # the next clips' uploads run beside these clips' chunks
+                clip, A = clips[0][0], clips[0][1]
+                what = ", seq %s, %d frames %dx%d step %d" % (clip["seq"], T_ - tG + 1, A.shape[1], A.shape[2], clip["t_step"])
+            if K > 1 and per_clip:       # the mean over the rank's clips, summed in float64; a term a clip does not have (no
+                names = list(dict.fromkeys(name for lc in per_clip for name in lc))      # face region) counts as 0 there
+                losses = {name: float(np.sum(np.array([lc.get(name, 0.0) for lc in per_clip], dtype=np.float64)) / K) for name in names}
+            if display is not None and (total_samples + batch) % max(1, opt.display_freq) < batch:
+                display.show(visuals, epoch, total_samples + batch)      # (clip 0's; enqueued behind the step; no host wait)
             torch.cuda.synchronize()
             stats.append(time.perf_counter() - ts)
             it += 1
-            total_samples += world
+            total_samples += batch
             if rank == 0 and ((it - 1) % max(1, opt.print_freq // 100) == 0 or it == steps):
                 line = "(iter %d, epoch %d%s, %.0f ms, all-reduce %.1f MB%s) %s" \
                     % (it - 1, epoch, what, 1e3 * stats[-1], trainer.comm_bytes / 2**20,
@@ -2113,9 +2189,9 @@ def run_train(opt, steps=None, watch=None):
                 print(line, flush=True)
                 if display is not None:
                     display.log(line)
-            last_pos = (epoch, (k + 1) * world)
-            if total_samples % max(1, opt.save_latest_freq) < world:
-                checkpoint("latest", epoch, (k + 1) * world)
+            last_pos = (epoch, (k + 1) * batch)
+            if total_samples % max(1, opt.save_latest_freq) < batch:
+                checkpoint("latest", epoch, (k + 1) * batch)
         else:
             epoch_iter = 0
             last_pos = (epoch + 1, 0)

@@ -9,7 +9,9 @@
 One process per GPU: the reference fanned out over --gpu_ids inside one process with nn.DataParallel
 (torch/nn/parallel/data_parallel.py:116-137); here this script starts one rank per listed device itself
 (text2video_amd/launch.py; `python -m torch.distributed.run --nproc-per-node 8 train.py ...` works as well), every
-rank owns one clip of the batch and gradients are all-reduced over RCCL.  Built: the train step (generator,
+rank owns one clip of the batch and gradients are all-reduced over RCCL.  With fewer devices than --batchSize every rank
+walks batchSize / ranks clips per optimiser step and sums their gradients before the exchange (--batchSize must then be a
+multiple of the number of devices): --gpu_ids 0 --batchSize 8 trains the batch of the line above on one GPU.  Built: the train step (generator,
 multiscale + face + temporal discriminators, LSGAN + feature matching + VGG19 perceptual loss, Adam), the
 real-data loader (train_openpose / train_img), the epoch schedule with learning-rate decay, periodic
 checkpoints and --continue_train; --synthetic_data runs it without a dataset.  FlowNet2-based losses are not
