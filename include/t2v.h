@@ -176,7 +176,8 @@ int t2v_conv2d_forward_batch(t2v_ctx* ctx, void* stream, const t2v_conv_desc* d,
  * arithmetic of t2v_instance_norm_apply -- y carries the bits of t2v_instance_norm_apply followed by t2v_conv2d_forward, without
  * the pass over the map in between (what t2v_generator_forward* does with the last decoder layer's output unless
  * T2V_CHAIN_LAZY=0).  d: 7x7, stride 1, ReflectionPad 3, Cout <= 3, x_cs % 16 == 0, H, W >= 4 (the shapes the halo-tile kernel
- * takes; anything else is T2V_ERR_INVALID); mean_rstd [x_cs][2] as t2v_*_norm_finalize writes it; gamma, beta both or neither;
+ * takes; anything else is T2V_ERR_INVALID); mean_rstd [x_cs][2] as t2v_*_norm_finalize writes it -- one row per channel of the conv
+ * that produced x, so x_cs == Cin and x has no storage lane; gamma, beta both or neither;
  * relu must be 1 (the norm in front of a head is always followed by its ReLU). */
 int t2v_conv2d_forward_head_norm(t2v_ctx* ctx, void* stream, const t2v_conv_desc* d, const float* x, int x_cs,
                                  const float* w_packed, const float* bias, float* y, int y_cs, const float* mean_rstd,
@@ -230,7 +231,8 @@ enum { T2V_GEMM_TILE_PER_BLOCK_64x64 = 0, T2V_GEMM_TILE_PER_BLOCK_128x128 = 1, T
                                         * SpatialConvolutionMM's GEMM, THCUNN.h:664, in split-bf16 arithmetic) */ };
 int t2v_conv_winograd_gemm_form(const t2v_conv_desc* d, int nimg);
 /* forward with d->algo == T2V_ALGO_WINOGRAD | T2V_ALGO_WINOGRAD_F4 | T2V_ALGO_WINOGRAD_F4_BF16X2; same contract as
- * t2v_conv2d_forward plus the workspace */
+ * t2v_conv2d_forward plus the workspace.  Every form that runs through the *_winograd entries asks "y_cs == Cout" as well as
+ * x_cs == Cin (anything else is T2V_ERR_INVALID): these entries meet no storage lane on either side. */
 int t2v_conv2d_forward_winograd(t2v_ctx* ctx, void* stream, const t2v_conv_desc* d, const float* x, int x_cs,
                                 const float* w_packed, const float* bias, float* y, int y_cs, float* stats_partial,
                                 float* workspace);
@@ -518,14 +520,16 @@ int t2v_adam_step_multi(t2v_ctx* ctx, void* stream, const int64_t* ptrs, const i
                         const int32_t* chunk_tensor, const int64_t* chunk_off, int nchunks, int chunk, double beta1,
                         double beta2, double eps);
 
-/* layout / dtype plumbing on the device */
+/* layout / dtype plumbing on the device.  nchw_to_nhwc: channels [C, dst_cs) of dst are written as zero.  nhwc_to_nchw:
+ * channels [C, src_cs) of src are ignored. */
 int t2v_nchw_to_nhwc(t2v_ctx* ctx, void* stream, const float* src, float* dst, int C, int H, int W, int dst_cs);
 int t2v_nhwc_to_nchw(t2v_ctx* ctx, void* stream, const float* src, float* dst, int C, int H, int W, int src_cs);
 /* ToTensor + Normalize(.5,.5) ($SP/torchvision/transforms/functional.py:38-60,206-208) of a
- * uint8 HWC(3) pose map into channels [c0,c0+3) of an NHWC fp32 buffer */
+ * uint8 HWC(3) pose map into channels [c0,c0+3) of an NHWC fp32 buffer; the other channels of dst are not touched */
 int t2v_pose_u8_to_f32(t2v_ctx* ctx, void* stream, const uint8_t* src_hwc3, float* dst, long npix, int dst_cs, int c0);
 /* util.tensor2im [SURVEY 3.2]: uint8((x+1)/2*255 clipped), same layout */
 int t2v_tensor2im_u8(t2v_ctx* ctx, void* stream, const float* x, uint8_t* y, long n);
+/* dst[pix][dst_c0 + c] = src[pix][src_c0 + c] for c < nc; every other channel of src is ignored, of dst not touched */
 int t2v_copy_channels(t2v_ctx* ctx, void* stream, const float* src, int src_cs, int src_c0, float* dst,
                       int dst_cs, int dst_c0, int nc, long npix);
 

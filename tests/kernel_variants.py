@@ -177,7 +177,19 @@ CONV_CASES = [
     _case("Q1_reflect_min_h2_nk3", 2, 70, 8, 24, 3, 1, 1, True, False, False, igemm("Q", 1, 0, 1, 2)),
     _case("Q1_stats_1x1_nk1", 40, 40, 4, 64, 1, 1, 0, False, False, True, igemm("Q", 1, 1, 0, 2)),
     _case("Q1_stats_reflect_nk4_offset", 33, 17, 12, 64, 3, 1, 1, True, False, True, igemm("Q", 1, 1, 1, 2), offset=100.0),
+    # Cin % 4 != 0 (x_cs > Cin: the pad K slots of every tap meet the storage lanes; tests/storage_lanes.py runs these
+    # geometries with junk in the lanes)
+    _case("Q1_stats_reflect_k3_cin3", 17, 19, 3, 64, 3, 1, 1, True, False, True, igemm("Q", 1, 1, 1, 2),
+          note="Cin 3 -> storage 4: nk 2"),
+    _case("Q1_stats_k4s2p2_cin6_disc", 16, 16, 6, 64, 4, 2, 2, False, False, True, igemm("Q", 1, 1, 0, 2),
+          note="the discriminators' first layer: Cin 6 -> storage 8, nk 4"),
+    _case("Q1_stats_k3s2_cin9_cout96", 33, 47, 9, 96, 3, 2, 1, False, False, True, igemm("Q", 1, 1, 0, 2),
+          note="Cin 9 -> storage 12; Cout 96 asks for 128x128 tiles, 4 of them fill the chip poorly: 64x64, N tail 32/64"),
+    _case("Q1_zero_s2_cin6_cout30", 35, 41, 6, 30, 3, 2, 1, False, False, False, igemm("Q", 1, 0, 0, 2),
+          note="Cin 6 -> storage 8 and Cout 30 -> storage 32"),
     _case("Q2_convT_odd_r3", 9, 11, 4, 32, 3, 2, 1, False, True, False, igemm("Q", 2, 0, 0, 3), op=0),
+    _case("Q2_stats_convT_cin5_r3", 9, 11, 5, 32, 3, 2, 1, False, True, True, igemm("Q", 2, 1, 0, 3),
+          note="Cin 5 -> storage 8: the phases have nk 1, 1, 1, 1 with 1, 2, 2, 4 taps"),
     _case("Q2_convT_b15_3840b_r3", 64, 64, 4, 32, 3, 2, 1, False, True, False, igemm("Q", 2, 0, 0, 3), batch=15,
           note="4 phases x 64 tiles x 15 = 3840 blocks < 4096"),
     _case("Q2_convT_b16_4096b_r2", 64, 64, 4, 32, 3, 2, 1, False, True, False, igemm("Q", 2, 0, 0, 2), batch=16,
@@ -893,7 +905,7 @@ TABLE = {
     "t2v::conv_igemm_kernel<t2v::TileCfg<32,2,2,1,1>,0,true,true,3>":
         Unreachable(_Q_REFLECT_RING3),
     "t2v::conv_igemm_kernel<t2v::TileCfg<32,2,2,1,1>,1,false,false,2>":
-        Cases(("Q1_zero_s2_odd_cout30", "Q1_zero_k3_nk4_b2",)),
+        Cases(("Q1_zero_s2_odd_cout30", "Q1_zero_k3_nk4_b2", "Q1_zero_s2_cin6_cout30",)),
     "t2v::conv_igemm_kernel<t2v::TileCfg<32,2,2,1,1>,1,false,false,3>":
         Unreachable('64x64 tiles with one phase always take RING 2 in launch_pad (Cfg::BM == 64 && nphases == 1); MODE 1 is single-phase by definition'),
     "t2v::conv_igemm_kernel<t2v::TileCfg<32,2,2,1,1>,1,false,true,2>":
@@ -901,11 +913,11 @@ TABLE = {
     "t2v::conv_igemm_kernel<t2v::TileCfg<32,2,2,1,1>,1,false,true,3>":
         Unreachable('64x64 tiles with one phase always take RING 2 in launch_pad (Cfg::BM == 64 && nphases == 1); MODE 1 is single-phase by definition'),
     "t2v::conv_igemm_kernel<t2v::TileCfg<32,2,2,1,1>,1,true,false,2>":
-        Cases(("Q1_stats_1x1_nk1",)),
+        Cases(("Q1_stats_1x1_nk1", "Q1_stats_k4s2p2_cin6_disc", "Q1_stats_k3s2_cin9_cout96",)),
     "t2v::conv_igemm_kernel<t2v::TileCfg<32,2,2,1,1>,1,true,false,3>":
         Unreachable('64x64 tiles with one phase always take RING 2 in launch_pad (Cfg::BM == 64 && nphases == 1); MODE 1 is single-phase by definition'),
     "t2v::conv_igemm_kernel<t2v::TileCfg<32,2,2,1,1>,1,true,true,2>":
-        Cases(("Q1_stats_reflect_nk4_offset",)),
+        Cases(("Q1_stats_reflect_nk4_offset", "Q1_stats_reflect_k3_cin3",)),
     "t2v::conv_igemm_kernel<t2v::TileCfg<32,2,2,1,1>,1,true,true,3>":
         Unreachable('64x64 tiles with one phase always take RING 2 in launch_pad (Cfg::BM == 64 && nphases == 1); MODE 1 is single-phase by definition'),
     "t2v::conv_igemm_kernel<t2v::TileCfg<32,2,2,1,1>,2,false,false,2>":
@@ -919,7 +931,7 @@ TABLE = {
     "t2v::conv_igemm_kernel<t2v::TileCfg<32,2,2,1,1>,2,true,false,2>":
         Cases(("Q2_stats_convT_b16_r2",)),
     "t2v::conv_igemm_kernel<t2v::TileCfg<32,2,2,1,1>,2,true,false,3>":
-        Cases(("Q2_stats_convT_nk124_r3",)),
+        Cases(("Q2_stats_convT_nk124_r3", "Q2_stats_convT_cin5_r3",)),
     "t2v::conv_igemm_kernel<t2v::TileCfg<32,2,2,1,1>,2,true,true,2>":
         Unreachable(_MODE2_REFLECT),
     "t2v::conv_igemm_kernel<t2v::TileCfg<32,2,2,1,1>,2,true,true,3>":

@@ -30,13 +30,14 @@ class HeaderError(ValueError):
 
 
 class Header:
-    """functions: name -> (return type, [parameter types]) as C spells them, names removed; signatures: name ->
-    (restype, argtypes); fields: struct name -> [(type, field)]; structs: struct name -> ctypes.Structure; constants:
-    name -> int.  All in the header's order."""
+    """functions: name -> (return type, [parameter types]) as C spells them, names removed; parameters: name -> [parameter
+    names], in the same order; signatures: name -> (restype, argtypes); fields: struct name -> [(type, field)]; structs:
+    struct name -> ctypes.Structure; constants: name -> int.  All in the header's order."""
 
     def __init__(self, text, name, base=None):
         self.name, self.base = name, base
         self.functions, self.signatures, self.fields, self.structs, self.constants, self.opaque = {}, {}, {}, {}, {}, set()
+        self.parameters = {}
         text = re.sub(r"//[^\n]*", " ", re.sub(r"/\*.*?\*/", " ", text, flags=re.S))
         code = []
         for line in text.split("\n"):
@@ -107,14 +108,16 @@ class Header:
         m = re.fullmatch(r"(.+?)\b(\w+) ?\(([^()]*)\)", decl)
         if not m:
             self._bad("neither a prototype (no function-pointer parameter), a struct, an enum nor an opaque typedef", decl)
-        params = []
+        params, names = [], []
         for p in ([] if m.group(3).strip() == "void" else m.group(3).split(",")):
             d = _DECLARATOR.fullmatch(p.strip())
             if not d or d.group(3):
                 self._bad("parameter `%s`: not `type name` (variadic, nameless or empty; no parameters is `(void)`)" % p.strip(), decl)
             params.append(self._spell(d.group(1)))
+            names.append(d.group(2))
         ret = self._spell(m.group(1))
         self.functions[m.group(2)] = (ret, params)
+        self.parameters[m.group(2)] = names
         self.signatures[m.group(2)] = (self.ctype(ret, decl, returned=True), [self.ctype(p, decl) for p in params])
 
     @staticmethod
