@@ -33,9 +33,20 @@ def list_images(root, pattern):
     return sorted(out)
 
 
-def pair_files(dir_a, dir_b, pattern="fake_B_*"):
-    """-> (paired relative paths, only under dir_a, only under dir_b), each sorted"""
+def pair_files(dir_a, dir_b, pattern="fake_B_*", by_stem=False):
+    """-> (paired relative paths, only under dir_a, only under dir_b), each sorted.
+    by_stem: files pair when their relative paths agree up to the extension (a tree of .png frames against one of .jpg
+    frames); a pair is then the tuple (path under dir_a, path under dir_b).  Of several files of one tree with the same
+    stem, the first in sorted order pairs and the others count as unpaired."""
     a, b = list_images(dir_a, pattern), list_images(dir_b, pattern)
+    if by_stem:
+        first_a, first_b = {}, {}
+        for paths, first in ((a, first_a), (b, first_b)):
+            for p in paths:
+                first.setdefault(os.path.splitext(p)[0], p)
+        return ([(first_a[k], first_b[k]) for k in sorted(first_a) if k in first_b],
+                [p for p in a if first_a[os.path.splitext(p)[0]] != p or os.path.splitext(p)[0] not in first_b],
+                [p for p in b if first_b[os.path.splitext(p)[0]] != p or os.path.splitext(p)[0] not in first_a])
     sa, sb = set(a), set(b)
     return [p for p in a if p in sb], [p for p in a if p not in sb], [p for p in b if p not in sa]
 
@@ -45,43 +56,47 @@ DECODE_BATCH = 32        # pairs per jpeg_decode.decode_files call under --gpu_d
 
 
 def _decoded_pairs(pairs, dir_a, dir_b, device, gpu_decode, fallback):
-    """yield (relative path, a, b): the two RGB images uint8 [H,W,3] of every pair -- host arrays from Pillow, or device
-    tensors from the GPU decoder (`fallback` collects the files Pillow decoded for it)"""
+    """pairs: [(path under dir_a, path under dir_b)].  yield (the path under dir_a, a, b): the two RGB images uint8 [H,W,3]
+    of every pair -- host arrays from Pillow, or device tensors from the GPU decoder (`fallback` collects the files Pillow
+    decoded for it)"""
     import numpy as np
     if not gpu_decode:
         from PIL import Image
-        for rel in pairs:
+        for rel, rel_b in pairs:
             with Image.open(os.path.join(dir_a, rel)) as im:
                 a = np.array(im.convert("RGB"))
-            with Image.open(os.path.join(dir_b, rel)) as im:
+            with Image.open(os.path.join(dir_b, rel_b)) as im:
                 b = np.array(im.convert("RGB"))
             yield rel, a, b
         return
     from . import jpeg_decode
     for at in range(0, len(pairs), DECODE_BATCH):
         batch = pairs[at:at + DECODE_BATCH]
-        files = [os.path.join(d, rel) for d in (dir_a, dir_b) for rel in batch]
+        files = [os.path.join(dir_a, rel) for rel, _ in batch] + [os.path.join(dir_b, rel) for _, rel in batch]
         blobs = []
         for f in files:
             with open(f, "rb") as fh:
                 blobs.append(fh.read())
         tensors, fell = jpeg_decode.decode_files(blobs, device)
         fallback.extend((files[i], reason) for i, reason in fell)
-        for j, rel in enumerate(batch):
+        for j, (rel, _) in enumerate(batch):
             yield rel, tensors[j], tensors[len(batch) + j]
 
 
 def compare_trees(dir_a, dir_b, pattern="fake_B_*", device="cuda:0", temporal=False, gpu_decode=False, fallback=None,
-                  temporal_flow="lk"):
+                  temporal_flow="lk", pair_by_stem=False):
     """-> the report: {"definition", "overall", "sequences": {dir: summary}, "unpaired_a", "unpaired_b", "size_mismatch"};
     temporal: every summary gains "temporal" (metrics.pool_temporal over the directory's consecutive pairs), the report
     "temporal_definition", "temporal_flow" (the estimator: lk, or lkhs = ops.optical_flow_u8 with the Horn-Schunck refinement)
     and "temporal_skipped" (second files of pairs that changed size or are narrower than 8 pixels).
-    gpu_decode: decode on the GPU (the same report); `fallback`, a list, receives (file, reason) of what Pillow decoded then"""
+    gpu_decode: decode on the GPU (the same report); `fallback`, a list, receives (file, reason) of what Pillow decoded then;
+    pair_by_stem: pair_files(by_stem=True) -- the report names a pair by its path under dir_a"""
     from ._xp import torch
     from . import metrics as M
     from . import ops
-    pairs, only_a, only_b = pair_files(dir_a, dir_b, pattern)
+    pairs, only_a, only_b = pair_files(dir_a, dir_b, pattern, pair_by_stem)
+    if not pair_by_stem:
+        pairs = [(p, p) for p in pairs]
     flow_kw = ops.temporal_flow_kwargs(temporal_flow)
     per_seq, mismatch, pending = {}, [], []
     t_pending, t_skipped, last = [], [], None      # last: (directory, device a, device b) of the previous paired file
@@ -136,6 +151,8 @@ def main(argv=None):
     ap.add_argument("--temporal_flow", default=None, choices=["lk", "lkhs"], help="with --temporal: the flow estimator, lk "
                     "(default) or lkhs = with the Horn-Schunck refinement; named in the report")
     ap.add_argument("--gpu_decode", action="store_true", help="decode the JPEG files on the GPU, in batches (the same report)")
+    ap.add_argument("--pair_by_stem", action="store_true", help="pair files whose relative paths agree up to the extension: a "
+                    "tree of .png frames (test.py --frame_format png) against one of .jpg frames")
     ap.add_argument("--json", default=None, metavar="OUT", help="write the report to this file")
     ap.add_argument("--gpu_ids", default="0")
     args = ap.parse_args(argv)
@@ -149,7 +166,8 @@ def main(argv=None):
         _xp.use_lean()          # no torch needed for an allocator and a stream (honoured when torch is not loaded yet)
     fallback = []
     rep = compare_trees(args.dir_a, args.dir_b, args.pattern, "cuda:%d" % int(str(args.gpu_ids).split(",")[0]), args.temporal,
-                        args.gpu_decode, fallback, **({"temporal_flow": args.temporal_flow} if args.temporal_flow else {}))
+                        args.gpu_decode, fallback, **({"temporal_flow": args.temporal_flow} if args.temporal_flow else {}),
+                        **({"pair_by_stem": True} if args.pair_by_stem else {}))
     if fallback:
         print("--gpu_decode: Pillow decoded %d file(s), the first: %s (%s)" % ((len(fallback),) + fallback[0]), file=sys.stderr)
     for seq, s in list(rep["sequences"].items()) + [("overall", rep["overall"])]:

@@ -60,6 +60,12 @@ class StepEncoder:
         self.d2h_bytes = 0
         self.encode_s = self.d2h_s = 0.0      # host time spent enqueueing the encode calls / the copies
 
+    def _encode(self, out, lengths):
+        ops.jpeg_encode_u8(self.batch, self.quality, out=out, lengths=lengths, workspace=self.workspace)
+
+    def _file(self, scan):
+        return jpeg.file_bytes(self.header, scan)
+
     def image(self, i):
         """frame i of the step being assembled: a uint8 device view [H,W,4]"""
         return self.batch.narrow(0, i, 1).view(self.H, self.W, 4)
@@ -72,7 +78,7 @@ class StepEncoder:
             self.host[slot] = torch.empty(need, dtype=torch.uint8, pin_memory=True)
         out, lengths, host = self.out[slot], self.lengths[slot], self.host[slot]
         t0 = time.perf_counter()
-        ops.jpeg_encode_u8(self.batch, self.quality, out=out, lengths=lengths, workspace=self.workspace)
+        self._encode(out, lengths)
         t1 = time.perf_counter()
         ops.copy_bytes_to_host(host, 0, lengths, 0, 4 * self.nimg)
         o = LENGTHS_BYTES
@@ -113,6 +119,6 @@ class StepEncoder:
             scan = buf[o:o + min(n, w)].tobytes()
             if i in rest:
                 scan += rest[i].numpy().tobytes()
-            files.append(jpeg.file_bytes(self.header, scan))
+            files.append(self._file(scan))
             o += w
         return files

@@ -125,7 +125,8 @@ _REAL_A_LUT = _real_A_u8(np.arange(256, dtype=np.uint8)).tobytes()      # the sa
 
 
 class _JpegStep:
-    """--gpu_jpeg: the frames of one step and geometry whose JPEG scans one encode call produced (run_test's frame loop)"""
+    """--gpu_jpeg / --frame_format png: the frames of one step and geometry whose files one encode call produced (run_test's
+    frame loop)"""
     __slots__ = ("encoder", "step", "paths")
 
     def __init__(self, encoder, step, paths):
@@ -222,7 +223,10 @@ def run_test(opt, model=None, device=None, dataset=None):
     want_jpeg = bool(getattr(opt, "gpu_jpeg", False))
     jpeg_quality = int(getattr(opt, "jpeg_quality", None) or 75)
     jpeg_state, jpeg_refused = {}, set()      # (H, W, frames per step) -> StepEncoder; geometries the encoder does not take
-    vis = Visualizer(opt, quality=jpeg_quality if want_jpeg else None)
+    # --frame_format png: lossless files, encoded on the GPU as well (ops.png_encode_u8) and handled like the JPEG steps
+    want_png = getattr(opt, "frame_format", "jpg") == "png"
+    want_encoded, frame_ext = want_jpeg or want_png, ".png" if want_png else ".jpg"
+    vis = Visualizer(opt, quality=jpeg_quality if want_jpeg else None, ext=frame_ext)
     dev = torch.device(device)
     cs = ops.round_up(3 * opt.n_frames_G, 4)
     pinned = {}      # shape -> ring of 3 pinned host buffers (allocating pinned memory per frame costs ~0.2 ms)
@@ -261,7 +265,7 @@ def run_test(opt, model=None, device=None, dataset=None):
             files = p.encoder.files(p.step)      # (waits for the step's event)
             ops.check_async_errors()
             for m, a_path in enumerate(p.paths):
-                vis.save_bytes({"real_A": files[2 * m + 1], "fake_B": files[2 * m]}, a_path)
+                vis.save_bytes({"real_A": files[2 * m + 1], "fake_B": files[2 * m]}, a_path, frame_ext)
 
         def finish(p):
             if isinstance(p, _JpegStep):
@@ -311,7 +315,10 @@ def run_test(opt, model=None, device=None, dataset=None):
             round trip) of every member into one batch, ONE encode call, then the lengths and a first window of every scan
             to a pinned buffer (jpeg_frames.StepEncoder); no host synchronisation -- finish_jpeg waits for the step's event"""
             enc = jpeg_state.get((H, W, len(members)))
-            if enc is None:
+            if enc is None and want_png:
+                from .png_frames import StepEncoder
+                enc = jpeg_state[(H, W, len(members))] = StepEncoder(H, W, 2 * len(members), dev)
+            elif enc is None:
                 from .jpeg_frames import StepEncoder
                 enc = jpeg_state[(H, W, len(members))] = StepEncoder(H, W, 2 * len(members), jpeg_quality, dev)
             t1 = time.perf_counter()
@@ -374,8 +381,8 @@ def run_test(opt, model=None, device=None, dataset=None):
                     outs = model.inference_nhwc_batch([L.window for _, L, _ in members], [L.rec for _, L, _ in members])
                 split["generator_s"] = split.get("generator_s", 0.0) + time.perf_counter() - tg
                 compare = []      # --metrics: after EVERY member's D2H event, so that no frame's JPEG waits for a comparison
-                if want_jpeg and (gh, gw) not in jpeg_refused:
-                    if ops.jpeg_supported(gh, gw):
+                if want_encoded and (gh, gw) not in jpeg_refused:
+                    if ops.png_supported(gh, gw) if want_png else ops.jpeg_supported(gh, gw):
                         encode_group(gh, gw, members, outs, now, compare)
                         for k, L, data, u8 in compare:
                             t3 = time.perf_counter()
@@ -383,8 +390,8 @@ def run_test(opt, model=None, device=None, dataset=None):
                             split["metrics_s"] = split.get("metrics_s", 0.0) + time.perf_counter() - t3
                         continue
                     jpeg_refused.add((gh, gw))
-                    print("warning: --gpu_jpeg: the encoder does not take %dx%d frames; these are written by Pillow"
-                          % (gh, gw), file=sys.stderr)
+                    print("warning: %s: the encoder does not take %dx%d frames; these are written by Pillow"
+                          % ("--frame_format png" if want_png else "--gpu_jpeg", gh, gw), file=sys.stderr)
                 for (k, L, data), out in zip(members, outs):
                     t1 = time.perf_counter()
                     u8 = ops.tensor2im_u8(out)
@@ -459,10 +466,11 @@ def run_test(opt, model=None, device=None, dataset=None):
     marks["to_last_jpeg_s"] = time.perf_counter() - t_start
     d2h_bytes = counters["d2h_bytes"] + sum(enc.d2h_bytes for enc in jpeg_state.values())
     marks["d2h_bytes_per_frame"] = d2h_bytes // counters["n"] if counters["n"] else 0
-    if want_jpeg:
-        split["jpeg_s"] = sum(enc.encode_s for enc in jpeg_state.values())
+    if want_encoded:
+        key = "png" if want_png else "jpeg"
+        split[key + "_s"] = sum(enc.encode_s for enc in jpeg_state.values())
         split["d2h_s"] = split.get("d2h_s", 0.0) + sum(enc.d2h_s for enc in jpeg_state.values())
-        split["jpeg_second_copies"] = sum(enc.second_copies for enc in jpeg_state.values())
+        split[key + "_second_copies"] = sum(enc.second_copies for enc in jpeg_state.values())
     videos = []
     if getattr(opt, "write_video", False):
         # the reference's next stage (image2video*.py, text2video_audio.sh:44) on the frames just written; under

@@ -836,6 +836,79 @@ def jpeg_encode_u8(images, quality=75, out=None, lengths=None, workspace=None):
 
 
 # ----------------------------------------------------------------------------------------------------------------------
+# PNG encoding (libt2v_png.so, include/t2v_png.h): complete files, nothing is added on the host
+# ----------------------------------------------------------------------------------------------------------------------
+_png_workspace = {}      # device -> uint8 workspace of t2v_png_encode_u8 (grown on demand; uses are stream-ordered)
+
+
+def _png():
+    from . import _pnglib
+    return _pnglib
+
+
+def png_supported(H, W):
+    """whether png_encode_u8 takes H x W images (t2v_png_supported)"""
+    return bool(_png().load().t2v_png_supported(int(H), int(W)))
+
+
+def png_file_capacity(H, W):
+    """bytes no file of an H x W image exceeds (t2v_png_file_capacity; 0: a geometry png_encode_u8 refuses)"""
+    return int(_png().load().t2v_png_file_capacity(int(H), int(W)))
+
+
+def png_workspace_bytes(H, W, nimg):
+    """bytes of workspace png_encode_u8 needs for nimg H x W images (0: a call it refuses)"""
+    return int(_png().load().t2v_png_workspace_bytes(int(H), int(W), int(nimg)))
+
+
+def png_encode_u8(images, out=None, lengths=None, workspace=None):
+    """Lossless PNG files of uint8 device images (t2v_png_encode_u8, include/t2v_png.h): images is a contiguous uint8
+    device tensor [N,H,W,3|4] or [H,W,3|4] (R, G, B in channels 0..2; a fourth channel is ignored).
+    -> (out, lengths): out a uint8 device tensor [N, capacity] whose row i starts with image i's complete file (signature
+    ... IEND), lengths an int32 device tensor [N] of the files' byte lengths.
+    out: that tensor to write instead, any capacity >= 1 per row: a file longer than the row is reported through
+    lengths[i] > capacity, its first `capacity` bytes are valid and nothing behind them is written (default: rows of
+    png_file_capacity(H, W) bytes, which every file fits).  lengths: an int32 device tensor [N] to write instead.
+    workspace: a uint8 device tensor of at least png_workspace_bytes(H, W, N) bytes, 256-byte aligned (default: one kept
+    per device).  One memset and seven launches on the current stream, no host synchronisation; an unsupported geometry
+    (png_supported) or an argument that does not fit raises with nothing launched."""
+    P = _png()
+    context()
+    if not (images.is_cuda and images.dtype == torch.uint8 and images.is_contiguous() and images.dim() in (3, 4)
+            and images.shape[-1] in (3, 4)):
+        raise ValueError("png_encode_u8: images must be a contiguous uint8 device tensor [N,H,W,3|4] or [H,W,3|4]")
+    N = images.shape[0] if images.dim() == 4 else 1
+    H, W, cs = (int(v) for v in images.shape[-3:])
+    if not png_supported(H, W):
+        raise ValueError("png_encode_u8: %dx%d is outside %d..%d per dimension" % (H, W, P.MIN_DIM, P.MAX_DIM))
+    if not 1 <= N <= P.MAX_IMAGES:
+        raise ValueError("png_encode_u8: %d images (1..%d per call)" % (N, P.MAX_IMAGES))
+    dev = images.device
+    if out is None:
+        out = torch.empty(N, png_file_capacity(H, W), dtype=torch.uint8, device=dev)
+    if not (out.is_cuda and out.dtype == torch.uint8 and out.is_contiguous() and out.dim() == 2 and out.shape[0] == N
+            and out.shape[1] >= 1):
+        raise ValueError("png_encode_u8: out must be a contiguous uint8 device tensor [%d, capacity]" % N)
+    if lengths is None:
+        lengths = torch.empty(N, dtype=torch.int32, device=dev)
+    if not (lengths.is_cuda and lengths.dtype == torch.int32 and lengths.is_contiguous() and lengths.numel() == N):
+        raise ValueError("png_encode_u8: lengths must be a contiguous int32 device tensor [%d]" % N)
+    need = png_workspace_bytes(H, W, N)
+    if workspace is None:
+        workspace = _png_workspace.get(str(dev))
+        if workspace is None or workspace.numel() < need:
+            workspace = _png_workspace[str(dev)] = torch.empty(need, dtype=torch.uint8, device=dev)
+    elif not (workspace.is_cuda and workspace.dtype == torch.uint8 and workspace.is_contiguous()):
+        raise ValueError("png_encode_u8: workspace must be a contiguous uint8 device tensor")
+    if workspace.numel() < need or workspace.data_ptr() % 256:
+        raise ValueError("png_encode_u8: workspace holds %d bytes at an address that is %d mod 256; %d images of %dx%d need "
+                         "%d aligned bytes" % (workspace.numel(), workspace.data_ptr() % 256, N, H, W, need))
+    P.check(P.load().t2v_png_encode_u8(_stream(), _p(images), cs, H, W, N, _p(workspace), _p(out), out.shape[1], _p(lengths)),
+            "encode_u8")
+    return out, lengths
+
+
+# ----------------------------------------------------------------------------------------------------------------------
 # JPEG decoding (libt2v_jpegdec.so, include/t2v_jpeg_decode.h; the host part: text2video_amd/jpeg.py parse())
 # ----------------------------------------------------------------------------------------------------------------------
 _jpegdec_workspace = {}      # device -> uint8 workspace of t2v_jpegdec_decode_u8 (grown on demand; uses are stream-ordered)

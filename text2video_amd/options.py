@@ -161,9 +161,19 @@ class TestOptions(BaseOptions):
         g("--gpu_jpeg", action="store_true", help="encode fake_B_*.jpg / real_A_*.jpg on the GPU (ops.jpeg_encode_u8: the "
           "bytes Pillow writes) instead of copying every frame to the host and encoding it on threads there")
         g("--jpeg_quality", type=int, default=None, help="with --gpu_jpeg: the JPEG quality, 1..100 (default 75, Pillow's)")
+        g("--frame_format", type=str, default="jpg", choices=["jpg", "png"], help="jpg (default): fake_B_*.jpg / real_A_*.jpg as "
+          "always.  png: the same frames as lossless fake_B_*.png / real_A_*.png, encoded on the GPU (ops.png_encode_u8; a "
+          "geometry it refuses is written by Pillow); not with --gpu_jpeg / --jpeg_quality.  vid2vid/image2video*.py and the "
+          "mux of --write_video / the pipeline take JPEG frames only: a PNG tree is for evaluation "
+          "(python -m text2video_amd.evaluate --pair_by_stem), a later re-encode or a regression diff")
 
     def parse(self, argv=None, save=False):
         opt = super().parse(argv, save)
+        if opt.frame_format == "png" and (opt.gpu_jpeg or opt.jpeg_quality is not None):
+            self.parser.error("--frame_format png with --gpu_jpeg / --jpeg_quality: those are the JPEG writer's; PNG frames are "
+                              "lossless and always encoded on the GPU")
+        if opt.frame_format == "png" and getattr(opt, "write_video", False):
+            self.parser.error("--frame_format png with --write_video: the mux (like vid2vid/image2video*.py) takes JPEG frames only")
         if opt.jpeg_quality is not None and not opt.gpu_jpeg:
             self.parser.error("--jpeg_quality %d: the quality of --gpu_jpeg, which is not given" % opt.jpeg_quality)
         if opt.jpeg_quality is not None and not 1 <= opt.jpeg_quality <= 100:
